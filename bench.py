@@ -15,6 +15,15 @@ counters.  Inputs are resident in HBM before the timed region.
 
 Prints ONE JSON line (rank 0).  ``value`` = changes that entered history over
 all ranks / max-over-ranks wall time of the K timed steps.
+
+A plain run (``--gpus 1 --steps K --warmup W``) does what that headline needs and
+nothing else: generate the shard, warm up, time the K steps, print the line.
+``--dump-outputs DIR`` also writes what the last timed step computed (a fixed
+sample of documents) as ``DIR/<name>.npy``.  ``--full`` adds every other leg:
+per-kernel roofline, oracle parity sample, CPU baselines, the PCIe-inclusive and
+raw-blocks legs, the resident-store legs, the Node DocBackend legs, the
+actor-major arrival order, the rocprofv3 PMC traffic passes, and (N > 1) the
+clock exchange; it also writes the detail file and the progress log.
 """
 from __future__ import annotations
 
@@ -38,18 +47,23 @@ WORKLOAD_KIND = {"C1": "map sets, 2 alternating actors", "C2": "map LWW sets + c
 
 
 _T0 = time.time()
-_PROGRESS = {"stderr": False, "file": None}
+_PROGRESS = {"stderr": False, "file": None, "log": False}
 OUT_DIR = os.path.join(HERE, "gpurun_out")
 LINE_MAX = 4096          # the one stdout line the driver parses stays far below this
+DUMP_DOCS = 4096         # documents sampled by --dump-outputs (~10 KB of float64 each at C4)
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 0x484D
 
 
 def _progress(msg: str) -> None:
-    """A progress line into gpurun_out/bench_progress.log (a long run keeps writing under
-    gpurun_out/), and on stderr only with --progress: nothing follows the JSON line in the
-    captured output."""
+    """A progress line into bench_progress.log in the output folder (--full only: a long run
+    keeps writing there), and on stderr only with --progress: nothing follows the JSON line in
+    the captured output."""
     line = f"[bench {time.time() - _T0:7.1f}s] {msg}"
     if _PROGRESS["stderr"]:
         print(line, file=sys.stderr, flush=True)
+    if not _PROGRESS["log"]:
+        return
     try:
         if _PROGRESS["file"] is None:
             os.makedirs(OUT_DIR, exist_ok=True)
@@ -115,14 +129,24 @@ def _side(name, fn):
         return {"error": f"{type(ex).__name__}: {ex}"[:300]}
 
 
-def compact_line(full: dict) -> dict:
+def compact_line(full: dict, plain: bool = False) -> dict:
     """The one JSON line the driver parses: the headline, its roofline and CPU baseline, and a
     one-level summary of every side leg.  The whole record (per-round tables, Node run lists,
-    PMC detail) goes to the detail file named in `detail`."""
+    PMC detail) goes to the detail file named in `detail`.  `plain`: the record of a run without
+    --full, which measured the headline only; the line then holds no roofline, baseline or leg."""
     line = {k: full.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
                                      "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
     line["value"], line["ms_per_step"] = _r(line["value"], 6), _r(line["ms_per_step"], 6)
     line["config"] = full.get("config")
+    if plain:
+        for k in ("unsupported_docs", "error_docs", "dump_outputs", "ranks_note"):
+            if full.get(k) is not None:
+                line[k] = full[k]
+        line["event_ms_per_step"] = _r(full.get("event_ms_per_step"), 5)
+        line["full"] = False
+        if full.get("detail_file"):
+            line["detail"] = full["detail_file"]
+        return line
     ro = full.get("roofline") or {}
     line["roofline"] = {k: _r(ro.get(k), 6) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic",
                                                      "kernel", "kernel_ms", "alg_bytes")}
@@ -185,13 +209,15 @@ def compact_line(full: dict) -> dict:
     line["legs"] = {k: {a: b for a, b in v.items() if b is not None} for k, v in legs.items()}
     if full.get("ranks_note"):
         line["ranks_note"] = full["ranks_note"]
+    if full.get("dump_outputs"):
+        line["dump_outputs"] = full["dump_outputs"]
     line["detail"] = full.get("detail_file")
     return line
 
 
-def dump_line(full: dict) -> str:
+def dump_line(full: dict, plain: bool = False) -> str:
     """compact_line as text, trimmed below LINE_MAX by dropping side legs if it ever grows."""
-    line = compact_line(full)
+    line = compact_line(full, plain)
     s = json.dumps(line, separators=(",", ":"))
     for k in list(line.get("legs", {}))[::-1]:
         if len(s) < LINE_MAX:
@@ -262,8 +288,15 @@ def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="GPUs of this node (ranks); without WORLD_SIZE in the environment, N > 1 starts N ranks")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline (roofline, oracle parity, CPU baselines, end-to-end, resident "
+                         "store, Node, arrival order, PMC traffic, clock exchange), the detail file and the progress "
+                         "log; the --no-* / --*-docs options below shape these legs and do nothing without --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; a fixed sample of "
+                         "documents, the same from run to run with the same arguments)")
     ap.add_argument("--docs", type=int, default=1_000_000, help="documents per GPU")
     ap.add_argument("--config", default="C4")
     ap.add_argument("--cpu-sample-docs", type=int, default=200_000)
@@ -289,10 +322,15 @@ def main() -> int:
                     help="override the config's arrival order (0 generation, 1 actor-major as RepoBackend.loadDocument "
                          "concatenates, 2 shuffled)")
     ap.add_argument("--progress", action="store_true", help="progress lines on stderr too")
-    ap.add_argument("--detail", default=os.path.join(OUT_DIR, "bench_detail.json"),
-                    help="file for the full record (the stdout line is its compact summary)")
+    ap.add_argument("--detail", default=None,
+                    help="file for the whole record (the stdout line is its compact summary); with --full it "
+                         "defaults to bench_detail.json in the output folder")
     args = ap.parse_args()
-    _PROGRESS["stderr"] = args.progress
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.detail is None and args.full:
+        args.detail = os.path.join(OUT_DIR, "bench_detail.json")
+    _PROGRESS["stderr"], _PROGRESS["log"] = args.progress, args.full
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
         # no launcher: this process starts the ranks and touches no GPU itself (the count
@@ -348,8 +386,12 @@ def main() -> int:
     wall = time.perf_counter() - t_start
     _progress(f"timed steps: {wall * 1e3 / args.steps:.3f} ms/step")
     ev_ms = ev0.elapsed_time(ev1)
+    dumped = None
+    if args.dump_outputs:
+        dumped = _dump_outputs(run, batch, dev, args.dump_outputs, rank)
     # per-launch kernel durations (both kernels): HIP events on the launch stream, extra launches
-    kern = run.kernel_roofline(max(3, min(args.steps, 10)))
+    kern = run.kernel_roofline(max(3, min(args.steps, 10))) if args.full else None
+    side = args.full and rank == 0 and ws == 1          # the legs measured on one GPU only
     nd, nc, no, S = batch.n_docs, len(batch.changes), len(batch.ops), batch.a_stride
     docs_res = run.docs_res
     applied = int(docs_res["hist_len"].astype(np.int64).sum())
@@ -371,7 +413,7 @@ def main() -> int:
     value = applied_all * args.steps / wall_max
     ms_per_step = wall_max * 1000.0 / args.steps
     xchg = None
-    if ws > 1:
+    if ws > 1 and args.full:
         # off the merge's critical path and outside `value`: a failure here is reported in the
         # line instead of costing the whole scaling measurement.  It has not run on a multi-GPU
         # node yet, so a watchdog bounds it: past XCHG_TIMEOUT_S rank 0 prints the line with the
@@ -400,7 +442,7 @@ def main() -> int:
     # spot parity against the oracle on a sample (checker only; not timed)
     parity = None
     cpu = cpu_mt = None
-    if rank == 0 and ws == 1 and args.check_docs > 0:      # checker only: rank 0 at N=1
+    if side and args.check_docs > 0:                       # checker only: rank 0 at N=1
         import oracle.oracle as O
         k = min(args.check_docs, nd)
         sub = _subbatch(batch, k)
@@ -408,7 +450,7 @@ def main() -> int:
         o = O.merge(sub, threads=min(16, os.cpu_count() or 1))
         parity = bool(_same(sub, g, o))
         _progress(f"oracle parity sample: {parity}")
-    if rank == 0 and ws == 1 and not args.no_cpu:          # CPU legs: rank 0 at N=1 only
+    if side and not args.no_cpu:                           # CPU legs: rank 0 at N=1 only
         import oracle.oracle as O
         ns = min(args.cpu_sample_docs, nd)
         cs = _subbatch(batch, ns)
@@ -432,7 +474,7 @@ def main() -> int:
     # end to end: host tables -> device -> merge -> host results (hm_merge_host, PCIe included);
     # reported beside the kernel rate, never as `value`
     e2e = None
-    if rank == 0 and ws == 1 and not args.no_e2e:
+    if side and not args.no_e2e:
         eng.merge(_subbatch(batch, min(nd, 1000)))          # allocate staging once
         t = time.perf_counter()
         ge = eng.merge(batch)
@@ -461,14 +503,14 @@ def main() -> int:
     # from raw hypercore blocks: JSON blocks (as Block.pack writes them) -> the native
     # multi-threaded decoder (hm_decode_blocks) -> hm_merge_host; reported beside `value`
     from_blocks = None
-    if rank == 0 and ws == 1 and not args.no_e2e and args.config in ("C1", "C2", "C4") and args.block_docs > 0:
+    if side and not args.no_e2e and args.config in ("C1", "C2", "C4") and args.block_docs > 0:
         from_blocks = _side("from_blocks", lambda: _from_blocks(eng, batch, cfg, args))
     # applyRemoteChanges on resident documents: every document of the shard resident in the
     # store, then rounds in which each receives its next 1-2 changes (DocBackend.ts:169-185)
     incremental = None
     incremental_text = None
     incremental_c5 = None
-    if rank == 0 and ws == 1 and not args.no_incremental and args.config == "C4" and args.arrival is None:
+    if side and not args.no_incremental and args.config == "C4" and args.arrival is None:
         incremental = _side("resident C4", lambda: _incremental(eng, batch, args, oracle_docs=200))
         _progress("resident C4 leg done")
         # the same event on text documents (C3: RGA inserts / deletes on the resident element order)
@@ -493,13 +535,13 @@ def main() -> int:
             del c5
     # the Node host path end to end through the DocBackend message API (C2 sample)
     node = None
-    if rank == 0 and ws == 1 and not args.no_node:
+    if side and not args.no_node:
         node = _side("node legs", lambda: _node_e2e(args))
         _progress("node legs done")
     # the same workload in RepoBackend.loadDocument's arrival order (actor-major concatenation,
     # src/RepoBackend.ts:242-248): changes whose deps come later in the array wait in the queue
     orders = None
-    if rank == 0 and ws == 1 and args.arrival is None and args.config == "C4" and not args.no_orders:
+    if side and args.arrival is None and args.config == "C4" and not args.no_orders:
         try:
             del run
             torch.cuda.empty_cache()
@@ -529,7 +571,7 @@ def main() -> int:
             orders = {"actor_major": {"error": f"{type(ex).__name__}: {ex}"[:300]}}
 
     traffic = None
-    if rank == 0 and ws == 1 and not args.no_traffic:
+    if side and not args.no_traffic:
         traffic = _pmc_traffic(args, kern["kernel"])
         _progress("merge kernel PMC passes done")
         if incremental and incremental.get("roofline"):
@@ -543,27 +585,30 @@ def main() -> int:
 
     if rank == 0:
         line = _line(args, ws, value, ms_per_step, nd, nc, no, batch, kern, traffic, ev_ms, xchg)
-        line.update({
-            "cpu_baseline": cpu, "cpu_parallel": cpu_mt, "end_to_end": e2e, "from_blocks": from_blocks,
-            "resident_incremental": incremental, "resident_incremental_text": incremental_text,
-            "resident_incremental_c5": incremental_c5, "node_docbackend": node,
-            "arrival_orders": orders,
-            "host": _host_info(),
-            "parity_sample_ok": parity, "unsupported_docs": unsupported, "error_docs": errors,
-            "gen_s": round(gen_s, 2),
-        })
+        line["full"], line["dump_outputs"] = args.full, dumped
+        line.update({"unsupported_docs": unsupported, "error_docs": errors, "gen_s": round(gen_s, 2)})
+        if args.full:
+            line.update({
+                "cpu_baseline": cpu, "cpu_parallel": cpu_mt, "end_to_end": e2e, "from_blocks": from_blocks,
+                "resident_incremental": incremental, "resident_incremental_text": incremental_text,
+                "resident_incremental_c5": incremental_c5, "node_docbackend": node,
+                "arrival_orders": orders,
+                "host": _host_info(),
+                "parity_sample_ok": parity,
+            })
 
         line["detail_file"] = None
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
-            with open(args.detail, "w") as f:
-                json.dump(line, f, indent=1)
-            line["detail_file"] = os.path.relpath(os.path.abspath(args.detail), HERE)
-        except OSError as ex:
-            _progress(f"detail file not written: {ex}")
+        if args.detail is not None:                  # (a plain run writes it only when asked to)
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
+                with open(args.detail, "w") as f:
+                    json.dump(line, f, indent=1)
+                line["detail_file"] = os.path.relpath(os.path.abspath(args.detail), HERE)
+            except OSError as ex:
+                _progress(f"detail file not written: {ex}")
         _progress("done")
         sys.stderr.flush()
-        print(dump_line(line), flush=True)
+        print(dump_line(line, plain=not args.full), flush=True)
     if ws > 1:
         dist.destroy_process_group()
     return 0
@@ -583,10 +628,11 @@ def _line(args, ws, value, ms_per_step, nd, nc, no, batch, kern, traffic, ev_ms,
                                f"{nc / max(nd, 1):.0f} changes/doc, {WORKLOAD_KIND.get(args.config, '')}"
                                + ("" if args.arrival is None else f", arrival order {ARRIVAL[args.arrival]}"), "docs_per_gpu": nd,
                    "changes_per_gpu": nc, "ops_per_gpu": no, "parallelism": f"doc-shard{ws}"},
-        "roofline": {"bound": "hbm", "achieved": kern["achieved"], "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                     "frac": kern["frac"], "traffic": traffic["bytes"] if traffic else None,
-                     "kernel": kern["kernel"], "kernel_ms": kern["kernel_ms"], "alg_bytes": kern["alg_bytes"],
-                     "kernels": kern["kernels"], "traffic_detail": traffic},
+        "roofline": None if kern is None else {
+            "bound": "hbm", "achieved": kern["achieved"], "peak": PEAK_HBM_GBS, "unit": "GB/s",
+            "frac": kern["frac"], "traffic": traffic["bytes"] if traffic else None,
+            "kernel": kern["kernel"], "kernel_ms": kern["kernel_ms"], "alg_bytes": kern["alg_bytes"],
+            "kernels": kern["kernels"], "traffic_detail": traffic},
         "cpu_baseline": None, "cpu_parallel": None,
         "event_ms_per_step": ev_ms / args.steps,
         "clock_exchange": xchg,
@@ -1063,6 +1109,70 @@ class _Resident:
         assert achieved / PEAK_HBM_GBS <= 1.0, f"roofline fraction above 1: {ks}"
         return {"kernel": dom["kernel"], "kernel_ms": dom["ms"], "alg_bytes": dom["alg_bytes"],
                 "achieved": achieved, "frac": achieved / PEAK_HBM_GBS, "kernels": ks}
+
+
+def _ranges(off, cnt):
+    """The indices of the concatenated ranges [off[i], off[i] + cnt[i])."""
+    off, cnt = off.astype(np.int64), cnt.astype(np.int64)
+    first = np.cumsum(cnt) - cnt
+    return np.repeat(off - first, cnt) + np.arange(int(cnt.sum()), dtype=np.int64)
+
+
+def _as_f64(a):
+    """A result table as float64, one column per field (a 64-bit field as its low and high 32-bit
+    words, so every value is exact); a plain integer array converts as it is."""
+    if a.dtype.names is None:
+        return a.astype(np.float64)
+    cols = []
+    for f in a.dtype.names:
+        x = a[f]
+        if x.dtype.itemsize == 8:
+            x = x.astype(np.uint64)
+            cols += [(x & np.uint64(0xFFFFFFFF)).astype(np.float64), (x >> np.uint64(32)).astype(np.float64)]
+        else:
+            cols.append(x.astype(np.float64))
+    return np.stack(cols, axis=1) if len(a) else np.zeros((0, len(cols)), np.float64)
+
+
+def _dump_outputs(run, batch, dev, out_dir, rank):
+    """What the last step left in the result tables a caller of hm_merge_device receives, for a
+    fixed (seeded) sample of documents in ascending order, as float64 `<name>.npy` files in
+    `out_dir` (rank r > 0: `<name>.rank<r>.npy`): per document `docs` (the hm_doc_result fields),
+    `clock`, `back_clock`, `heads` (a_stride columns); per change of those documents `hist` and
+    `all_deps`; per register `regs`; per document its first n_surv rows of `surv` (the rows a
+    caller reads).  The sample is gathered on the device; it halves until the files fit
+    DUMP_MAX_BYTES.  Returns a summary for the result line."""
+    import torch
+    from hypermerge_amd.columnar import DOC_RESULT_DT, REG_RESULT_DT, SURV_RESULT_DT
+    nd, S = batch.n_docs, batch.a_stride
+    bd = batch.docs
+
+    def take(t, width, idx):
+        return t.view(t.numel() // width, width)[torch.from_numpy(idx).to(dev)].cpu().numpy()
+
+    k = min(nd, DUMP_DOCS)
+    while True:
+        sel = np.arange(nd, dtype=np.int64) if k >= nd else \
+            np.sort(np.random.default_rng(DUMP_SEED).choice(nd, k, replace=False)).astype(np.int64)
+        docs = take(run.r_docs, 32, sel).reshape(-1).view(DOC_RESULT_DT)
+        ci = _ranges(bd["change_off"][sel], bd["n_changes"][sel])
+        out = {"docs": docs,
+               "clock": take(run.r_clock, S, sel).view(np.uint32), "back_clock": take(run.r_bclock, S, sel).view(np.uint32),
+               "heads": take(run.r_heads, S, sel).view(np.uint32),
+               "hist": take(run.r_hist, 1, ci).reshape(-1), "all_deps": take(run.r_ad, S, ci).view(np.uint32),
+               "regs": take(run.r_regs, 16, _ranges(bd["reg_off"][sel], bd["n_regs"][sel])).reshape(-1).view(REG_RESULT_DT),
+               "surv": take(run.r_surv, 16, _ranges(bd["op_off"][sel], np.minimum(docs["n_surv"], bd["n_ops"][sel])))
+               .reshape(-1).view(SURV_RESULT_DT)}
+        out = {n: _as_f64(a) for n, a in out.items()}
+        total = sum(a.nbytes for a in out.values())
+        if total <= DUMP_MAX_BYTES or k <= 1:
+            break
+        k //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    for n, a in out.items():
+        np.save(os.path.join(out_dir, n + (".npy" if rank == 0 else f".rank{rank}.npy")), a)
+    return {"dir": out_dir, "docs": int(len(sel)), "of": int(nd), "bytes": int(total), "dtype": "float64",
+            "arrays": sorted(out)}
 
 
 def _host_info():

@@ -151,3 +151,37 @@ def test_failed_side_legs_keep_the_headline():
     assert line["legs"]["from_blocks"] == {"error": "OSError: y"}
     assert line["legs"]["actor_major"] == {"error": "MemoryError: z"}
     assert line["legs"]["resident_c4"]["speedup"] > 1
+
+
+def test_plain_line_holds_the_headline_only():
+    """Without --full the run measures the headline alone, and its line says so: the headline
+    keys with the values of the record, and no roofline, baseline or side leg."""
+    import json
+    b = _bench()
+    full = json.load(open(os.path.join(ROOT, "profiles", "r05", "final4", "bench_line.json")))
+    full.update(full=False, detail_file=None, dump_outputs={"dir": "out", "docs": 4096})
+    s = b.dump_line(full, plain=True)
+    assert len(s) < 2048 and "\n" not in s
+    line = json.loads(s)
+    for k in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "dtype", "config",
+              "unsupported_docs", "error_docs"):
+        assert line[k] == full[k], k
+    assert abs(line["value"] - full["value"]) / full["value"] < 1e-5
+    assert abs(line["ms_per_step"] - full["ms_per_step"]) / full["ms_per_step"] < 1e-5
+    assert line["full"] is False and line["dump_outputs"]["docs"] == 4096
+    for k in ("roofline", "cpu_baseline", "cpu_parallel", "legs", "parity_sample_ok", "clock_exchange", "detail"):
+        assert k not in line, k
+
+
+def test_dump_helpers():
+    """--dump-outputs' host side: the rows of a sample's documents, and tables as exact float64."""
+    import numpy as np
+    b = _bench()
+    assert b._ranges(np.array([5, 0, 10], np.uint32), np.array([2, 0, 3], np.uint32)).tolist() == [5, 6, 10, 11, 12]
+    assert b._ranges(np.zeros(0, np.uint32), np.zeros(0, np.uint32)).tolist() == []
+    a = np.zeros(2, np.dtype([("op", "<u4"), ("vtag", "<u4"), ("value", "<u8")]))
+    a["op"], a["vtag"], a["value"] = [1, 0xFFFFFFFF], [3, 4], [(1 << 63) + 5, 7]
+    f = b._as_f64(a)
+    assert f.dtype == np.float64 and f.tolist() == [[1, 3, 5, 1 << 31], [0xFFFFFFFF, 4, 7, 0]]
+    assert b._as_f64(a[:0]).shape == (0, 4)
+    assert b._as_f64(np.array([-1, 2], np.int32)).tolist() == [-1.0, 2.0]

@@ -12,7 +12,7 @@ for rep in range(int(os.environ.get("ABL_REPS", "1"))):
     for so in sys.argv[1:]:
         env = dict(os.environ, HMGPU_LIB=os.path.abspath(so))
         det = os.path.join(tempfile.gettempdir(), f"abl_{os.getpid()}_{os.path.basename(so)}.json")
-        out = subprocess.run([sys.executable, os.path.join(R, "bench.py"), "--steps", os.environ.get("ABL_STEPS", "10"),
+        out = subprocess.run([sys.executable, os.path.join(R, "bench.py"), "--full", "--steps", os.environ.get("ABL_STEPS", "10"),
                               "--warmup", "2", "--no-cpu", "--docs", os.environ.get("ABL_DOCS", "1000000"),
                               "--config", os.environ.get("ABL_CONFIG", "C4"), "--no-traffic", "--no-e2e", "--no-orders",
                               "--no-node", "--no-incremental", "--detail", det] + os.environ.get("ABL_ARGS", "").split(),

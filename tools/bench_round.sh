@@ -3,7 +3,7 @@
 set -o pipefail
 O=gpurun_out/${1:-bench}
 mkdir -p $O
-timeout -k 10 900 python -u bench.py > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
 grep '^{' $O/bench.log | tail -1 > $O/bench_line.json
 python3 -c "
 import json

@@ -5,7 +5,7 @@ set -o pipefail
 O=gpurun_out/${1:-final}
 mkdir -p $O
 if [ "$2" != "nobench" ]; then
-timeout -k 10 900 python -u bench.py > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
 grep '^{' $O/bench.log | tail -1 > $O/bench_line.json
 cp gpurun_out/bench_detail.json $O/bench_detail.json
 fi

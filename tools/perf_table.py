@@ -22,7 +22,7 @@ def main() -> int:
         if only and cfg not in only:
             continue
         extra = ["--arrival", "1"] if cfg.endswith("am") else []
-        cmd = [sys.executable, os.path.join(R, "bench.py"), "--config", cfg[:2], "--docs", str(docs), "--steps", str(steps),
+        cmd = [sys.executable, os.path.join(R, "bench.py"), "--full", "--config", cfg[:2], "--docs", str(docs), "--steps", str(steps),
                "--warmup", "2", "--cpu-sample-docs", str(cpu_docs), "--check-docs", str(check), "--no-traffic"] + extra
         if cfg != "C2":
             cmd.append("--no-node")                     # the Node leg runs its own C2 sample

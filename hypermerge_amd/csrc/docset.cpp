@@ -1878,6 +1878,81 @@ int hm_docset_clock_update(hm_docset *ds, uint32_t n, const uint32_t *docs, uint
     }
 }
 
+int hm_docset_blocked(hm_docset *ds, uint32_t *out_docs, uint32_t cap, uint32_t *out_n) {
+    if (!ds || !out_n || (cap && !out_docs)) return HM_ERR_INVALID;
+    Busy b(ds);
+    if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
+    try {
+        *out_n = 0;
+        const uint32_t nd = ds->n_docs.load();
+        std::vector<uint32_t> found;
+        for (uint32_t c = 0; c < N_CLASS; c++) {
+            if (!ds->stores[c] || !ds->opened[c]) continue;
+            std::vector<uint32_t> hs(ds->opened[c]);
+            uint32_t k = 0;
+            const int rc = hm_store_blocked(ds->stores[c], hs.data(), (uint32_t)hs.size(), &k);
+            if (rc) return rc;
+            if (!k) continue;
+            // (handle -> document of this class; a released handle is an empty document, never blocked)
+            std::vector<uint32_t> doc_of(ds->opened[c], HM_NONE);
+            for (uint32_t i = 0; i < nd; i++) {
+                const DocSt &d = ds->doc(i);
+                if (d.cls == c && d.handle < doc_of.size()) doc_of[d.handle] = i;
+            }
+            for (uint32_t j = 0; j < k; j++)
+                if (hs[j] < doc_of.size() && doc_of[hs[j]] != HM_NONE) found.push_back(doc_of[hs[j]]);
+        }
+        std::sort(found.begin(), found.end());
+        *out_n = (uint32_t)found.size();
+        if (found.size() > cap) return hm_engine_fail(ds->e, HM_ERR_NOMEM, "cap below the number of blocked documents");
+        if (!found.empty()) memcpy(out_docs, found.data(), found.size() * 4);
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_blocked");
+    }
+}
+
+int hm_docset_waiting(hm_docset *ds, uint32_t n, const uint32_t *docs, hm_text **out) {
+    if (!ds || !out || (n && !docs)) return HM_ERR_INVALID;
+    *out = nullptr;
+    Busy b(ds);
+    if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
+    try {
+        const uint32_t nd = ds->n_docs.load();
+        for (uint32_t i = 0; i < n; i++) if (docs[i] >= nd) return hm_engine_fail(ds->e, HM_ERR_INVALID, "bad docset document");
+        std::vector<std::string> js(n, "{\"queued\":[],\"missing\":{}}");      // (a document not placed yet)
+        for (uint32_t c = 0; c < N_CLASS; c++) {
+            std::vector<uint32_t> idx, hs;
+            for (uint32_t i = 0; i < n; i++) if (ds->doc(docs[i]).cls == c) { idx.push_back(i); hs.push_back(ds->doc(docs[i]).handle); }
+            if (idx.empty()) continue;
+            const uint32_t S = STRIDES[c], k = (uint32_t)idx.size();
+            std::vector<uint32_t> miss((size_t)k * S), nq(k), off(k + 1, 0);
+            int rc = hm_store_waiting(ds->stores[c], k, hs.data(), miss.data(), nullptr, nq.data());
+            if (rc) return rc;
+            for (uint32_t j = 0; j < k; j++) off[j + 1] = off[j] + nq[j];
+            std::vector<uint32_t> q(off[k] + 1);
+            if ((rc = hm_store_read_queue(ds->stores[c], k, hs.data(), off.data(), q.data()))) return rc;
+            for (uint32_t j = 0; j < k; j++) {
+                const DocSt &d = ds->doc(docs[idx[j]]);
+                std::string &o = js[idx[j]];
+                o = "{\"queued\":[";
+                for (uint32_t r = off[j]; r < off[j + 1]; r++) { if (r > off[j]) o += ','; o += std::to_string(q[r]); }
+                o += "],\"missing\":";
+                jclock(o, d, miss.data() + (size_t)j * S, d.actors.size());
+                o += '}';
+            }
+        }
+        std::unique_ptr<hm_text> t(new hm_text());
+        t->s = "[";
+        for (uint32_t i = 0; i < n; i++) { if (i) t->s += ','; t->s += js[i]; }
+        t->s += ']';
+        *out = t.release();
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_waiting");
+    }
+}
+
 int hm_docset_view(hm_docset *ds, uint32_t doc, hm_text **out) {
     if (!ds || !out || doc >= ds->n_docs.load()) return HM_ERR_INVALID;
     *out = nullptr;

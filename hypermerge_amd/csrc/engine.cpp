@@ -15,6 +15,7 @@
 #include "../../include/hypermerge_amd.h"
 #include "merge_kernels.h"
 #include "engine_internal.h"
+#include "waiting_kernels.h"
 
 struct hm_engine {
     int device = 0;
@@ -375,6 +376,67 @@ int hm_merge_host(hm_engine *e, const hm_batch *hb, const hm_results *ho) {
         return rc;
     } catch (...) {
         return fail(e, HM_ERR_DEVICE, "exception in hm_merge_host");
+    }
+}
+
+// (the missing-deps calls read the docs, changes and deps tables only: no op table is asked for)
+static int check_waiting_batch(hm_engine *e, const hm_batch *b) {
+    if (!b || b->a_stride == 0 || b->a_stride > HM_MAX_STRIDE) return fail(e, HM_ERR_INVALID, "a_stride must be in [1,256]");
+    if ((b->n_docs && !b->docs) || (b->n_changes && !b->changes) || (b->n_deps && !b->deps))
+        return fail(e, HM_ERR_INVALID, "row table missing");
+    return HM_OK;
+}
+
+int hm_missing_deps_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t *out_missing, void *stream) {
+    try {
+        if (!e || !r) return HM_ERR_INVALID;
+        int st = check_waiting_batch(e, b);
+        if (st) return st;
+        if (!b->n_docs) return HM_OK;
+        if (!out_missing || !r->docs || !r->clock || (b->n_changes && !r->hist))
+            return fail(e, HM_ERR_INVALID, "hm_missing_deps needs the results' docs, clock and hist tables");
+        HIPCHK(e, hipSetDevice(e->device));
+        hipError_t hr = hm_launch_waiting_batch(b, r, out_missing, stream ? (hipStream_t)stream : e->stream);
+        return hr == hipSuccess ? HM_OK : hip_fail(e, hr, "waiting_batch_kernel launch");
+    } catch (...) {
+        return fail(e, HM_ERR_DEVICE, "exception in hm_missing_deps_device");
+    }
+}
+
+int hm_missing_deps_host(hm_engine *e, const hm_batch *hb, const hm_results *hr, uint32_t *out_missing) {
+    try {
+        if (!e || !hr) return HM_ERR_INVALID;
+        int st = check_waiting_batch(e, hb);
+        if (st) return st;
+        if (!hb->n_docs) return HM_OK;
+        if (!out_missing || !hr->docs || !hr->clock || (hb->n_changes && !hr->hist))
+            return fail(e, HM_ERR_INVALID, "hm_missing_deps needs the results' docs, clock and hist tables");
+        HIPCHK(e, hipSetDevice(e->device));
+        const size_t S = hb->a_stride, n = hb->n_docs;
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t sz[7] = {n * sizeof(hm_doc_row), hb->n_changes * sizeof(hm_change_row), hb->n_deps * sizeof(hm_dep_row),
+                              n * sizeof(hm_doc_result), n * S * 4, (size_t)hb->n_changes * 4, n * S * 4};
+        const void *src[6] = {hb->docs, hb->changes, hb->deps, hr->docs, hr->clock, hr->hist};
+        size_t off[7], total = 0;
+        for (int i = 0; i < 7; i++) { off[i] = total; total += al(sz[i] ? sz[i] : 1); }
+        char *base = nullptr;
+        if (hipMalloc((void **)&base, total) != hipSuccess) return fail(e, HM_ERR_NOMEM, "hipMalloc missing-deps staging");
+        hipStream_t s = e->stream;
+        hm_batch b = *hb;
+        b.docs = (const hm_doc_row *)(base + off[0]); b.changes = (const hm_change_row *)(base + off[1]);
+        b.deps = (const hm_dep_row *)(base + off[2]);
+        hm_results d = {};
+        d.docs = (hm_doc_result *)(base + off[3]); d.clock = (uint32_t *)(base + off[4]); d.hist = (int32_t *)(base + off[5]);
+        hipError_t r = hipSuccess;
+        for (int i = 0; i < 6 && r == hipSuccess; i++)
+            if (sz[i]) r = hipMemcpyAsync(base + off[i], src[i], sz[i], hipMemcpyHostToDevice, s);
+        if (r == hipSuccess) r = hm_launch_waiting_batch(&b, &d, (uint32_t *)(base + off[6]), s);
+        if (r == hipSuccess) r = hipMemcpyAsync(out_missing, base + off[6], sz[6], hipMemcpyDeviceToHost, s);
+        if (r == hipSuccess) r = hipStreamSynchronize(s);
+        (void)hipFree(base);
+        return r == hipSuccess ? HM_OK : hip_fail(e, r, "hm_missing_deps_host");
+    } catch (...) {
+        return fail(e, HM_ERR_DEVICE, "exception in hm_missing_deps_host");
     }
 }
 

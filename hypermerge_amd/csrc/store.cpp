@@ -39,6 +39,7 @@
 #include "../../include/hypermerge_amd.h"
 #include "engine_internal.h"
 #include "store_kernels.h"
+#include "waiting_kernels.h"
 
 namespace {
 
@@ -984,6 +985,107 @@ int hm_store_read_history(hm_store *s, uint32_t n, const uint32_t *doc_handles, 
         return HM_OK;
     } catch (...) {
         return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_read_history");
+    }
+}
+
+int hm_store_blocked(hm_store *s, uint32_t *out_handles, uint32_t cap, uint32_t *out_n) {
+    if (!s || !out_n || (cap && !out_handles)) return HM_ERR_INVALID;
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        *out_n = 0;
+        if (!s->n_handles) return HM_OK;
+        hipStream_t st = hm_engine_stream(s->e);
+        const uint32_t rows = std::min(cap, s->n_handles);
+        int rc = ensure_stage(s, 256 + 4 * (size_t)rows + 4);
+        if (rc) return rc;
+        uint8_t *sp = s->stage.p;
+        SCHK(s, hipMemsetAsync(sp, 0, 4, st));
+        SCHK(s, hm_launch_blocked(s->res_docs, s->n_handles, (uint32_t *)(sp + 256), rows, (uint32_t *)sp, st));
+        SCHK(s, hipMemcpyAsync(&s->h_cnt[6], sp, 4, hipMemcpyDeviceToHost, st));
+        SCHK(s, hipStreamSynchronize(st));
+        const uint32_t k = s->h_cnt[6];
+        *out_n = k;
+        if (k > cap) return hm_engine_fail(s->e, HM_ERR_NOMEM, "cap below the number of blocked documents");
+        if (k) {
+            SCHK(s, hipMemcpy(out_handles, sp + 256, 4 * (size_t)k, hipMemcpyDeviceToHost));
+            std::sort(out_handles, out_handles + k);       // (the waves' blocks land in any order)
+        }
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_blocked");
+    }
+}
+
+// hm_store_waiting / hm_store_read_queue: one launch of the waiting pass over the staged requests
+static int waiting_impl(hm_store *s, uint32_t n, const uint32_t *doc_handles, uint32_t *out_missing, uint32_t *out_unmet,
+                        uint32_t *out_nq, const uint32_t *q_off, uint32_t *out_queue) {
+    const uint32_t S = s->S;
+    const uint32_t q_rows = q_off ? q_off[n] : 0;
+    hipStream_t st = hm_engine_stream(s->e);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t row_b = al(4 * (size_t)n * S);
+    const size_t o_h = 0, o_bad = al(4 * (size_t)n), o_off = o_bad + 256, o_nq = o_off + al(4 * ((size_t)n + 1)),
+                 o_miss = o_nq + al(4 * (size_t)n), o_unmet = o_miss + (out_missing ? row_b : 0),
+                 o_q = o_unmet + (out_unmet ? row_b : 0), total = o_q + al(4 * (size_t)q_rows + 4);
+    int rc = ensure_stage(s, total);
+    if (rc) return rc;
+    uint8_t *sp = s->stage.p;
+    SCHK(s, hipMemcpyAsync(sp + o_h, doc_handles, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    if (q_off) SCHK(s, hipMemcpyAsync(sp + o_off, q_off, 4 * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+    SCHK(s, hipMemsetAsync(sp + o_bad, 0, 4, st));
+    WaitingArgs A;
+    A.n = n; A.handles = (const uint32_t *)(sp + o_h); A.dm = s->dm; A.n_handles = s->n_handles; A.S = S;
+    A.changes = s->changes; A.deps = s->deps; A.lim_c = s->cap_c; A.lim_d = s->cap_d; A.hist = s->hist;
+    A.clock = s->clock; A.back_clock = s->back_clock; A.min_clock = s->min_clock;
+    A.out_missing = out_missing ? (uint32_t *)(sp + o_miss) : nullptr;
+    A.out_unmet = out_unmet ? (uint32_t *)(sp + o_unmet) : nullptr;
+    A.out_nq = out_nq ? (uint32_t *)(sp + o_nq) : nullptr;
+    A.q_off = q_off ? (const uint32_t *)(sp + o_off) : nullptr;
+    A.out_queue = q_off ? (uint32_t *)(sp + o_q) : nullptr;
+    A.bad = (uint32_t *)(sp + o_bad);
+    SCHK(s, hm_launch_waiting(A, st));
+    SCHK(s, hipMemcpyAsync(&s->h_cnt[7], sp + o_bad, 4, hipMemcpyDeviceToHost, st));
+    SCHK(s, hipStreamSynchronize(st));
+    const uint32_t bad = s->h_cnt[7];
+    if (bad & 1) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad handle");
+    if (bad & 2) return hm_engine_fail(s->e, HM_ERR_INVALID, "out_off does not match the documents' queue lengths");
+    if (out_missing) SCHK(s, hipMemcpyAsync(out_missing, sp + o_miss, 4 * (size_t)n * S, hipMemcpyDeviceToHost, st));
+    if (out_unmet) SCHK(s, hipMemcpyAsync(out_unmet, sp + o_unmet, 4 * (size_t)n * S, hipMemcpyDeviceToHost, st));
+    if (out_nq) SCHK(s, hipMemcpyAsync(out_nq, sp + o_nq, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (q_rows) SCHK(s, hipMemcpyAsync(out_queue, sp + o_q, 4 * (size_t)q_rows, hipMemcpyDeviceToHost, st));
+    SCHK(s, hipStreamSynchronize(st));
+    return HM_OK;
+}
+
+int hm_store_waiting(hm_store *s, uint32_t n, const uint32_t *doc_handles, uint32_t *out_missing, uint32_t *out_unmet_min,
+                     uint32_t *out_n_queued) {
+    if (!s || (n && !doc_handles)) return HM_ERR_INVALID;
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        if (!n) return HM_OK;
+        return waiting_impl(s, n, doc_handles, out_missing, out_unmet_min, out_n_queued, nullptr, nullptr);
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_waiting");
+    }
+}
+
+int hm_store_read_queue(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *out_off, uint32_t *out_log_index) {
+    if (!s || (n && (!doc_handles || !out_off))) return HM_ERR_INVALID;
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        if (!n) return HM_OK;
+        for (uint32_t i = 0; i < n; i++)
+            if (out_off[i + 1] < out_off[i]) return hm_engine_fail(s->e, HM_ERR_INVALID, "out_off must not decrease");
+        if (out_off[n] - out_off[0] && !out_log_index) return HM_ERR_INVALID;
+        if (out_off[0]) {
+            // (rows before out_off[0] are the caller's: stage the offsets from zero)
+            std::vector<uint32_t> off(out_off, out_off + n + 1);
+            for (auto &x : off) x -= out_off[0];
+            return waiting_impl(s, n, doc_handles, nullptr, nullptr, nullptr, off.data(), out_log_index + out_off[0]);
+        }
+        return waiting_impl(s, n, doc_handles, nullptr, nullptr, nullptr, out_off, out_log_index);
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_read_queue");
     }
 }
 

@@ -109,6 +109,27 @@ class DocSet:
         s, _ = _text(self._L, t)
         return json.loads(s)
 
+    def blocked(self) -> List[int]:
+        """Documents that hold queued changes (every stride class), ids ascending."""
+        n = ctypes.c_uint32()
+        out = np.zeros(1024, np.uint32)
+        st = self._L.hm_docset_blocked(self._h, out.ctypes.data, len(out), ctypes.byref(n))
+        if st == 34:                                  # HM_ERR_NOMEM: n = the count needed
+            out = np.zeros(n.value, np.uint32)
+            st = self._L.hm_docset_blocked(self._h, out.ctypes.data, len(out), ctypes.byref(n))
+        self.engine._check(st, "hm_docset_blocked")
+        return [int(x) for x in out[:n.value]]
+
+    def waiting(self, docs: Sequence[int]) -> List[Dict[str, Any]]:
+        """Per document {"queued": [log indices in queue order], "missing": {actorId: seq}}
+        (Backend.getMissingDeps of the rounds applied so far)."""
+        ids = np.ascontiguousarray(docs, np.uint32)
+        t = ctypes.c_void_p()
+        self.engine._check(self._L.hm_docset_waiting(self._h, len(ids), ids.ctypes.data, ctypes.byref(t)),
+                           "hm_docset_waiting")
+        s, _ = _text(self._L, t)
+        return json.loads(s)
+
     def handles(self, a_stride: int) -> Dict[str, int]:
         """hm_docset_handles: handles opened in the a_stride store and released ones awaiting reuse."""
         o, f = ctypes.c_uint32(), ctypes.c_uint32()

@@ -36,7 +36,8 @@ EXPORTS = ("hm_abi_version", "hm_status_message", "hm_engine_create", "hm_engine
            "hm_docset_engine", "hm_docset_open", "hm_docset_apply", "hm_text_data", "hm_text_results", "hm_text_free",
            "hm_docset_doc_info", "hm_docset_history_prefix", "hm_docset_clock_update", "hm_docset_view",
            "hm_docset_stats", "hm_docset_routing", "hm_docset_handles", "hm_sync_ranges_host", "hm_batch_submit_device", "hm_batch_wait_device",
-           "hm_batch_undo")
+           "hm_batch_undo", "hm_store_blocked", "hm_store_waiting", "hm_store_read_queue", "hm_missing_deps_device",
+           "hm_missing_deps_host", "hm_docset_blocked", "hm_docset_waiting")
 
 _lib = None
 
@@ -110,6 +111,11 @@ def lib():
             "hm_docset_doc_info": [vp, u32, vp], "hm_docset_history_prefix": [vp, u32, u32, vp],
             "hm_docset_clock_update": [vp, u32, vp, vp, vp, vp], "hm_docset_view": [vp, u32, vp],
             "hm_docset_stats": [vp, vp], "hm_docset_routing": [vp, vp], "hm_docset_handles": [vp, u32, vp, vp], "hm_sync_ranges_host": [vp, vp, vp, vp, vp, vp, u32, u32],
+            "hm_store_blocked": [vp, vp, u32, vp], "hm_store_waiting": [vp, u32, vp, vp, vp, vp],
+            "hm_store_read_queue": [vp, u32, vp, vp, vp],
+            "hm_missing_deps_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), vp, vp],
+            "hm_missing_deps_host": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), vp],
+            "hm_docset_blocked": [vp, vp, u32, vp], "hm_docset_waiting": [vp, u32, vp, vp],
         }
         for f, a in sig.items():
             getattr(L, f).argtypes = a
@@ -184,6 +190,23 @@ class Engine:
         """Device-resident merge: every pointer in the structs is a device pointer."""
         self._check(self._L.hm_merge_device(self._h, ctypes.byref(cbatch), ctypes.byref(cresults), None,
                                             ctypes.c_void_p(stream) if stream else None), "hm_merge_device")
+
+    def missing_deps(self, batch: Batch, results: Results) -> np.ndarray:
+        """getMissingDeps of every document of a merged batch: [n_docs, a_stride], per actor rank the
+        largest seq a queued change needs that opSet.clock has not reached (0 = no entry); a
+        document whose merge threw gets a zero row."""
+        out = np.zeros((batch.n_docs, batch.a_stride), np.uint32)
+        cb, cr = batch.c_struct(), results.c_struct()
+        self._check(self._L.hm_missing_deps_host(self._h, ctypes.byref(cb), ctypes.byref(cr), out.ctypes.data),
+                    "hm_missing_deps_host")
+        return out
+
+    def missing_deps_device(self, cbatch: CBatch, cresults: CResults, out_ptr: int, stream: int = 0) -> None:
+        """The same with every table and the [n_docs * a_stride] u32 output in device memory
+        (enqueued on the stream, not synchronised)."""
+        self._check(self._L.hm_missing_deps_device(self._h, ctypes.byref(cbatch), ctypes.byref(cresults),
+                                                   ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream) if stream else None),
+                    "hm_missing_deps_device")
 
     def last_kernel_ms(self) -> Sequence[float]:
         buf = (ctypes.c_float * 4)()

@@ -302,6 +302,23 @@ class History {
   }
 }
 
+// what one document waits for, read from the device: {queued: [log indices in queue order],
+// missing: {actorId: seq}} (Automerge getMissingDeps).  Like every read here it reflects the rounds
+// already applied: in 'async' mode await engine.idle() first (the docset refuses reads while a
+// round is in flight).
+function waitingOf(state) {
+  return JSON.parse(addon.docsetWaiting(state.ds, Uint32Array.of(state.id)))[0]
+}
+
+// opSet.queue: the changes Automerge left queued (a dependency has not arrived), in queue order
+class Queue {
+  constructor(state) {
+    this.items = waitingOf(state).queued.map((i) => state.change(i))
+    this.size = this.items.length
+  }
+  toArray() { return this.items }
+}
+
 // FNV-1a 64 over the UTF-8 bytes of an id string: the shard key (and the clock exchange's
 // record key) of hypermerge_amd/exchange.py and include/hypermerge_amd.h.
 // Computed on two 32-bit halves in plain Numbers (h * prime = h * 0x1b3 + h << 40; every partial
@@ -357,6 +374,7 @@ class GpuBackendState {
     this.shard = docId === undefined ? 0 : engine.shardOf(docId)
     this.ds = engine.docsets[this.shard]
     this.id = addon.docsetOpen(this.ds, 1)
+    engine.states[this.shard].set(this.id, this)    // (docset id -> state: GpuEngine.blocked names documents)
     this.log = []
     this.histLen = 0
     this.nQueued = 0
@@ -388,6 +406,7 @@ class GpuBackendState {
     if (p.length === 2 && p[0] === 'opSet' && p[1] === 'history') return new History(this)
     if (p.length === 2 && p[0] === 'opSet' && p[1] === 'clock') return Object.assign({}, this.clock)
     if (p.length === 2 && p[0] === 'opSet' && p[1] === 'deps') return Object.assign({}, this.deps)
+    if (p.length === 2 && p[0] === 'opSet' && p[1] === 'queue') return new Queue(this)
     throw new Error(`GpuBackendState.getIn: unsupported path ${JSON.stringify(p)}`)
   }
 }
@@ -406,6 +425,7 @@ class GpuEngine {
     this.diffs = o.diffs || 'ops'
     this.docsets = this.devices.map((d) => addon.docsetCreate(d, o.threads || 0, this.patches, o.binary !== false,
       this.diffs === 'net'))
+    this.states = this.docsets.map(() => new Map())     // per docset: document id -> state
     this.queues = new Map()          // state -> FIFO of jobs
     this.flushing = false
     this.scheduled = false
@@ -429,6 +449,25 @@ class GpuEngine {
   }
 
   get restrides() { return this.stats().moves }
+
+  // the documents that hold queued changes, across the docsets, and what each waits for:
+  // [{id (the docId given to init), state, missing: {actorId: seq}}].  Reflects the rounds already
+  // applied: in 'async' mode await idle() first.
+  blocked() {
+    const out = []
+    this.docsets.forEach((ds, k) => {
+      const buf = addon.docsetBlocked(ds)
+      if (!buf.length) return
+      const ids = new Uint32Array(buf.length / 4)
+      for (let i = 0; i < ids.length; i++) ids[i] = buf.readUInt32LE(4 * i)
+      const w = JSON.parse(addon.docsetWaiting(ds, ids))
+      ids.forEach((id, i) => {
+        const state = this.states[k].get(id)
+        out.push({ id: state ? state.docId : undefined, state, missing: w[i].missing })
+      })
+    })
+    return out
+  }
 
   // job: {entries|null, done(payload|null), fail(err)}
   enqueue(state, job) {
@@ -810,6 +849,9 @@ function makeBackend(engine) {
       return [state, r ? r.patch : emptyPatch(state)]
     },
     getPatch: (state) => fullPatch(state),
+    // Backend.getMissingDeps: {actorId: seq} the queued changes need and opSet.clock lacks (of the
+    // rounds already applied: in 'async' mode await engine.idle() first)
+    getMissingDeps: (state) => waitingOf(state).missing,
   }
 }
 
@@ -857,6 +899,10 @@ class DocBackend {
     this.minimumClock = Clock.union(clock, this.minimumClock || {})
     this.testMinimumClockSatisfied()
   }
+
+  // what this document's queued changes wait for, {actorId: seq} ({} before init; of the rounds
+  // already applied: in 'async' mode await engine.idle() first)
+  missingDeps() { return this.back ? waitingOf(this.back).missing : {} }
 
   // changes: Change objects (the reference's), or raw hypercore blocks / JSON texts of them
   applyRemoteChanges(changes) { this.remoteChangesQ.push(changes) }

@@ -930,6 +930,48 @@ static napi_value DocsetView(napi_env env, napi_callback_info info) {
     return js;
 }
 
+/* docsetBlocked(docset) -> Buffer of u32 document ids that hold queued changes, ascending (refused
+ * while a call on the docset is in flight, like docsetView) */
+static napi_value DocsetBlocked(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return NULL;
+    Docset *d = get_docset(env, argv[0]);
+    if (!d) return NULL;
+    uint32_t cap = 1024, n = 0;
+    uint32_t *out = (uint32_t *)malloc((size_t)cap * 4);
+    int st = out ? hm_docset_blocked(d->ds, out, cap, &n) : HM_ERR_NOMEM;
+    if (st == HM_ERR_NOMEM && out && n > cap) {          /* n = the count needed */
+        free(out);
+        cap = n;
+        out = (uint32_t *)malloc((size_t)cap * 4);
+        st = out ? hm_docset_blocked(d->ds, out, cap, &n) : HM_ERR_NOMEM;
+    }
+    if (st) { free(out); return throw_status(env, d->engine, st, "hm_docset_blocked"); }
+    napi_value r = buf_copy(env, out, (size_t)n * 4);
+    free(out);
+    return r;
+}
+
+/* docsetWaiting(docset, ids Uint32Array) -> JSON text, per document {"queued": [log indices],
+ * "missing": {actorId: seq}} (refused while a call on the docset is in flight) */
+static napi_value DocsetWaiting(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return NULL;
+    Docset *d = get_docset(env, argv[0]);
+    if (!d) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    hm_text *t = NULL;
+    int st = hm_docset_waiting(d->ds, (uint32_t)(n / 4), (const uint32_t *)p, &t);
+    if (st) return throw_status(env, d->engine, st, "hm_docset_waiting");
+    size_t len = 0;
+    const char *s = hm_text_data(t, &len);
+    napi_value js;
+    napi_create_string_utf8(env, s, len, &js);
+    hm_text_free(t);
+    return js;
+}
+
 /* docsetInfo(docset, doc) -> {aStride, nChanges, nOps, nActors, nObjs, nRegs, histLen, nQueued} */
 static napi_value DocsetInfo(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -1190,7 +1232,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"waitAsync", WaitAsync}, {"readRegs", ReadRegs},
         {"docsetCreate", DocsetCreate}, {"docsetOpen", DocsetOpen}, {"docsetApply", DocsetApply}, {"docsetApplyPacked", DocsetApplyPacked},
         {"docsetHistoryPrefix", DocsetHistoryPrefix}, {"docsetClockUpdate", DocsetClockUpdate},
-        {"docsetView", DocsetView}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
+        {"docsetView", DocsetView}, {"docsetBlocked", DocsetBlocked}, {"docsetWaiting", DocsetWaiting},{"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
         {"cursorsCreate", CursorsCreate}, {"cursorsReserve", CursorsReserve}, {"cursorsUpdate", CursorsUpdate},
         {"cursorsGet", CursorsGet}, {"cursorsEntry", CursorsEntry}, {"cursorsDocsWithActors", CursorsDocsWithActors},
         {"syncRanges", SyncRanges}, {"decodeBlocks", DecodeBlocks}, {"commCreateLocalDocsets", CommCreateLocalDocsets},

@@ -380,6 +380,51 @@ class DocStore:
             self._check(k, "hm_doc_history_prefix")
         return [int(x) for x in out[:k]]
 
+    # -- what blocked documents wait for (getMissingDeps); all read the rounds already waited for ----
+    def blocked(self) -> np.ndarray:
+        """Handles of the documents that hold queued changes, ascending (hm_store_blocked)."""
+        n = ctypes.c_uint32()
+        out = np.zeros(1024, np.uint32)
+        st = self._L.hm_store_blocked(self._h, _p(out), len(out), ctypes.byref(n))
+        if st == 34:                                  # HM_ERR_NOMEM: n = the count needed
+            out = np.zeros(n.value, np.uint32)
+            st = self._L.hm_store_blocked(self._h, _p(out), len(out), ctypes.byref(n))
+        self._check(st, "hm_store_blocked")
+        return out[:n.value].copy()
+
+    def waiting(self, handles) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(missing [n, S], unmet_min [n, S], n_queued [n]) of the listed documents: per actor rank
+        the largest seq a queued change needs and opSet.clock lacks, the minimumClock entries
+        DocBackend.clock has not reached, and the queue length (hm_store_waiting)."""
+        hs = np.ascontiguousarray(handles, np.uint32)
+        n = len(hs)
+        miss = np.zeros((n, self.S), np.uint32)
+        unmet = np.zeros((n, self.S), np.uint32)
+        nq = np.zeros(n, np.uint32)
+        self._check(self._L.hm_store_waiting(self._h, n, _p(hs), _p(miss), _p(unmet), _p(nq)), "hm_store_waiting")
+        return miss, unmet, nq
+
+    def queues(self, handles, n_queued) -> Tuple[np.ndarray, np.ndarray]:
+        """opSet.queue of the listed documents as log indices in queue order: (offsets [n + 1],
+        indices); n_queued from waiting() (hm_store_read_queue)."""
+        hs = np.ascontiguousarray(handles, np.uint32)
+        off = np.zeros(len(hs) + 1, np.uint32)
+        np.cumsum(np.asarray(n_queued, np.uint32), out=off[1:])
+        out = np.zeros(max(int(off[-1]), 1), np.uint32)
+        self._check(self._L.hm_store_read_queue(self._h, len(hs), _p(hs), _p(off), _p(out)), "hm_store_read_queue")
+        return off, out[:int(off[-1])]
+
+    def queue(self, h: int) -> List[int]:
+        """opSet.queue of one document (log indices, queue order)."""
+        _, _, nq = self.waiting([h])
+        return [int(x) for x in self.queues([h], nq)[1]]
+
+    def missing_deps(self, h: int) -> Dict[str, int]:
+        """Backend.getMissingDeps of one document: {actorId: seq}."""
+        miss, _, _ = self.waiting([h])
+        actors = self.enc[h].actors
+        return {actors[a]: int(s) for a, s in enumerate(miss[0]) if s}
+
     def set_min_clock(self, h: int, clock: Dict[str, int]) -> None:
         """minimumClock (actor id -> seq); its actors must already be in the document's actor table."""
         e = self.enc[h]

@@ -408,6 +408,32 @@ int hm_doc_history_prefix(hm_store *s, uint32_t doc, uint32_t n, uint32_t *out_l
 int hm_store_read_history(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
                           const uint32_t *out_off, uint32_t *out_log_index, uint32_t *out_all_deps);
 
+/* What blocked documents wait for (Automerge 0.12 getMissingDeps; no reference call site: the
+ * reference leaves opSet.queue alone until the dependency arrives).  A queued change (hist -1)
+ * needs every (actor, seq) of deps.set(actor, seq - 1) (causallyReady's rule: the change's own actor
+ * at seq - 1, whatever its deps say of that actor); the missing row holds, per actor rank, the
+ * largest needed seq that opSet.clock has not reached (0 = no entry).  n_queued > 0 exactly when
+ * the row is not zero.  All of these read the rounds already waited for (no batch in flight).
+ *
+ * hm_store_blocked: handles of the store's documents that hold queued changes, ascending;
+ * HM_ERR_NOMEM (with *out_n = the count needed) when cap is too small. */
+int hm_store_blocked(hm_store *s, uint32_t *out_handles, uint32_t cap, uint32_t *out_n);
+/* Per requested document (a handle may repeat): the missing row, the unmet minimumClock row
+ * (min_clock[a] where DocBackend.clock[a] < min_clock[a], else 0; all zero without
+ * hm_doc_set_min_clock) and the queue length (each output may be NULL). */
+int hm_store_waiting(hm_store *s, uint32_t n, const uint32_t *doc_handles,
+                     uint32_t *out_missing /* [n*S] */, uint32_t *out_unmet_min /* [n*S] */, uint32_t *out_n_queued /* [n] */);
+/* opSet.queue of each requested document as log indices in queue order: request i writes rows
+ * out_off[i] .. out_off[i+1]-1, out_off[i+1] - out_off[i] = its queue length (from
+ * hm_store_waiting's out_n_queued); a mismatch is HM_ERR_INVALID. */
+int hm_store_read_queue(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *out_off, uint32_t *out_log_index);
+/* The missing rows of a merged cold batch, [n_docs * a_stride]; a document whose status is not HM_OK
+ * gets a zero row.  _device: b's docs / changes / deps, r's docs / clock / hist and out_missing are
+ * device memory, enqueued on `stream` (NULL = the engine's) without synchronising; _host: host
+ * tables in, host rows out (staged, synchronous). */
+int hm_missing_deps_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t *out_missing, void *stream);
+int hm_missing_deps_host(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t *out_missing);
+
 /* minimumClock row of a document (rank-indexed, 0 = absent); used for the
  * min_cmp of the next merges (Clock.cmp(DocBackend.clock, minimumClock)). */
 int hm_doc_set_min_clock(hm_store *s, uint32_t doc, const uint32_t *clock);
@@ -575,6 +601,13 @@ int hm_docset_history_prefix(hm_docset *ds, uint32_t doc, uint32_t n, uint32_t *
  * *out_stored (optional) = JSON array of the stored clocks, in call order */
 int hm_docset_clock_update(hm_docset *ds, uint32_t n, const uint32_t *docs, uint8_t *out_written, uint8_t *out_differs,
                            hm_text **out_stored);
+/* documents that hold queued changes (hm_store_blocked over every stride class), ids ascending;
+ * HM_ERR_NOMEM (with *out_n = the count needed) when cap is too small */
+int hm_docset_blocked(hm_docset *ds, uint32_t *out_docs, uint32_t cap, uint32_t *out_n);
+/* what n documents wait for: JSON array, per document {"queued":[log indices in queue order],
+ * "missing":{"<actorId>":seq}} (Automerge getMissingDeps; hm_store_waiting + hm_store_read_queue
+ * per class, ranks mapped back to actor ids) */
+int hm_docset_waiting(hm_docset *ds, uint32_t n, const uint32_t *docs, hm_text **out);
 /* the merged document: {uuid: {"type", "keys": [[key, entry]], "elems": [[elemId, entry]]}} */
 int hm_docset_view(hm_docset *ds, uint32_t doc, hm_text **out);
 /* counters: calls, documents, class moves, net patches from the hit registers, net patches from every

@@ -252,6 +252,26 @@ int hm_merge_device(hm_engine *e, const hm_batch *b, const hm_results *o, void *
     }
 }
 
+int hm_debug_small_occupancy(hm_engine *e, const hm_batch *hb, uint32_t *out6) {
+    if (!e || !hb || !out6) return HM_ERR_INVALID;
+    if (hipSetDevice(e->device) != hipSuccess) return fail(e, HM_ERR_DEVICE, "hipSetDevice");
+    hm_batch b = *hb;
+    if (!b.max_changes && !b.max_ops && !b.max_regs && !b.max_objs && hb->docs) {
+        for (uint32_t d = 0; d < b.n_docs; d++) {          // (the hints hm_merge_host computes)
+            b.max_ops = std::max(b.max_ops, hb->docs[d].n_ops);
+            b.max_regs = std::max(b.max_regs, hb->docs[d].n_regs);
+            b.max_objs = std::max(b.max_objs, hb->docs[d].n_objs);
+            b.max_deps = std::max(b.max_deps, hb->docs[d].n_deps);
+            b.doc_flags |= hb->docs[d].flags;
+        }
+    }
+    const Caps c = launch_caps(&b);
+    out6[0] = hm_small_occupancy(c.opl, c.cls, c.lists, c.counters);
+    out6[1] = (uint32_t)e->num_cus;
+    out6[2] = c.opl; out6[3] = c.cls; out6[4] = c.lists ? 1u : 0u; out6[5] = c.counters ? 1u : 0u;
+    return HM_OK;
+}
+
 int hm_merge_host(hm_engine *e, const hm_batch *hb, const hm_results *ho) {
     try {
         if (!e || !hb || !ho) return HM_ERR_INVALID;

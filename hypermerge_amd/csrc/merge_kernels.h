@@ -36,10 +36,11 @@ struct SmallParams {
 };
 #ifdef __HIPCC__
 __device__ __forceinline__ bool hm_doc_row_ok(const SmallParams &p, const hm_doc_row &d) {
-    return (unsigned long long)d.change_off + d.n_changes <= p.lim_changes &&
-           (unsigned long long)d.dep_off + d.n_deps <= p.lim_deps &&
-           (unsigned long long)d.op_off + d.n_ops <= p.lim_ops &&
-           (unsigned long long)d.reg_off + d.n_regs <= p.lim_regs && d.n_actors <= p.a_stride;
+    // (no short-circuit: the four limits are one scalar load, not four dependent ones)
+    return ((unsigned long long)d.change_off + d.n_changes <= p.lim_changes) &
+           ((unsigned long long)d.dep_off + d.n_deps <= p.lim_deps) &
+           ((unsigned long long)d.op_off + d.n_ops <= p.lim_ops) &
+           ((unsigned long long)d.reg_off + d.n_regs <= p.lim_regs) & (d.n_actors <= p.a_stride);
 }
 #endif
 #ifdef __HIPCC__

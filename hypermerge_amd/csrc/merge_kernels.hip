@@ -87,6 +87,9 @@
 #ifndef HM_KARG_RELOAD
 #define HM_KARG_RELOAD 1    // merge_small_kernel: launch parameters re-read per document (see the kernel)
 #endif
+#ifndef HM_KARG_BATCH
+#define HM_KARG_BATCH 1     // five-wave instantiations: the fields a phase reads are requested in one batch where it begins
+#endif
 #ifndef HM_HIST_DP
 #define HM_HIST_DP 1        // queued documents: history by the parallel (t, pass, pos) solve before the pass loop
 #endif
@@ -128,7 +131,12 @@
 #define HM_OPAQUE_LANE 1    // per-document lane index the compiler cannot hoist out of the document loop
 #endif
 #ifndef HM_WAVES_PER_EU
-#define HM_WAVES_PER_EU 4   // register-allocator target: LDS already caps C4-class launches at ~4.25 waves/SIMD
+#define HM_WAVES_PER_EU 5   // map documents of <= 128 ops in the two small carves (classes 0 and 2): 96 VGPRs, no
+                            // spill (tools/kernel_resources.sh); the C4 carve (7,680 B allocated) lets 21 one-wave
+                            // workgroups share a CU's LDS, so registers decide: 20 per CU
+#endif
+#ifndef HM_WAVES_PER_EU_WIDE
+#define HM_WAVES_PER_EU_WIDE 4  // list launches and the class-1 carve (LDS holds fewer waves than that anyway)
 #endif
 #define WAVE 64
 #define NA_MAX 8
@@ -208,6 +216,17 @@ __device__ __forceinline__ uint32_t fresh_lane() {
     return threadIdx.x;
 #endif
 }
+// The instantiations held to 96 VGPRs (five waves per SIMD) take a fresh lane index in every
+// phase: whatever a phase derives from it (byte offsets, lane masks, comparisons) then lives
+// for that phase only.  Hoisted, those values filled some twenty registers across the whole
+// loop; the others keep threadIdx.x.
+template <bool FRESH> __device__ __forceinline__ uint32_t lane_id() {
+    if constexpr (FRESH) return fresh_lane();
+    else return threadIdx.x;
+}
+// (the instantiations that run at five waves: list launches and the class-1 carve keep threadIdx.x
+// and their parameter loads where they are used)
+template <int OPL, bool LISTS, int CLS> struct Diet { static constexpr bool on = OPL <= 2 && !LISTS && CLS != 1; };
 // One-wave workgroups: a wave's LDS instructions execute in issue order, so an exchange
 // through LDS between lanes needs only a compiler ordering point — no s_waitcnt, no barrier
 // (__syncthreads' workgroup fence would drain lgkmcnt at every exchange).
@@ -360,12 +379,12 @@ __device__ __forceinline__ void need_set(uint32_t &lo, uint32_t &hi, uint32_t a,
 // words, bank = slot mod 32) put on a handful of banks (4-way conflicts on C4's 8 x 8 logs)
 __device__ __forceinline__ uint32_t fidx(uint32_t a, uint32_t s) { return (s & 63) * NA_MAX + (a & (NA_MAX - 1)); }
 // all ones, two 16-byte stores per lane
-__device__ __forceinline__ void clear_first(LDS uint32_t *first) {
+__device__ __forceinline__ void clear_first(LDS uint32_t *first, uint32_t lane) {
     static_assert(NA_MAX * 64 == 2 * WAVE * 4, "first-table size");
     LDS uint4 *f4 = (LDS uint4 *)first;
     const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);
-    f4[threadIdx.x] = ones;
-    f4[threadIdx.x + WAVE] = ones;
+    f4[lane] = ones;
+    f4[lane + WAVE] = ones;
 }
 
 // tie order key of an assign at position p on its register: odd p first (p descending),
@@ -628,13 +647,17 @@ __device__ unsigned long long hm_async_checked, hm_async_bad;
 template <int OPL>
 __device__ __forceinline__ void async_check(const SmallParams &p, const hm_doc_row &doc, const Rows &got) {
     const Rows want = load_rows<OPL>(p, doc);
+    const uint32_t lane = threadIdx.x;
     auto ne4 = [](uint4 a, uint4 b) { return a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w; };
     auto ne2 = [](uint2 a, uint2 b) { return a.x != b.x || a.y != b.y; };
-    bool bad = ne4(want.c01, got.c01) || ne2(want.c2, got.c2) || ne4(want.a0, got.a0) || ne4(want.b0, got.b0) ||
-               ne2(want.d0, got.d0) || ne2(want.d1, got.d1);
-    if (OPL > 1) bad = bad || ne4(want.a1, got.a1) || ne4(want.b1, got.b1);
-    if (OPL > 2) bad = bad || ne4(want.a2, got.a2) || ne4(want.b2, got.b2);
-    if (OPL > 3) bad = bad || ne4(want.a3, got.a3) || ne4(want.b3, got.b3);
+    // the change words on every lane (zero past the table); op and dep rows on the lanes that
+    // hold one (the others keep the table's last row, which no consumer reads)
+    auto op_ne = [&](uint32_t k, uint4 wa, uint4 wb, uint4 ga, uint4 gb) { return k < doc.n_ops && (ne4(wa, ga) || ne4(wb, gb)); };
+    bool bad = ne4(want.c01, got.c01) || ne2(want.c2, got.c2) || op_ne(lane, want.a0, want.b0, got.a0, got.b0) ||
+               (lane < doc.n_deps && ne2(want.d0, got.d0)) || (lane + WAVE < doc.n_deps && ne2(want.d1, got.d1));
+    if (OPL > 1) bad = bad || op_ne(lane + WAVE, want.a1, want.b1, got.a1, got.b1);
+    if (OPL > 2) bad = bad || op_ne(lane + 2 * WAVE, want.a2, want.b2, got.a2, got.b2);
+    if (OPL > 3) bad = bad || op_ne(lane + 3 * WAVE, want.a3, want.b3, got.a3, got.b3);
     const unsigned long long m = __ballot(bad);
     if (threadIdx.x == 0) {
         atomicAdd(&hm_async_checked, 1ull);
@@ -647,8 +670,8 @@ __device__ __forceinline__ void async_check(const SmallParams &p, const hm_doc_r
 // waits with an explicit vmcnt(N) — N the store instructions write_outputs is certain to issue
 // after them on the path taken — instead of the vmcnt(0) a counted load gets, which also waited
 // for every one of this document's stores.  Lanes past a table's rows re-load its last row (every
-// address stays inside the document's range; a uniform branch skips an empty table) and are zeroed
-// once the data is in.  The destinations are named "+v" by the wait statement, so no consumer is
+// address stays inside the document's range; a uniform branch skips an empty table); their change
+// words are zeroed once the data is in.  The destinations are named "+v" by the wait statement, so no consumer is
 // scheduled above it (cdna_hip_programming.md, 'What hipcc does not do' item 1, form ii).
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -658,94 +681,85 @@ struct AsyncRows { u32x2 c0, c1, c2; u32x4 a0, b0, a1, b1, a2, b2, a3, b3; u32x2
 #else
 #define HM_AL_POL ""
 #endif
-__device__ __forceinline__ u32x2 aload2(const void *p) {
+// Scalar-base form: a table's base plus the document's offset is wave-uniform (an SGPR pair), the
+// lane's part a 32-bit byte offset (row index x row size, < 2^16), the second half of a row an
+// immediate offset: no 64-bit address arithmetic and no address register pairs per lane.
+template <int IMM> __device__ __forceinline__ u32x2 aload2(const void *base, uint32_t off) {
     u32x2 v;
-    asm volatile("global_load_dwordx2 %0, %1, off" HM_AL_POL : "=v"(v) : "v"(p) : "memory");
+    asm volatile("global_load_dwordx2 %0, %1, %2 offset:%3" HM_AL_POL : "=v"(v) : "v"(off), "s"(base), "n"(IMM) : "memory");
     return v;
 }
-__device__ __forceinline__ u32x4 aload4(const void *p) {
+template <int IMM> __device__ __forceinline__ u32x4 aload4(const void *base, uint32_t off) {
     u32x4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off" HM_AL_POL : "=v"(v) : "v"(p) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" HM_AL_POL : "=v"(v) : "v"(off), "s"(base), "n"(IMM) : "memory");
     return v;
 }
-template <int OPL>
-__device__ __forceinline__ AsyncRows load_rows_async(const SmallParams &p, const hm_doc_row &doc) {
-    const uint32_t lane = threadIdx.x;
+template <int OPL, bool LISTS>
+__device__ __forceinline__ AsyncRows load_rows_async(const SmallParams &p, const hm_doc_row &doc, uint32_t lane) {
     AsyncRows r;
     r.c0 = r.c1 = r.c2 = r.d0 = r.d1 = u32x2{0u, 0u};
     r.a0 = r.b0 = r.a1 = r.b1 = r.a2 = r.b2 = r.a3 = r.b3 = u32x4{0u, 0u, 0u, 0u};
+    static_assert(sizeof(hm_change_row) == 24 && sizeof(hm_op_row) == 32 && sizeof(hm_dep_row) == 8, "row sizes");
+    auto row = [&](uint32_t k, uint32_t n) { return k < n ? k : n - 1u; };      // (n > 0) lanes past the table: its last row
     if (doc.n_changes) {
-        const uint32_t i = lane < doc.n_changes ? lane : doc.n_changes - 1u;
-        const uint2 *cs = reinterpret_cast<const uint2 *>(p.changes + doc.change_off + i);
-        r.c0 = aload2(cs); r.c1 = aload2(cs + 1); r.c2 = aload2(cs + 2);
+        const hm_change_row *cs = p.changes + doc.change_off;
+        const uint32_t o = row(lane, doc.n_changes) * 24u;
+        r.c0 = aload2<0>(cs, o); r.c1 = aload2<8>(cs, o); r.c2 = aload2<16>(cs, o);
     }
     if (doc.n_ops) {
-        const uint32_t i0 = lane < doc.n_ops ? lane : doc.n_ops - 1u;
-        const uint4 *o0 = reinterpret_cast<const uint4 *>(p.ops + doc.op_off + i0);
-        r.a0 = aload4(o0); r.b0 = aload4(o0 + 1);
+        const hm_op_row *os = p.ops + doc.op_off;
+        const uint32_t o0 = row(lane, doc.n_ops) * 32u;
+        r.a0 = aload4<0>(os, o0); r.b0 = aload4<16>(os, o0);
         if (OPL > 1) {
-            const uint32_t i1 = lane + WAVE < doc.n_ops ? lane + WAVE : doc.n_ops - 1u;
-            const uint4 *o1 = reinterpret_cast<const uint4 *>(p.ops + doc.op_off + i1);
-            r.a1 = aload4(o1); r.b1 = aload4(o1 + 1);
+            const uint32_t o1 = row(lane + WAVE, doc.n_ops) * 32u;
+            r.a1 = aload4<0>(os, o1); r.b1 = aload4<16>(os, o1);
         }
         if (OPL > 2) {
-            const uint32_t i2 = lane + 2 * WAVE < doc.n_ops ? lane + 2 * WAVE : doc.n_ops - 1u;
-            const uint4 *o2 = reinterpret_cast<const uint4 *>(p.ops + doc.op_off + i2);
-            r.a2 = aload4(o2); r.b2 = aload4(o2 + 1);
+            const uint32_t o2 = row(lane + 2 * WAVE, doc.n_ops) * 32u;
+            r.a2 = aload4<0>(os, o2); r.b2 = aload4<16>(os, o2);
         }
         if (OPL > 3) {
-            const uint32_t i3 = lane + 3 * WAVE < doc.n_ops ? lane + 3 * WAVE : doc.n_ops - 1u;
-            const uint4 *o3 = reinterpret_cast<const uint4 *>(p.ops + doc.op_off + i3);
-            r.a3 = aload4(o3); r.b3 = aload4(o3 + 1);
+            const uint32_t o3 = row(lane + 3 * WAVE, doc.n_ops) * 32u;
+            r.a3 = aload4<0>(os, o3); r.b3 = aload4<16>(os, o3);
         }
     }
     if (doc.n_deps) {
-        const uint32_t i0 = lane < doc.n_deps ? lane : doc.n_deps - 1u, i1 = lane + WAVE < doc.n_deps ? lane + WAVE : doc.n_deps - 1u;
-        r.d0 = aload2(p.deps + doc.dep_off + i0); r.d1 = aload2(p.deps + doc.dep_off + i1);
+        const hm_dep_row *dp = p.deps + doc.dep_off;
+        r.d0 = aload2<0>(dp, row(lane, doc.n_deps) * 8u); r.d1 = aload2<0>(dp, row(lane + WAVE, doc.n_deps) * 8u);
     }
     return r;
 }
-// the wait (see above) and the rows as load_rows returns them: write_outputs padded an OK
-// document's stores to at least HM_ASYNC_STORES instructions after the loads (pad_stores), so
-// one fixed wait leaves every one of them in flight; other outcomes wait for everything.  (One
-// asm statement: a wait chosen at run time would merge register values after it, and the copies
-// the compiler may then place ahead of the wait read the destinations before the data lands.)
-template <int OPL>
-__device__ __forceinline__ Rows take_rows_async(AsyncRows &r, const hm_doc_row &doc, bool padded) {
+// the wait (see above) and the rows as load_rows returns them: pad_stores brought the store
+// instructions issued after the loads to at least HM_ASYNC_STORES whatever the document's outcome,
+// so one fixed wait leaves that many in flight.  One asm statement on one path: with a wait per
+// outcome the destinations' values merged after the two statements, and the compiler placed the
+// register copies of one side ahead of its wait, where they read the destinations before the
+// data had landed (seen in the generated code once the rows were no longer zeroed by selects).
+template <int OPL, bool DIET>
+__device__ __forceinline__ Rows take_rows_async(AsyncRows &r, const hm_doc_row &doc) {
     // (the statement names only the destinations this instantiation loads: a pinned unused one
     // costs a register across write_outputs)
 #define HM_AW2 "+v"(r.c0), "+v"(r.c1), "+v"(r.c2), "+v"(r.a0), "+v"(r.b0), "+v"(r.a1), "+v"(r.b1), "+v"(r.d0), "+v"(r.d1)
 #define HM_AW3 HM_AW2, "+v"(r.a2), "+v"(r.b2)
 #define HM_AW4 HM_AW3, "+v"(r.a3), "+v"(r.b3)
-    if constexpr (OPL <= 2) {
-        if (padded) asm volatile("s_waitcnt vmcnt(%9)" : HM_AW2 : "n"(HM_ASYNC_STORES) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" : HM_AW2 :: "memory");
-    } else if constexpr (OPL == 3) {
-        if (padded) asm volatile("s_waitcnt vmcnt(%11)" : HM_AW3 : "n"(HM_ASYNC_STORES) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" : HM_AW3 :: "memory");
-    } else {
-        if (padded) asm volatile("s_waitcnt vmcnt(%13)" : HM_AW4 : "n"(HM_ASYNC_STORES) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" : HM_AW4 :: "memory");
-    }
+    if constexpr (OPL <= 2) asm volatile("s_waitcnt vmcnt(%9)" : HM_AW2 : "n"(HM_ASYNC_STORES) : "memory");
+    else if constexpr (OPL == 3) asm volatile("s_waitcnt vmcnt(%11)" : HM_AW3 : "n"(HM_ASYNC_STORES) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%13)" : HM_AW4 : "n"(HM_ASYNC_STORES) : "memory");
 #undef HM_AW4
 #undef HM_AW3
 #undef HM_AW2
-    const uint32_t lane = threadIdx.x;
+    // Only the change words are zeroed past the table (change_of: "zero rows for lanes >= n");
+    // the op and dep rows of such lanes (the table's last row again) are never read: stage_op
+    // and the dep staging skip them.
+    const bool c = lane_id<DIET>() < doc.n_changes;
     Rows o;
-    const bool c = lane < doc.n_changes, k0 = lane < doc.n_ops, k1 = lane + WAVE < doc.n_ops;
     o.c01 = c ? make_uint4(r.c0.x, r.c0.y, r.c1.x, r.c1.y) : make_uint4(0u, 0u, 0u, 0u);
     o.c2 = c ? make_uint2(r.c2.x, r.c2.y) : make_uint2(0u, 0u);
-    o.a0 = k0 ? make_uint4(r.a0.x, r.a0.y, r.a0.z, r.a0.w) : make_uint4(0u, 0u, 0u, 0u);
-    o.b0 = k0 ? make_uint4(r.b0.x, r.b0.y, r.b0.z, r.b0.w) : make_uint4(0u, 0u, 0u, 0u);
-    o.a1 = k1 ? make_uint4(r.a1.x, r.a1.y, r.a1.z, r.a1.w) : make_uint4(0u, 0u, 0u, 0u);
-    o.b1 = k1 ? make_uint4(r.b1.x, r.b1.y, r.b1.z, r.b1.w) : make_uint4(0u, 0u, 0u, 0u);
-    const bool k2 = lane + 2 * WAVE < doc.n_ops, k3 = lane + 3 * WAVE < doc.n_ops;
-    o.a2 = k2 ? make_uint4(r.a2.x, r.a2.y, r.a2.z, r.a2.w) : make_uint4(0u, 0u, 0u, 0u);
-    o.b2 = k2 ? make_uint4(r.b2.x, r.b2.y, r.b2.z, r.b2.w) : make_uint4(0u, 0u, 0u, 0u);
-    o.a3 = k3 ? make_uint4(r.a3.x, r.a3.y, r.a3.z, r.a3.w) : make_uint4(0u, 0u, 0u, 0u);
-    o.b3 = k3 ? make_uint4(r.b3.x, r.b3.y, r.b3.z, r.b3.w) : make_uint4(0u, 0u, 0u, 0u);
-    o.d0 = lane < doc.n_deps ? make_uint2(r.d0.x, r.d0.y) : make_uint2(0u, 0u);
-    o.d1 = lane + WAVE < doc.n_deps ? make_uint2(r.d1.x, r.d1.y) : make_uint2(0u, 0u);
+    o.a0 = make_uint4(r.a0.x, r.a0.y, r.a0.z, r.a0.w); o.b0 = make_uint4(r.b0.x, r.b0.y, r.b0.z, r.b0.w);
+    o.a1 = make_uint4(r.a1.x, r.a1.y, r.a1.z, r.a1.w); o.b1 = make_uint4(r.b1.x, r.b1.y, r.b1.z, r.b1.w);
+    o.a2 = make_uint4(r.a2.x, r.a2.y, r.a2.z, r.a2.w); o.b2 = make_uint4(r.b2.x, r.b2.y, r.b2.z, r.b2.w);
+    o.a3 = make_uint4(r.a3.x, r.a3.y, r.a3.z, r.a3.w); o.b3 = make_uint4(r.b3.x, r.b3.y, r.b3.z, r.b3.w);
+    o.d0 = make_uint2(r.d0.x, r.d0.y); o.d1 = make_uint2(r.d1.x, r.d1.y);
     return o;
 }
 #endif
@@ -768,10 +782,10 @@ __device__ __forceinline__ void stage_op(const SmallLds &L, uint32_t k, uint32_t
     L.opval[k] = ((u64)b.w << 32) | b.z;
     if (LISTS) L.opelem[k] = a.w;
 }
-template <int OPL, bool LISTS>
+template <int OPL, bool LISTS, bool DIET>
 __device__ __forceinline__ void stage_rows(const SmallParams &p, const SmallLds &L, const hm_doc_row &doc, const Rows &r,
                                            uint32_t cap_deps) {
-    const uint32_t lane = threadIdx.x, m = doc.n_ops;
+    const uint32_t lane = lane_id<DIET>(), m = doc.n_ops;
     stage_op<LISTS>(L, lane, m, r.a0, r.b0);
     if (OPL > 1) stage_op<LISTS>(L, lane + WAVE, m, r.a1, r.b1);
     if (OPL > 2) stage_op<LISTS>(L, lane + 2 * WAVE, m, r.a2, r.b2);
@@ -832,10 +846,10 @@ __device__ __forceinline__ OpCheck op_check(const SmallLds &L, int32_t ohv, uint
 }
 
 // Merge one document with the whole wave (no global stores).  Every return is wave-uniform.
-template <int OPL, bool LISTS>
+template <int OPL, bool LISTS, bool DIET>
 __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const SmallLds &L, const hm_doc_row &doc,
                                                    const uint2 w0, const uint2 w1, const uint2 w2, DocState &st) {
-    const uint32_t lane = threadIdx.x;
+    uint32_t lane = lane_id<DIET>();          // (taken again at the phase boundaries below)
     const uint32_t n = doc.n_changes, A = doc.n_actors, m = doc.n_ops, R = doc.n_regs, O = doc.n_objs;
     st.hist = -1; st.H = 0; st.total = 0; st.doc_lists = false;
 
@@ -845,7 +859,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     if (HM_PRIO_K1) __builtin_amdgcn_s_setprio(HM_PRIO_K1);
     const bool act = lane < n;
     const hm_change_row c = change_of(w0, w1, w2);      // zero rows for lanes >= n (load_rows)
-    clear_first(L.first);
+    clear_first(L.first, lane);
     if (lane < NA_MAX) { L.base[lane] = 0xFFFFFFFFu; L.bclock[lane] = 0; L.headv[lane] = 0; L.chain[lane] = 0; }
     if (lane == 0) { *L.errkey = ~0ull; L.flags[0] = 0; L.flags[1] = 0; *L.cov = 0; }
     const uint32_t dep_lo = doc.dep_off, ndep = doc.n_deps;
@@ -881,6 +895,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     wave_sync();
 
     STAMP(L, 1);
+    if constexpr (DIET) lane = fresh_lane();
     if (HM_ABLATE & 16) return OUT_UNSUPPORTED;
     // Every dep row at once: its lookups (the actor's base seq, then the first-arrival table)
     // are done per row here, so the per-change loop below reads one LDS word per dep.
@@ -941,6 +956,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     wave_sync();
 
     STAMP(L, 2);
+    if constexpr (DIET) lane = fresh_lane();
     if (HM_ABLATE & 32) return OUT_UNSUPPORTED;
     int32_t hist = -1;
     uint32_t H = 0;
@@ -1201,6 +1217,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
         // as bytes (0x7F = never satisfiable in this batch)
         uint32_t need_lo = 0, need_hi = 0;
         if (act) {
+#pragma unroll 1        // (a rare path: unrolled by four it spilled two registers at 96 VGPRs)
             for (uint32_t j = 0; j < c.n_deps; j++) {
                 const uint32_t inf = L.depinfo[my_dep0 + j];
                 const uint32_t a = (inf >> 16) & (NA_MAX - 1), rel = (inf >> 8) & 0x7F;
@@ -1209,7 +1226,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
             const uint32_t ps = seq - 1;
             need_set(need_lo, need_hi, a8, ps != 0 ? (ps >= mybase ? ps - mybase + 1 : 0x7Fu) : 0u);
         }
-        clear_first(L.first);                                                           // -> applied lane
+        clear_first(L.first, lane);                                                           // -> applied lane
         wave_sync();
         uint32_t crel_lo = 0, crel_hi = 0;      // relative applied clock per actor (bytes)
         u64 queued = 0;
@@ -1275,6 +1292,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
 
     if (HM_PRIO_HIST && queued_doc) __builtin_amdgcn_s_setprio(0);
     STAMP(L, 3);
+    if constexpr (DIET) lane = fresh_lane();
     if (HM_ABLATE & 512) return OUT_UNSUPPORTED;
     // ---------------- K1b: ancestor sets in history order ----------------
     if (act) L.hist_of[lane] = hist;
@@ -1353,6 +1371,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     if (hv) L.anc[lane] = anc;
     wave_sync();
     STAMP(L, 4);
+    if constexpr (DIET) lane = fresh_lane();
     if (HM_ABLATE & 64) return OUT_UNSUPPORTED;
     const u64 covered = *L.cov;
     // transitiveDeps folds deps.set(actor, seq-1) in key order: acc = max(acc, FC(d)); acc[a_d] = s_d.
@@ -1389,6 +1408,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     wave_sync();
 
     STAMP(L, 5);
+    if constexpr (DIET) lane = fresh_lane();
     if (HM_PRIO_FOLD && !HM_PRIO_K2) __builtin_amdgcn_s_setprio(0);
     if (HM_PRIO_K2) __builtin_amdgcn_s_setprio(HM_PRIO_K2);
     if (HM_ABLATE & 2) return OUT_UNSUPPORTED;
@@ -1431,6 +1451,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
         }
     }
     STAMP(L, 6);
+    if constexpr (DIET) lane = fresh_lane();
     if (HM_ABLATE & 128) return OUT_UNSUPPORTED;
     if (__ballot(malformed)) return OUT_UNSUPPORTED;
     // counter sums need the carve's survsum table (launches flagged HM_DOC_HAS_COUNTERS)
@@ -1478,6 +1499,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     if (*L.flags & FL_UNSUPPORTED) return OUT_UNSUPPORTED;
 
     STAMP(L, 7);
+    if constexpr (DIET) lane = fresh_lane();
     if (HM_PRIO_K2 && !HM_PRIO_RANK) __builtin_amdgcn_s_setprio(0);
     if (HM_PRIO_RANK) __builtin_amdgcn_s_setprio(HM_PRIO_RANK);
     if (HM_ABLATE & 4) return OUT_UNSUPPORTED;
@@ -1573,6 +1595,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     wave_sync();
     if (HM_PRIO_RANK) __builtin_amdgcn_s_setprio(0);
     STAMP(L, 8);
+    if constexpr (DIET) lane = fresh_lane();
     if (HM_ABLATE & 256) return OUT_UNSUPPORTED;
     if constexpr (LISTS) {
         if (doc_lists) {
@@ -1634,8 +1657,9 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
 // Clock.cmp(DocBackend.clock, minimumClock) of a merged document, from the min_clock row loaded
 // before the merge (mc, lane < S): computed before the next document's rows are requested, so
 // no wait for that load sits behind the prefetch and this document's stores
-__device__ __forceinline__ uint32_t min_cmp_of(const SmallParams &p, const SmallLds &L, const hm_doc_row &doc, uint32_t mc) {
-    const uint32_t lane = threadIdx.x, S = p.a_stride;
+__device__ __forceinline__ uint32_t min_cmp_of(const SmallParams &p, const SmallLds &L, const hm_doc_row &doc, uint32_t mc,
+                                               uint32_t lane) {
+    const uint32_t S = p.a_stride;
     const uint32_t bc = (lane < S && lane < doc.n_actors) ? L.bclock[lane] : 0u;
     const bool aGTE = __ballot(lane < S && bc < mc) == 0;
     const bool bGTE = __ballot(lane < S && mc < bc) == 0;
@@ -1645,9 +1669,8 @@ __device__ __forceinline__ uint32_t min_cmp_of(const SmallParams &p, const Small
 // A merged document's survivor rows, read out of LDS into registers (lane + WAVE t): the next
 // document's rows overwrite the op tables they come from before these are stored.
 template <int OPL> struct SurvRows { hm_surv_result r[OPL]; };
-template <int OPL>
-__device__ __forceinline__ SurvRows<OPL> surv_rows(const SmallParams &p, const SmallLds &L, const DocState &st) {
-    const uint32_t lane = threadIdx.x;
+template <int OPL, bool LISTS>
+__device__ __forceinline__ SurvRows<OPL> surv_rows(const SmallParams &p, const SmallLds &L, const DocState &st, uint32_t lane) {
     SurvRows<OPL> o;
 #pragma unroll
     for (int t = 0; t < OPL; t++) {
@@ -1679,11 +1702,21 @@ __device__ __forceinline__ void st4(void *dst, uint32_t v) {
     *reinterpret_cast<uint32_t *>(dst) = v;
 #endif
 }
-template <int OPL, bool LISTS>
+// The result row of a document that was not merged here (the rare outcomes).  Its words are made
+// opaque inside the branch: as plain constants the compiler built the rows
+// once, ahead of the document loop, and held them in VGPR tuples across every merge.
+__device__ __forceinline__ void put_status_row(hm_doc_result *dres, uint32_t status, uint32_t err_change, uint32_t err_op) {
+    uint32_t zero = 0u;
+    asm volatile("" : "+v"(status), "+v"(err_change), "+v"(err_op), "+v"(zero));
+    hm_doc_result r;
+    r.status = (int32_t)status; r.err_change = err_change; r.err_op = err_op;
+    r.hist_len = zero; r.n_queued = zero; r.n_surv = zero; r.min_cmp = zero; r.pad = zero;
+    *dres = r;
+}
+template <int OPL, bool LISTS, bool DIET>
 __device__ __forceinline__ void write_outputs(const SmallParams &p, const SmallLds &L, uint32_t d, uint32_t ds,
                                               const hm_doc_row &doc, Outcome oc, const DocState &st, uint32_t mcmp,
-                                              const SurvRows<OPL> &sv) {
-    const uint32_t lane = threadIdx.x;
+                                              const SurvRows<OPL> &sv, uint32_t lane) {
     const uint32_t S = p.a_stride;
     const uint32_t n = doc.n_changes, A = doc.n_actors, R = doc.n_regs;
     hm_doc_result *dres = p.res_docs + ds;      // ds: row of the per-document outputs
@@ -1691,50 +1724,47 @@ __device__ __forceinline__ void write_outputs(const SmallParams &p, const SmallL
         // an Automerge throw aborted this document's Backend.applyChanges
         const u64 ek = *L.errkey;
         if (lane == 0) {
-            hm_doc_result r = {};
-            r.status = (int32_t)(ek & 0xFF);
-            r.err_change = (uint32_t)((ek >> 8) & 0xFFFF);
-            const uint32_t opp1 = (uint32_t)((ek >> 24) & 0xFFFF);
-            r.err_op = opp1 ? opp1 - 1 : HM_NONE;
-            if (r.status == HM_ERR_UNSUPPORTED) { r.err_change = HM_NONE; r.err_op = HM_NONE; }
-            *dres = r;
+            const uint32_t status = (uint32_t)(ek & 0xFF), opp1 = (uint32_t)((ek >> 24) & 0xFFFF);
+            const bool uns = status == HM_ERR_UNSUPPORTED;
+            put_status_row(dres, status, uns ? HM_NONE : (uint32_t)((ek >> 8) & 0xFFFF), (uns || !opp1) ? HM_NONE : opp1 - 1);
         }
         return;
     }
     if (oc == OUT_INVALID) {
         // malformed row (ranges outside the batch tables): nothing of it is read or written
-        if (lane == 0) {
-            hm_doc_result r = {};
-            r.status = HM_ERR_INVALID; r.err_change = HM_NONE; r.err_op = HM_NONE;
-            *dres = r;
-        }
-        for (uint32_t a = lane; a < S; a += WAVE) {
-            p.res_clock[(size_t)ds * S + a] = 0u; p.res_heads[(size_t)ds * S + a] = 0u;
-            p.res_back_clock[(size_t)ds * S + a] = 0u;
-        }
+        if (lane == 0) put_status_row(dres, (uint32_t)HM_ERR_INVALID, HM_NONE, HM_NONE);
+        uint32_t *ck = p.res_clock + (size_t)ds * S, *hd = p.res_heads + (size_t)ds * S, *bk = p.res_back_clock + (size_t)ds * S;
+        for (uint32_t a = lane; a < S; a += WAVE) { ck[a] = 0u; hd[a] = 0u; bk[a] = 0u; }
         return;
     }
     if (oc == OUT_UNSUPPORTED) {
         // outside this kernel's envelope: merge_large_kernel finds the status and takes the document
         if (lane == 0) {
-            hm_doc_result r = {};
-            r.status = HM_DEFERRED; r.err_change = HM_NONE; r.err_op = HM_NONE;
-            *dres = r;
+            put_status_row(dres, (uint32_t)HM_DEFERRED, HM_NONE, HM_NONE);
 #if !HM_ABLATE
             p.deferred[atomicAdd(p.n_deferred, 1u)] = d;     // merge_large_kernel's work list
 #endif
         }
         return;
     }
+    // Every table's address is a wave-uniform row base (the table plus the document's offset, on
+    // the scalar unit) plus the lane's 32-bit part: the stores take the scalar-base form, with
+    // no 64-bit address arithmetic per lane.
+#if HM_KARG_RELOAD
+    if constexpr (DIET && HM_KARG_BATCH)
+        asm volatile("" :: "s"(p.res_docs), "s"(p.res_clock), "s"(p.res_back_clock), "s"(p.res_heads), "s"(p.res_hist),
+                     "s"(p.res_all_deps), "s"(p.res_regs), "s"(p.res_surv));     // (see the document loop)
+#endif
+    hm_reg_result *regs = p.res_regs + doc.reg_off;
     for (uint32_t r = lane; r < R; r += WAVE) {
         const int32_t li = (LISTS && st.doc_lists) ? (int32_t)L.insmin[r] : -1;
-        st16(p.res_regs + doc.reg_off + r, make_uint4(L.survcnt[r], L.regoff[r], (uint32_t)li, L.regobj[r]));
+        st16(regs + r, make_uint4(L.survcnt[r], L.regoff[r], (uint32_t)li, L.regobj[r]));
     }
     // allDeps rows: lane = arrival index writes its change's row (zeros if not applied;
     // chain[a] is empty for a >= A)
     if (lane < n) {
         const u64 an = st.hist >= 0 ? L.anc[st.hist] : 0ull;
-        uint32_t *row = p.res_all_deps + (size_t)(doc.change_off + lane) * S;
+        uint32_t *row = (p.res_all_deps + (size_t)doc.change_off * S) + lane * S;     // (lane * S < 2^14)
         if (S == 8 || S == 4) {
             uint32_t v[NA_MAX];
 #pragma unroll
@@ -1745,18 +1775,17 @@ __device__ __forceinline__ void write_outputs(const SmallParams &p, const SmallL
             for (uint32_t a = 0; a < S; a++) row[a] = a < NA_MAX ? (uint32_t)__popcll(an & L.chain[a]) : 0u;
         }
     }
+    uint32_t *ck = p.res_clock + (size_t)ds * S, *hd = p.res_heads + (size_t)ds * S, *bk = p.res_back_clock + (size_t)ds * S;
     if (lane < S) {
         const bool ar = lane < A;
-        p.res_clock[(size_t)ds * S + lane] = ar ? (uint32_t)__popcll(L.chain[lane]) : 0u;
-        p.res_heads[(size_t)ds * S + lane] = ar ? L.headv[lane] : 0u;
-        p.res_back_clock[(size_t)ds * S + lane] = ar ? L.bclock[lane] : 0u;   // DocBackend.clock (queued included)
+        ck[lane] = ar ? (uint32_t)__popcll(L.chain[lane]) : 0u;
+        hd[lane] = ar ? L.headv[lane] : 0u;
+        bk[lane] = ar ? L.bclock[lane] : 0u;                              // DocBackend.clock (queued included)
     }
-    for (uint32_t a = WAVE + lane; a < S; a += WAVE) {                   // wide rows: actors >= 64 are absent
-        p.res_clock[(size_t)ds * S + a] = 0u; p.res_heads[(size_t)ds * S + a] = 0u; p.res_back_clock[(size_t)ds * S + a] = 0u;
-    }
+    for (uint32_t a = WAVE + lane; a < S; a += WAVE) { ck[a] = 0u; hd[a] = 0u; bk[a] = 0u; }   // wide rows: actors >= 64 are absent
     const bool act = lane < n;
     const u64 q = __ballot(act && st.hist == -1);
-    if (act) st4(p.res_hist + doc.change_off + lane, (uint32_t)st.hist);
+    if (act) st4((p.res_hist + doc.change_off) + lane, (uint32_t)st.hist);
     if (lane == 0) {
         hm_doc_result r = {};
         r.status = HM_OK; r.err_change = HM_NONE; r.err_op = HM_NONE;
@@ -1767,7 +1796,7 @@ __device__ __forceinline__ void write_outputs(const SmallParams &p, const SmallL
 #pragma unroll
     for (int t = 0; t < OPL; t++) {
         const uint32_t q = lane + WAVE * t;
-        if (q < st.total) st16(p.res_surv + doc.op_off + q, make_uint4(sv.r[t].op, sv.r[t].vtag, (uint32_t)sv.r[t].value,
+        if (q < st.total) st16((p.res_surv + doc.op_off) + q, make_uint4(sv.r[t].op, sv.r[t].vtag, (uint32_t)sv.r[t].value,
                                                                        (uint32_t)(sv.r[t].value >> 32)));
     }
 }
@@ -1780,6 +1809,7 @@ __device__ __forceinline__ void write_outputs(const SmallParams &p, const SmallL
 // are changes), the 32-byte result row (two: no store is wider than 16 bytes), the survivor rows
 // (one dwordx4 per 64).  pad_stores tops it up to HM_ASYNC_STORES with stores of the result row's
 // pad word (zero, as the row itself wrote it), issued by asm so each is exactly one instruction.
+// The count is of instructions, whatever their addressing form (scalar base or per-lane pointer).
 template <int OPL>
 __device__ __forceinline__ uint32_t out_stores_min(const SmallParams &p, const hm_doc_row &doc, const DocState &st) {
     const uint32_t S = p.a_stride, n = doc.n_changes;
@@ -1790,19 +1820,25 @@ __device__ __forceinline__ uint32_t out_stores_min(const SmallParams &p, const h
     return c;
 }
 template <int OPL>
-__device__ __forceinline__ void pad_stores(const SmallParams &p, const hm_doc_row &doc, const DocState &st, uint32_t ds) {
+__device__ __forceinline__ void pad_stores(const SmallParams &p, const hm_doc_row &doc, const DocState &st, uint32_t ds, bool ok) {
     uint32_t *pad = &p.res_docs[ds].pad;
     const uint32_t zero = 0u;
-    for (uint32_t c = out_stores_min<OPL>(p, doc, st); c < HM_ASYNC_STORES; c++)      // (wave-uniform)
+    // (a document not merged here counts no store of its own and gets all HM_ASYNC_STORES pad stores,
+    // its result row's pad word being zero too: ten dword stores to one address per such document,
+    // where it took a vmcnt(0) wait before -- extra store traffic on batches that defer or refuse
+    // most documents, e.g. under HM_CFG_GENERAL_ONLY)
+    for (uint32_t c = ok ? out_stores_min<OPL>(p, doc, st) : 0u; c < HM_ASYNC_STORES; c++)      // (wave-uniform)
         asm volatile("global_store_dword %0, %1, off" :: "v"(pad), "v"(zero) : "memory");
 }
 #endif
 
 template <int OPL, bool LISTS, int CLS>
-__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(OPL >= 3 ? (LISTS ? (OPL == 3 ? HM_WAVES_PER_EU_LIST3 : HM_WAVES_PER_EU_OPL4 - 1) : HM_WAVES_PER_EU_OPL4) : HM_WAVES_PER_EU)))
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(OPL >= 3 ? (LISTS ? (OPL == 3 ? HM_WAVES_PER_EU_LIST3 : HM_WAVES_PER_EU_OPL4 - 1) : HM_WAVES_PER_EU_OPL4)
+                                              : (!LISTS && CLS != 1 ? HM_WAVES_PER_EU : HM_WAVES_PER_EU_WIDE))))
 void merge_small_kernel(SmallParams p) {
     extern __shared__ __align__(16) uint8_t lds_raw[];
     typedef SizeClass<CLS> C;
+    constexpr bool DIET = Diet<OPL, LISTS, CLS>::on;
     SmallLds L;
     small_carve((LDS uint8_t *)lds_raw, WAVE * OPL, C::NR, C::NO, C::ND, LISTS, true, &L);
     p.cap_regs = C::NR; p.cap_objs = C::NO; p.cap_deps = C::ND;     // (the loop reads the C:: constants)
@@ -1827,7 +1863,7 @@ void merge_small_kernel(SmallParams p) {
     uint2 w0, w1, w2;                        // this document's change row (lane = arrival index)
     {
         const Rows r = load_rows<OPL>(p, doc);
-        stage_rows<OPL, LISTS>(p, L, doc, r, C::ND);
+        stage_rows<OPL, LISTS, DIET>(p, L, doc, r, C::ND);
         w0 = make_uint2(r.c01.x, r.c01.y); w1 = make_uint2(r.c01.z, r.c01.w); w2 = r.c2;
     }
     wave_sync();
@@ -1835,6 +1871,12 @@ void merge_small_kernel(SmallParams p) {
 #if HM_KARG_RELOAD
         asm volatile("" : "+s"(kp));
         const SmallParams &p = *(const SmallParams *)kp;
+        // The fields a phase reads are requested together where the phase begins (here, ahead of
+        // the next document's row loads, and ahead of the output stores): left to their uses they
+        // were one scalar load per uniform branch, each waited for at once, i.e. a scalar-cache
+        // round trip per field on the wave's path.
+        if constexpr (DIET && HM_KARG_BATCH)
+            asm volatile("" :: "s"(p.n_docs), "s"(p.a_stride), "s"(p.general_only), "s"(p.docs), "s"(p.min_clock), "s"(p.doc_slot));
 #endif
         // software pipeline over this wave's documents: the next document's rows are
         // loaded before this document's stores and staged to LDS after them
@@ -1846,8 +1888,9 @@ void merge_small_kernel(SmallParams p) {
         // is read back after the merge (a uniform load would be moved to scalar registers at once,
         // putting an HBM round trip in front of every document)
         static_assert(sizeof(hm_doc_row) == 12 * sizeof(uint32_t), "doc row words");
+        const uint32_t lane0 = lane_id<DIET>();
         uint32_t docw = 0;
-        if (more && threadIdx.x < 12) docw = reinterpret_cast<const uint32_t *>(p.docs + dn)[threadIdx.x];
+        if (more && lane0 < 12) docw = reinterpret_cast<const uint32_t *>(p.docs + dn)[lane0];
         auto take_docn = [&]() {
             uint32_t w[12];
 #pragma unroll
@@ -1872,7 +1915,7 @@ void merge_small_kernel(SmallParams p) {
         // document's rows are requested (min_cmp_of), so neither waits behind that prefetch
         const uint32_t ds = hm_slot(p, d);
         uint32_t mc = 0;
-        if (p.min_clock && threadIdx.x < p.a_stride) mc = p.min_clock[(size_t)ds * p.a_stride + threadIdx.x];
+        if (p.min_clock && lane0 < p.a_stride) mc = (p.min_clock + (size_t)ds * p.a_stride)[lane0];
         if (p.min_clock && p.a_stride > WAVE) {
             // wide rows (> 64 actors; this kernel merges documents of <= 8): actors >= 64 have
             // DocBackend.clock 0, so they only decide whether any minimumClock entry there is
@@ -1881,20 +1924,38 @@ void merge_small_kernel(SmallParams p) {
             for (uint32_t a = WAVE + threadIdx.x; a < p.a_stride; a += WAVE) extra |= p.min_clock[(size_t)ds * p.a_stride + a];
             if (__ballot(extra != 0) && threadIdx.x == NA_MAX) mc |= 1u;
         }
-        const Outcome oc = !dok ? OUT_INVALID : in_env ? merge_doc_small<OPL, LISTS>(p, L, doc, w0, w1, w2, st) : OUT_UNSUPPORTED;
+        const Outcome oc = !dok ? OUT_INVALID : in_env ? merge_doc_small<OPL, LISTS, DIET>(p, L, doc, w0, w1, w2, st) : OUT_UNSUPPORTED;
         STAMP(L, 9);
-        uint32_t mcmp = oc == OUT_OK ? min_cmp_of(p, L, doc, mc) : 0u;
+        // One lane index for the whole output phase, taken here: between the next document's row
+        // loads and its wait (take_rows_async) no statement may make the compiler wait for memory,
+        // and it waits (vmcnt(0)) ahead of an asm statement whose destination register it believes
+        // a load may still write.
+        const uint32_t lane_io = lane_id<DIET>();
+        uint32_t mcmp = oc == OUT_OK ? min_cmp_of(p, L, doc, mc, lane_io) : 0u;
 #if HM_FENCE_MCMP
         // computed here, not sunk to its use in write_outputs: there its wait for the minimumClock
         // row (s_waitcnt vmcnt(0)) would also wait for the next document's row loads issued below
         asm volatile("" : "+s"(mcmp) :: "memory");
 #endif
+#if HM_ASYNC_NEXT
+        // The next document's row words are waited for here on every path, not only under `more`
+        // below: the compiler tracks outstanding loads per register without regard to the branch
+        // conditions, and a load it believes may still be in flight makes it wait for everything
+        // (vmcnt(0): the row loads issued below included) wherever the register is next written,
+        // which the output phase does.
+        asm volatile("" : "+v"(docw));
+#endif
 #if !HM_PREFETCH_EARLY
         if (more) {
+#if HM_KARG_RELOAD
+            if constexpr (DIET && HM_KARG_BATCH)
+                asm volatile("" :: "s"(p.changes), "s"(p.deps), "s"(p.ops), "s"(p.a_stride), "s"(p.lim_changes), "s"(p.lim_deps),
+                             "s"(p.lim_ops), "s"(p.lim_regs));
+#endif
             take_docn();
             dokn = check_doc(p, docn);
 #if HM_ASYNC_NEXT
-            if constexpr (ASY) anext = load_rows_async<OPL>(p, docn);
+            if constexpr (ASY) anext = load_rows_async<OPL, LISTS>(p, docn, lane_io);
             else
 #endif
             next = load_rows<OPL>(p, docn);
@@ -1902,37 +1963,37 @@ void merge_small_kernel(SmallParams p) {
 #endif
         STAMP(L, 12);
         if (HM_PRIO_IO) __builtin_amdgcn_s_setprio(HM_PRIO_IO);
-        const SurvRows<OPL> sv = surv_rows<OPL>(p, L, st);
+        const SurvRows<OPL> sv = surv_rows<OPL, LISTS>(p, L, st, lane_io);
 #if HM_STAGE_FIRST
         // the next document's rows go to LDS before this document's stores are issued: a wait
         // for a load also waits for every older store (vmcnt counts both in issue order), so
         // staging after the stores waited for all of them; now nothing waits for the stores
         // until the next document's merge has run
         wave_sync();
-        if (more) stage_rows<OPL, LISTS>(p, L, docn, next, C::ND);
+        if (more) stage_rows<OPL, LISTS, DIET>(p, L, docn, next, C::ND);
         STAMP(L, 11);
-        write_outputs<OPL, LISTS>(p, L, d, ds, doc, oc, st, mcmp, sv);
+        write_outputs<OPL, LISTS, DIET>(p, L, d, ds, doc, oc, st, mcmp, sv, lane_io);
         if (HM_PRIO_IO) __builtin_amdgcn_s_setprio(0);
         wave_sync();
         STAMP(L, 10);
         if (!more) break;
 #else
-        write_outputs<OPL, LISTS>(p, L, d, ds, doc, oc, st, mcmp, sv);
+        write_outputs<OPL, LISTS, DIET>(p, L, d, ds, doc, oc, st, mcmp, sv, lane_io);
 #if HM_ASYNC_NEXT
-        if constexpr (ASY) { if (more && oc == OUT_OK) pad_stores<OPL>(p, doc, st, ds); }
+        if constexpr (ASY) { if (more) pad_stores<OPL>(p, doc, st, ds, oc == OUT_OK); }
 #endif
         wave_sync();
         STAMP(L, 10);
         if (!more) break;
 #if HM_ASYNC_NEXT
         if constexpr (ASY) {
-            next = take_rows_async<OPL>(anext, docn, oc == OUT_OK);
+            next = take_rows_async<OPL, DIET>(anext, docn);
 #if HM_ASYNC_CHECK
             async_check<OPL>(p, docn, next);
 #endif
         }
 #endif
-        stage_rows<OPL, LISTS>(p, L, docn, next, C::ND);
+        stage_rows<OPL, LISTS, DIET>(p, L, docn, next, C::ND);
         if (HM_PRIO_IO) __builtin_amdgcn_s_setprio(0);
         wave_sync();
         STAMP(L, 11);

@@ -368,6 +368,12 @@ int hm_store_inc_states(hm_store *s, uint32_t *out);
  * out2[1] = those whose two reads differed (the asynchronous wait was too short); reset zeroes
  * both.  Returns 1 in a check build, 0 in the product build (out2 untouched), < 0 on a HIP error. */
 int hm_debug_async_check(unsigned long long *out2, int reset);
+/* The persistent grid of merge_small_kernel for a host batch (its max_* hints, or its document
+ * table when they are all 0): out6[0] = resident one-wave workgroups per CU of the instantiation
+ * the launch uses (the smaller of the register and the LDS bound), out6[1] = the device's CUs
+ * (the grid is their product, at most n_docs), out6[2..5] = the instantiation itself: op rows per
+ * lane, size class, lists, counters.  Launches nothing.  Returns HM_OK or an hm_status. */
+int hm_debug_small_occupancy(hm_engine *e, const hm_batch *host_batch, uint32_t *out6);
 
 /* Sizes of a document's log and merged state. */
 typedef struct {

@@ -90,6 +90,17 @@ struct Names {
             if (k.h == h && k.tag == tg && k.len == n && !memcmp(arena.data() + k.off, p, n)) { fresh = false; return v - 1; }
         }
     }
+    // the id of a name already interned, or HM_NONE (nothing is added)
+    uint32_t find(const char *p, uint32_t n, uint32_t tg) const {
+        if (slot.empty()) return HM_NONE;
+        const uint32_t h = (uint32_t)hash_bytes(p, n, tg);
+        for (uint32_t i = h & mask;; i = (i + 1) & mask) {
+            const uint32_t v = slot[i];
+            if (!v) return HM_NONE;
+            const K &k = keys[v - 1];
+            if (k.h == h && k.tag == tg && k.len == n && !memcmp(arena.data() + k.off, p, n)) return v - 1;
+        }
+    }
     void truncate(uint32_t n) {
         if (n >= keys.size()) return;
         arena.resize(keys[n].off);
@@ -1950,6 +1961,68 @@ int hm_docset_waiting(hm_docset *ds, uint32_t n, const uint32_t *docs, hm_text *
         return HM_OK;
     } catch (...) {
         return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_waiting");
+    }
+}
+
+int hm_docset_missing_changes(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off,
+                              const char *actor_ids, const uint32_t *actor_off, const double *seqs, uint32_t flags,
+                              hm_text **out) {
+    if (!ds || !out || (n && (!docs || !entry_off))) return HM_ERR_INVALID;
+    *out = nullptr;
+    Busy b(ds);
+    if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
+    try {
+        const uint32_t nd = ds->n_docs.load();
+        for (uint32_t i = 0; i < n; i++) {
+            if (docs[i] >= nd) return hm_engine_fail(ds->e, HM_ERR_INVALID, "bad docset document");
+            if (entry_off[i + 1] < entry_off[i]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "entry_off must not decrease");
+        }
+        if (n && entry_off[n] - entry_off[0] && (!actor_ids || !actor_off || !seqs)) return HM_ERR_INVALID;
+        std::vector<std::string> js(n, "[]");                                    // (a document not placed yet)
+        for (uint32_t c = 0; c < N_CLASS; c++) {
+            std::vector<uint32_t> idx, hs, off(1, 0), eseq;
+            std::vector<uint16_t> eact;
+            for (uint32_t i = 0; i < n; i++) {
+                const DocSt &d = ds->doc(docs[i]);
+                if (d.cls != c) continue;
+                idx.push_back(i); hs.push_back(d.handle);
+                for (uint32_t k = entry_off[i]; k < entry_off[i + 1]; k++) {
+                    if (actor_off[k + 1] < actor_off[k]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease");
+                    const uint32_t a = d.actors.find(actor_ids + actor_off[k], actor_off[k + 1] - actor_off[k], 0);
+                    if (a == HM_NONE || a >= d.rank_of.size()) continue;       // (an actor the document has never seen)
+                    const double v = seqs[k];
+                    eact.push_back(d.rank_of[a]);
+                    eseq.push_back(!(v > 0) ? 0u : v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v);
+                }
+                off.push_back((uint32_t)eact.size());
+            }
+            if (idx.empty()) continue;
+            const uint32_t k = (uint32_t)idx.size();
+            std::vector<uint32_t> rng(2 * (size_t)k), log;
+            uint32_t total = 0;
+            int rc = hm_store_missing_changes(ds->stores[c], k, hs.data(), off.data(), eact.data(), eseq.data(), flags, nullptr,
+                                              rng.data(), nullptr, 0, &total);
+            if (rc == HM_ERR_NOMEM && total) {                   // (the counts are known: now with room)
+                log.resize(total);
+                rc = hm_store_missing_changes(ds->stores[c], k, hs.data(), off.data(), eact.data(), eseq.data(), flags, nullptr,
+                                              rng.data(), log.data(), total, &total);
+            }
+            if (rc) return rc;
+            for (uint32_t j = 0; j < k; j++) {
+                std::string &o = js[idx[j]];
+                o = "[";
+                for (uint32_t r = 0; r < rng[2 * j + 1]; r++) { if (r) o += ','; o += std::to_string(log[rng[2 * j] + r]); }
+                o += ']';
+            }
+        }
+        std::unique_ptr<hm_text> t(new hm_text());
+        t->s = "[";
+        for (uint32_t i = 0; i < n; i++) { if (i) t->s += ','; t->s += js[i]; }
+        t->s += ']';
+        *out = t.release();
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_missing_changes");
     }
 }
 

@@ -16,6 +16,7 @@
 #include "merge_kernels.h"
 #include "engine_internal.h"
 #include "waiting_kernels.h"
+#include "changes_kernels.h"
 
 struct hm_engine {
     int device = 0;
@@ -457,6 +458,109 @@ int hm_missing_deps_host(hm_engine *e, const hm_batch *hb, const hm_results *hr,
         return r == hipSuccess ? HM_OK : hip_fail(e, r, "hm_missing_deps_host");
     } catch (...) {
         return fail(e, HM_ERR_DEVICE, "exception in hm_missing_deps_host");
+    }
+}
+
+static ChangesArgs changes_batch_args(const hm_batch *b, const hm_results *r, const uint32_t *entry_off,
+                                      const uint16_t *entry_actor, const uint32_t *entry_seq, uint32_t n_entries,
+                                      uint32_t flags, uint32_t *out_closure, uint32_t *out_range, uint32_t *out_log,
+                                      uint32_t cap, uint32_t *total, uint32_t *bad) {
+    ChangesArgs A = {};
+    A.n = b->n_docs; A.docs = b->docs; A.res = r->docs; A.n_docs = b->n_docs; A.S = b->a_stride;
+    A.changes = b->changes; A.hist = r->hist; A.all_deps = r->all_deps; A.lim_c = b->n_changes;
+    A.entry_off = entry_off; A.entry_actor = entry_actor; A.entry_seq = entry_seq; A.n_entries = n_entries; A.flags = flags;
+    A.out_closure = out_closure; A.out_range = out_range; A.out_log = out_log; A.cap = cap; A.total = total; A.bad = bad;
+    return A;
+}
+
+int hm_missing_changes_device(hm_engine *e, const hm_batch *b, const hm_results *r, const uint32_t *entry_off,
+                              const uint16_t *entry_actor, const uint32_t *entry_seq, uint32_t n_entries, uint32_t flags,
+                              uint32_t *out_closure, uint32_t *out_range, uint32_t *out_log_index, uint32_t cap,
+                              uint32_t *out_total, uint32_t *out_bad, void *stream) {
+    try {
+        if (!e || !r) return HM_ERR_INVALID;
+        int st = check_waiting_batch(e, b);
+        if (st) return st;
+        if (!b->n_docs) return HM_OK;
+        if (flags & ~(HM_MC_RAW | HM_MC_ONLY_LISTED)) return fail(e, HM_ERR_INVALID, "unknown HM_MC_* flag");
+        if (!entry_off || !out_range || !out_total || !out_bad || (cap && !out_log_index) || (n_entries && (!entry_actor || !entry_seq)))
+            return fail(e, HM_ERR_INVALID, "hm_missing_changes: entry table or output missing");
+        if (!r->docs || (b->n_changes && (!r->hist || !r->all_deps)))
+            return fail(e, HM_ERR_INVALID, "hm_missing_changes needs the results' docs, hist and all_deps tables");
+        HIPCHK(e, hipSetDevice(e->device));
+        const ChangesArgs A = changes_batch_args(b, r, entry_off, entry_actor, entry_seq, n_entries, flags, out_closure, out_range,
+                                                 out_log_index, cap, out_total, out_bad);
+        hipError_t hr = hm_launch_missing_changes(A, stream ? (hipStream_t)stream : e->stream);
+        return hr == hipSuccess ? HM_OK : hip_fail(e, hr, "changes_batch_kernel launch");
+    } catch (...) {
+        return fail(e, HM_ERR_DEVICE, "exception in hm_missing_changes_device");
+    }
+}
+
+int hm_missing_changes_host(hm_engine *e, const hm_batch *hb, const hm_results *hr, const uint32_t *entry_off,
+                            const uint16_t *entry_actor, const uint32_t *entry_seq, uint32_t flags, uint32_t *out_closure,
+                            uint32_t *out_range, uint32_t *out_log_index, uint32_t cap, uint32_t *out_total) {
+    try {
+        if (!e || !hr || !out_total) return HM_ERR_INVALID;
+        int st = check_waiting_batch(e, hb);
+        if (st) return st;
+        *out_total = 0;
+        if (!hb->n_docs) return HM_OK;
+        if (flags & ~(HM_MC_RAW | HM_MC_ONLY_LISTED)) return fail(e, HM_ERR_INVALID, "unknown HM_MC_* flag");
+        if (!entry_off || !out_range || (cap && !out_log_index))
+            return fail(e, HM_ERR_INVALID, "hm_missing_changes: entry table or output missing");
+        if (!hr->docs || (hb->n_changes && (!hr->hist || !hr->all_deps)))
+            return fail(e, HM_ERR_INVALID, "hm_missing_changes needs the results' docs, hist and all_deps tables");
+        const size_t S = hb->a_stride, n = hb->n_docs;
+        if (entry_off[0]) return fail(e, HM_ERR_INVALID, "entry_off must start at 0");
+        for (size_t i = 0; i < n; i++)
+            if (entry_off[i + 1] < entry_off[i]) return fail(e, HM_ERR_INVALID, "entry_off must not decrease");
+        const size_t ne = entry_off[n];
+        if (ne && (!entry_actor || !entry_seq)) return fail(e, HM_ERR_INVALID, "hm_missing_changes: entry table or output missing");
+        HIPCHK(e, hipSetDevice(e->device));
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        // inputs 0..7, then counters (total, bad), ranges, closure rows, log indices
+        const size_t sz[12] = {n * sizeof(hm_doc_row), hb->n_changes * sizeof(hm_change_row), n * sizeof(hm_doc_result),
+                               (size_t)hb->n_changes * 4, (size_t)hb->n_changes * S * 4, (n + 1) * 4, ne * 2, ne * 4,
+                               8, n * 8, out_closure ? n * S * 4 : 0, (size_t)cap * 4};
+        const void *src[8] = {hb->docs, hb->changes, hr->docs, hr->hist, hr->all_deps, entry_off, entry_actor, entry_seq};
+        size_t off[12], total = 0;
+        for (int i = 0; i < 12; i++) { off[i] = total; total += al(sz[i] ? sz[i] : 1); }
+        char *base = nullptr;
+        if (hipMalloc((void **)&base, total) != hipSuccess) return fail(e, HM_ERR_NOMEM, "hipMalloc missing-changes staging");
+        hipStream_t s = e->stream;
+        hm_batch b = *hb;
+        b.docs = (const hm_doc_row *)(base + off[0]); b.changes = (const hm_change_row *)(base + off[1]);
+        hm_results d = {};
+        d.docs = (hm_doc_result *)(base + off[2]); d.hist = (int32_t *)(base + off[3]); d.all_deps = (uint32_t *)(base + off[4]);
+        uint32_t cnt[2] = {0, 0};
+        hipError_t r = hipMemsetAsync(base + off[8], 0, 8, s);
+        for (int i = 0; i < 8 && r == hipSuccess; i++)
+            if (sz[i]) r = hipMemcpyAsync(base + off[i], src[i], sz[i], hipMemcpyHostToDevice, s);
+        if (r == hipSuccess) {
+            const ChangesArgs A = changes_batch_args(&b, &d, (const uint32_t *)(base + off[5]), (const uint16_t *)(base + off[6]),
+                                                     (const uint32_t *)(base + off[7]), (uint32_t)ne, flags,
+                                                     out_closure ? (uint32_t *)(base + off[10]) : nullptr, (uint32_t *)(base + off[9]),
+                                                     (uint32_t *)(base + off[11]), cap, (uint32_t *)(base + off[8]),
+                                                     (uint32_t *)(base + off[8] + 4));
+            r = hm_launch_missing_changes(A, s);
+        }
+        if (r == hipSuccess) r = hipMemcpyAsync(cnt, base + off[8], 8, hipMemcpyDeviceToHost, s);
+        if (r == hipSuccess) r = hipMemcpyAsync(out_range, base + off[9], sz[9], hipMemcpyDeviceToHost, s);
+        if (r == hipSuccess && out_closure) r = hipMemcpyAsync(out_closure, base + off[10], sz[10], hipMemcpyDeviceToHost, s);
+        if (r == hipSuccess) r = hipStreamSynchronize(s);
+        if (r == hipSuccess && !cnt[1] && cnt[0] && cnt[0] <= cap)
+            r = hipMemcpy(out_log_index, base + off[11], (size_t)cnt[0] * 4, hipMemcpyDeviceToHost);
+        (void)hipFree(base);
+        if (r != hipSuccess) return hip_fail(e, r, "hm_missing_changes_host");
+        if (cnt[1] & HM_MC_BAD_RANK) return fail(e, HM_ERR_INVALID, "entry actor rank outside a_stride");
+        if (cnt[1] & HM_MC_BAD_REPEAT) return fail(e, HM_ERR_INVALID, "actor rank repeated within a request");
+        if (cnt[1]) return fail(e, HM_ERR_INVALID, "bad entry_off");
+        *out_total = cnt[0];
+        if (cnt[0] > cap) return fail(e, HM_ERR_NOMEM, "cap below the rows of the missing changes");
+        return HM_OK;
+    } catch (...) {
+        return fail(e, HM_ERR_DEVICE, "exception in hm_missing_changes_host");
     }
 }
 

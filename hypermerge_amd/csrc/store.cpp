@@ -40,6 +40,7 @@
 #include "engine_internal.h"
 #include "store_kernels.h"
 #include "waiting_kernels.h"
+#include "changes_kernels.h"
 
 namespace {
 
@@ -1086,6 +1087,64 @@ int hm_store_read_queue(hm_store *s, uint32_t n, const uint32_t *doc_handles, co
         return waiting_impl(s, n, doc_handles, nullptr, nullptr, nullptr, out_off, out_log_index);
     } catch (...) {
         return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_read_queue");
+    }
+}
+
+int hm_store_missing_changes(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *entry_off,
+                             const uint16_t *entry_actor, const uint32_t *entry_seq, uint32_t flags, uint32_t *out_closure,
+                             uint32_t *out_range, uint32_t *out_log_index, uint32_t cap, uint32_t *out_total) {
+    if (!s || !out_total || (n && (!doc_handles || !entry_off || !out_range)) || (cap && !out_log_index)) return HM_ERR_INVALID;
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        *out_total = 0;
+        if (!n) return HM_OK;
+        if (flags & ~(HM_MC_RAW | HM_MC_ONLY_LISTED)) return hm_engine_fail(s->e, HM_ERR_INVALID, "unknown HM_MC_* flag");
+        if (entry_off[0]) return hm_engine_fail(s->e, HM_ERR_INVALID, "entry_off must start at 0");
+        for (uint32_t i = 0; i < n; i++)
+            if (entry_off[i + 1] < entry_off[i]) return hm_engine_fail(s->e, HM_ERR_INVALID, "entry_off must not decrease");
+        const uint32_t ne = entry_off[n];
+        if (ne && (!entry_actor || !entry_seq)) return HM_ERR_INVALID;
+        const uint32_t S = s->S;
+        hipStream_t st = hm_engine_stream(s->e);
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t o_cnt = 0, o_h = 256, o_off = o_h + al(4 * (size_t)n), o_ea = o_off + al(4 * ((size_t)n + 1)),
+                     o_es = o_ea + al(2 * (size_t)ne + 2), o_rng = o_es + al(4 * (size_t)ne + 4), o_cl = o_rng + al(8 * (size_t)n),
+                     o_log = o_cl + (out_closure ? al(4 * (size_t)n * S) : 0), total = o_log + al(4 * (size_t)cap + 4);
+        int rc = ensure_stage(s, total);
+        if (rc) return rc;
+        uint8_t *sp = s->stage.p;
+        SCHK(s, hipMemsetAsync(sp + o_cnt, 0, 8, st));        // (total, bad)
+        SCHK(s, hipMemcpyAsync(sp + o_h, doc_handles, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+        SCHK(s, hipMemcpyAsync(sp + o_off, entry_off, 4 * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+        if (ne) {
+            SCHK(s, hipMemcpyAsync(sp + o_ea, entry_actor, 2 * (size_t)ne, hipMemcpyHostToDevice, st));
+            SCHK(s, hipMemcpyAsync(sp + o_es, entry_seq, 4 * (size_t)ne, hipMemcpyHostToDevice, st));
+        }
+        ChangesArgs A = {};
+        A.n = n; A.handles = (const uint32_t *)(sp + o_h); A.dm = s->dm; A.n_handles = s->n_handles; A.S = S;
+        A.changes = s->changes; A.hist = s->hist; A.all_deps = s->all_deps; A.lim_c = s->cap_c;
+        A.entry_off = (const uint32_t *)(sp + o_off); A.entry_actor = (const uint16_t *)(sp + o_ea);
+        A.entry_seq = (const uint32_t *)(sp + o_es); A.n_entries = ne; A.flags = flags;
+        A.out_closure = out_closure ? (uint32_t *)(sp + o_cl) : nullptr;
+        A.out_range = (uint32_t *)(sp + o_rng); A.out_log = (uint32_t *)(sp + o_log); A.cap = cap;
+        A.total = (uint32_t *)(sp + o_cnt); A.bad = (uint32_t *)(sp + o_cnt + 4);
+        SCHK(s, hm_launch_missing_changes(A, st));
+        SCHK(s, hipMemcpyAsync(&s->h_cnt[8], sp + o_cnt, 8, hipMemcpyDeviceToHost, st));
+        SCHK(s, hipStreamSynchronize(st));
+        const uint32_t tot = s->h_cnt[8], bad = s->h_cnt[9];
+        if (bad & HM_MC_BAD_HANDLE) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad handle");
+        if (bad & HM_MC_BAD_RANK) return hm_engine_fail(s->e, HM_ERR_INVALID, "entry actor rank outside the store's a_stride");
+        if (bad & HM_MC_BAD_REPEAT) return hm_engine_fail(s->e, HM_ERR_INVALID, "actor rank repeated within a request");
+        if (bad) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad entry_off");
+        *out_total = tot;
+        SCHK(s, hipMemcpyAsync(out_range, sp + o_rng, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+        if (out_closure) SCHK(s, hipMemcpyAsync(out_closure, sp + o_cl, 4 * (size_t)n * S, hipMemcpyDeviceToHost, st));
+        if (tot && tot <= cap) SCHK(s, hipMemcpyAsync(out_log_index, sp + o_log, 4 * (size_t)tot, hipMemcpyDeviceToHost, st));
+        SCHK(s, hipStreamSynchronize(st));
+        if (tot > cap) return hm_engine_fail(s->e, HM_ERR_NOMEM, "cap below the rows of the missing changes");
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_missing_changes");
     }
 }
 

@@ -130,6 +130,31 @@ class DocSet:
         s, _ = _text(self._L, t)
         return json.loads(s)
 
+    def missing_changes(self, docs: Sequence[int], clocks: Sequence[Dict[str, float]], flags: int = 0) -> List[List[int]]:
+        """Backend.getMissingChanges of many documents: clocks[i] is the peer's {actorId: seq} for
+        document docs[i], read in its insertion order.  Per request the log indices, in history
+        order, of the applied changes that peer lacks (hm_docset_missing_changes)."""
+        ids = np.ascontiguousarray(docs, np.uint32)
+        assert len(clocks) == len(ids)
+        eoff = np.zeros(len(ids) + 1, np.uint32)
+        names: List[bytes] = []
+        seqs: List[float] = []
+        for i, clock in enumerate(clocks):
+            for a, q in clock.items():
+                names.append(a.encode("utf-8", "surrogatepass"))
+                seqs.append(float(q))
+            eoff[i + 1] = len(names)
+        aoff = np.zeros(len(names) + 1, np.uint32)
+        np.cumsum([len(x) for x in names], out=aoff[1:])
+        data = np.frombuffer(b"".join(names) + b"\0", np.uint8)
+        sq = np.array(seqs + [0.0], np.float64)
+        t = ctypes.c_void_p()
+        self.engine._check(self._L.hm_docset_missing_changes(self._h, len(ids), ids.ctypes.data, eoff.ctypes.data,
+                                                             data.ctypes.data, aoff.ctypes.data, sq.ctypes.data, flags,
+                                                             ctypes.byref(t)), "hm_docset_missing_changes")
+        s, _ = _text(self._L, t)
+        return json.loads(s)
+
     def handles(self, a_stride: int) -> Dict[str, int]:
         """hm_docset_handles: handles opened in the a_stride store and released ones awaiting reuse."""
         o, f = ctypes.c_uint32(), ctypes.c_uint32()

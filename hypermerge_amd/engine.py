@@ -37,7 +37,8 @@ EXPORTS = ("hm_abi_version", "hm_status_message", "hm_engine_create", "hm_engine
            "hm_docset_doc_info", "hm_docset_history_prefix", "hm_docset_clock_update", "hm_docset_view",
            "hm_docset_stats", "hm_docset_routing", "hm_docset_handles", "hm_sync_ranges_host", "hm_batch_submit_device", "hm_batch_wait_device",
            "hm_batch_undo", "hm_store_blocked", "hm_store_waiting", "hm_store_read_queue", "hm_missing_deps_device",
-           "hm_missing_deps_host", "hm_docset_blocked", "hm_docset_waiting")
+           "hm_missing_deps_host", "hm_docset_blocked", "hm_docset_waiting", "hm_store_missing_changes",
+           "hm_missing_changes_device", "hm_missing_changes_host", "hm_docset_missing_changes")
 
 _lib = None
 
@@ -116,6 +117,12 @@ def lib():
             "hm_missing_deps_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), vp, vp],
             "hm_missing_deps_host": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), vp],
             "hm_docset_blocked": [vp, vp, u32, vp], "hm_docset_waiting": [vp, u32, vp, vp],
+            "hm_store_missing_changes": [vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, u32, vp],
+            "hm_missing_changes_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), vp, vp, vp, u32, u32,
+                                          vp, vp, vp, u32, vp, vp, vp],
+            "hm_missing_changes_host": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), vp, vp, vp, u32,
+                                        vp, vp, vp, u32, vp],
+            "hm_docset_missing_changes": [vp, u32, vp, vp, vp, vp, vp, u32, vp],
         }
         for f, a in sig.items():
             getattr(L, f).argtypes = a
@@ -137,6 +144,33 @@ def lib():
         L.hm_text_free.restype = None
         _lib = L
     return _lib
+
+
+MC_RAW, MC_ONLY_LISTED = 1, 2   # HM_MC_*
+
+
+def pack_entries(have, n: int):
+    """have-clocks as the C-ABI's entry tables (entry_off [n + 1] u32, entry_actor u16, entry_seq u32):
+    `have` is an [n, S] array of rank-indexed rows (its non-zero columns become entries, in rank
+    order) or per request a sequence of (actor rank, seq) in the clock's key order."""
+    off = np.zeros(n + 1, np.uint32)
+    ea: list = []
+    es: list = []
+    if isinstance(have, np.ndarray) and have.ndim == 2:
+        assert have.shape[0] == n, have.shape
+        for i in range(n):
+            nz = np.flatnonzero(have[i])
+            ea.extend(int(a) for a in nz)
+            es.extend(int(have[i, a]) for a in nz)
+            off[i + 1] = len(ea)
+    else:
+        assert len(have) == n, len(have)
+        for i, ents in enumerate(have):
+            for a, q in ents:
+                ea.append(int(a))
+                es.append(min(max(int(q), 0), 0xFFFFFFFF))
+            off[i + 1] = len(ea)
+    return off, np.array(ea + [0], np.uint16), np.array(es + [0], np.uint32)
 
 
 class _Config(ctypes.Structure):
@@ -207,6 +241,39 @@ class Engine:
         self._check(self._L.hm_missing_deps_device(self._h, ctypes.byref(cbatch), ctypes.byref(cresults),
                                                    ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream) if stream else None),
                     "hm_missing_deps_device")
+
+    def missing_changes(self, batch: Batch, results: Results, have, flags: int = 0, closure: bool = False):
+        """getMissingChanges of every document of a merged batch: per document the document-local
+        log indices, in history order, of the applied changes a peer with the clock `have` lacks.
+        have: an [n_docs, a_stride] array of rank-indexed rows (0 = no entry; the entries are taken
+        in rank order), or per document a sequence of (actor rank, seq) in the clock's key order.
+        closure=True: also the [n_docs, a_stride] transitiveDeps rows.  A document whose merge threw
+        offers nothing."""
+        n, S = batch.n_docs, batch.a_stride
+        off, ea, es = pack_entries(have, n)
+        rng = np.zeros((max(n, 1), 2), np.uint32)
+        clo = np.zeros((max(n, 1), S), np.uint32)
+        cb, cr = batch.c_struct(), results.c_struct()
+        cap = len(batch.changes)                       # (no document offers more than its own rows)
+        out = np.zeros(max(cap, 1), np.uint32)
+        tot = ctypes.c_uint32()
+        self._check(self._L.hm_missing_changes_host(self._h, ctypes.byref(cb), ctypes.byref(cr), off.ctypes.data,
+                                                    ea.ctypes.data, es.ctypes.data, flags, clo.ctypes.data,
+                                                    rng.ctypes.data, out.ctypes.data, cap, ctypes.byref(tot)),
+                    "hm_missing_changes_host")
+        lists = [[int(x) for x in out[int(o):int(o) + int(c)]] for o, c in rng[:n]]
+        return (lists, clo[:n]) if closure else lists
+
+    def missing_changes_device(self, cbatch: CBatch, cresults: CResults, entry_off: int, entry_actor: int, entry_seq: int,
+                               n_entries: int, flags: int, out_closure: int, out_range: int, out_log: int, cap: int,
+                               out_total: int, out_bad: int, stream: int = 0) -> None:
+        """The same with every table, the entry arrays and the outputs in device memory (pointers;
+        out_total / out_bad are device words zeroed by the caller; enqueued, not synchronised)."""
+        p = lambda x: ctypes.c_void_p(x) if x else None
+        self._check(self._L.hm_missing_changes_device(self._h, ctypes.byref(cbatch), ctypes.byref(cresults), p(entry_off),
+                                                      p(entry_actor), p(entry_seq), n_entries, flags, p(out_closure),
+                                                      p(out_range), p(out_log), cap, p(out_total), p(out_bad), p(stream)),
+                    "hm_missing_changes_device")
 
     def small_occupancy(self, batch: Batch) -> Sequence[int]:
         """(resident one-wave workgroups per CU, CUs, op rows per lane, size class, lists, counters) of

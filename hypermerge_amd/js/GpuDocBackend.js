@@ -319,6 +319,27 @@ class Queue {
   toArray() { return this.items }
 }
 
+// which changes peers lack (Automerge getMissingChanges), many documents of one docset in one device
+// call: ids[i] with the peer's clock clocks[i] ({actorId: seq}, an Immutable / ES Map or a plain
+// object; its key order is kept, the answer depends on it when the clock is not causally closed).
+// Returns per request the log indices in history order.  flags: 1 the clock is the threshold row
+// itself (no transitive closure), 2 only actors the clock lists.  Reads the rounds already applied.
+const plainClock = (c) => (!c ? {} : typeof c.toJS === 'function' ? c.toJS() : c instanceof Map ? Object.fromEntries(c) : c)
+function missingIndices(ds, ids, clocks, flags) {
+  const eoff = new Uint32Array(ids.length + 1)
+  const names = [], seqs = []
+  clocks.forEach((clock, i) => {
+    const c = plainClock(clock)
+    for (const a of Object.keys(c)) { names.push(Buffer.from(a, 'utf8')); seqs.push(Number(c[a])) }
+    eoff[i + 1] = names.length
+  })
+  const aoff = new Uint32Array(names.length + 1)
+  names.forEach((b, k) => { aoff[k + 1] = aoff[k] + b.length })
+  return JSON.parse(addon.docsetMissingChanges(ds, Uint32Array.from(ids), eoff, Buffer.concat(names), aoff,
+    Float64Array.from(seqs), flags || 0))
+}
+const missingOf = (state, clock, flags) => missingIndices(state.ds, [state.id], [clock], flags)[0].map((i) => state.change(i))
+
 // FNV-1a 64 over the UTF-8 bytes of an id string: the shard key (and the clock exchange's
 // record key) of hypermerge_amd/exchange.py and include/hypermerge_amd.h.
 // Computed on two 32-bit halves in plain Numbers (h * prime = h * 0x1b3 + h << 40; every partial
@@ -465,6 +486,21 @@ class GpuEngine {
         const state = this.states[k].get(id)
         out.push({ id: state ? state.docId : undefined, state, missing: w[i].missing })
       })
+    })
+    return out
+  }
+
+  // the sync loop's question for many documents at once: states[i]'s changes that a peer whose
+  // clock is clocks[i] lacks, as Change objects in history order (one device call per docset).
+  // Reflects the rounds already applied: in 'async' mode await idle() first.
+  missingChanges(states, clocks, flags) {
+    const out = new Array(states.length)
+    this.docsets.forEach((ds, k) => {
+      const at = []
+      states.forEach((st, i) => { if (st.shard === k) at.push(i) })
+      if (!at.length) return
+      const idx = missingIndices(ds, at.map((i) => states[i].id), at.map((i) => clocks[i]), flags)
+      at.forEach((i, j) => { out[i] = idx[j].map((x) => states[i].change(x)) })
     })
     return out
   }
@@ -852,6 +888,19 @@ function makeBackend(engine) {
     // Backend.getMissingDeps: {actorId: seq} the queued changes need and opSet.clock lacks (of the
     // rounds already applied: in 'async' mode await engine.idle() first)
     getMissingDeps: (state) => waitingOf(state).missing,
+    // Backend.getMissingChanges(state, clock): the applied changes a peer with that clock lacks, in
+    // history order; getChanges(old, new) asks it with old's opSet.clock (Automerge throws when old
+    // is not behind new); getChangesForActor(state, actorId, afterSeq): that actor's changes past
+    // afterSeq.  All read the rounds already applied.
+    getMissingChanges: (state, clock) => missingOf(state, clock, 0),
+    getChanges: (oldState, newState) => {
+      const have = oldState.getIn(['opSet', 'clock']), now = newState.getIn(['opSet', 'clock'])
+      for (const a of Object.keys(have)) {
+        if (have[a] > (now[a] || 0)) throw new RangeError('Cannot diff two states that have diverged')
+      }
+      return missingOf(newState, have, 0)
+    },
+    getChangesForActor: (state, actorId, afterSeq) => missingOf(state, { [actorId]: afterSeq || 0 }, 3),
   }
 }
 

@@ -23,7 +23,7 @@ from .columnar import (ACTIONS, CHANGE_DT, DEP_DT, DOC_DT, DOC_RESULT_DT, OP_DT,
                        SURV_RESULT_DT, DATATYPES, DOC_HAS_COUNTERS, DOC_HAS_LISTS, DT_COUNTER, HEAD,
                        INC, INS, LINK, MAKE_LIST, MAKE_TEXT, NONE, ROOT_ID, SET, DEL, V_NULL, V_OBJ,
                        Batch, CBatch, Results, _value, content_key, js_key)
-from .engine import Engine, EngineError, lib
+from .engine import MC_ONLY_LISTED, MC_RAW, Engine, EngineError, lib, pack_entries
 
 
 class StringPool:
@@ -424,6 +424,47 @@ class DocStore:
         miss, _, _ = self.waiting([h])
         actors = self.enc[h].actors
         return {actors[a]: int(s) for a, s in enumerate(miss[0]) if s}
+
+    # -- what a peer lacks (getMissingChanges / getChanges / getChangesForActor) ----------------------
+    def missing_changes_rows(self, handles, have, flags: int = 0) -> Tuple[List[List[int]], np.ndarray]:
+        """hm_store_missing_changes over rank entries: `have` as engine.pack_entries takes it.
+        Returns (per request the log indices in history order, the [n, S] transitiveDeps rows)."""
+        hs = np.ascontiguousarray(handles, np.uint32)
+        n = len(hs)
+        off, ea, es = pack_entries(have, n)
+        rng = np.zeros((max(n, 1), 2), np.uint32)
+        clo = np.zeros((max(n, 1), self.S), np.uint32)
+        tot = ctypes.c_uint32()
+        cap = 4096
+        out = np.zeros(cap, np.uint32)
+        args = (self._h, n, _p(hs), _p(off), _p(ea), _p(es), flags, _p(clo), _p(rng))
+        st = self._L.hm_store_missing_changes(*args, _p(out), cap, ctypes.byref(tot))
+        if st == 34 and tot.value > cap:              # HM_ERR_NOMEM: tot = the rows needed
+            cap = tot.value
+            out = np.zeros(cap, np.uint32)
+            st = self._L.hm_store_missing_changes(*args, _p(out), cap, ctypes.byref(tot))
+        self._check(st, "hm_store_missing_changes")
+        return [[int(x) for x in out[int(o):int(o) + int(c)]] for o, c in rng[:n]], clo[:n]
+
+    def missing_changes(self, handles, clocks, flags: int = 0) -> List[List[int]]:
+        """Backend.getMissingChanges of many documents in one call: clocks[i] is the peer's
+        {actorId: seq} for document handles[i], read in its insertion order (the answer depends on
+        it when the clock is not causally closed); an actor the document has never seen names none
+        of its changes and is dropped.  Per request the log indices, in history order, of the
+        applied changes the peer lacks."""
+        have = []
+        for h, clock in zip(handles, clocks):
+            rank = {a: i for i, a in enumerate(self.enc[h].actors)}
+            have.append([(rank[a], q) for a, q in clock.items() if a in rank])
+        return self.missing_changes_rows(handles, have, flags)[0]
+
+    def changes_since(self, h: int, clock: Dict[str, int]) -> List[int]:
+        """getMissingChanges of one document (getChanges(old, new) with old's opSet.clock)."""
+        return self.missing_changes([h], [clock])[0]
+
+    def changes_for_actor(self, h: int, actor: str, after: int = 0) -> List[int]:
+        """Backend.getChangesForActor: the actor's applied changes with seq > after, history order."""
+        return self.missing_changes([h], [{actor: after}], MC_RAW | MC_ONLY_LISTED)[0]
 
     def set_min_clock(self, h: int, clock: Dict[str, int]) -> None:
         """minimumClock (actor id -> seq); its actors must already be in the document's actor table."""

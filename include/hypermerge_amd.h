@@ -440,6 +440,51 @@ int hm_store_read_queue(hm_store *s, uint32_t n, const uint32_t *doc_handles, co
 int hm_missing_deps_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t *out_missing, void *stream);
 int hm_missing_deps_host(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t *out_missing);
 
+/* Which of a document's changes a peer lacks, given the peer's clock (Automerge 0.12
+ * Backend.getMissingChanges(state, have); getChanges(old, new) is the same with old's opSet.clock;
+ * the reference's sync loop asks it when a peer's clock arrives, src/RepoBackend.ts:394-428).
+ *   transitiveDeps(have): deps = {}; for (actor, seq) of have IN ITS KEY ORDER, seq > 0:
+ *       deps = max-merge(deps, states[actor][seq-1].allDeps)   -- no such state: nothing merged
+ *       deps[actor] = seq                                      -- set after the merge: it can lower the entry
+ *   missing = history.filter(c => c.seq > (deps[c.actor] || 0))
+ * so the answer is in history (application) order, never holds a queued (hist -1) or duplicate
+ * (hist -2) change, and depends on the entries' order when `have` is not causally closed.
+ *
+ * Requests i = 0..n-1: document doc_handles[i] (a handle may repeat), entries entry_off[i] ..
+ * entry_off[i+1]-1 of (entry_actor rank, entry_seq) in the have-clock's key order (entry_off[0] = 0,
+ * not decreasing; a rank at most once per request).  out_closure (optional, [n*S]) = the
+ * transitiveDeps row; out_range [2n] = (offset into out_log_index, count) per request; the blocks
+ * lie in unspecified order, each block holds log indices in history order.  *out_total = rows
+ * needed; HM_ERR_NOMEM when that exceeds cap (the ranges' counts, out_closure and *out_total are still
+ * valid, out_log_index is not; out_log_index may be NULL when cap is 0).  HM_ERR_INVALID: a handle
+ * outside the store, a rank >= a_stride, a rank repeated within a request, bad entry_off.  No batch
+ * in flight.  A call's rows stay below 2^32.
+ * flags: HM_MC_RAW: the entries are the threshold row itself (no fold; ranks not listed read 0);
+ * HM_MC_ONLY_LISTED: changes of actors without an entry are left out.  getChangesForActor(a, n) is
+ * HM_MC_RAW | HM_MC_ONLY_LISTED with the one entry (a, n). */
+#define HM_MC_RAW 1u
+#define HM_MC_ONLY_LISTED 2u
+int hm_store_missing_changes(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *entry_off,
+                             const uint16_t *entry_actor, const uint32_t *entry_seq, uint32_t flags,
+                             uint32_t *out_closure, uint32_t *out_range, uint32_t *out_log_index,
+                             uint32_t cap, uint32_t *out_total);
+/* The same for the documents of a merged cold batch: request i = document i of b (n = b->n_docs), read
+ * from b's docs / changes and r's docs / hist / all_deps; a document whose status is not HM_OK offers
+ * nothing.  n_entries = rows of entry_actor / entry_seq (= entry_off[n_docs]).
+ * _device: every table, the entry arrays and the outputs are device memory, enqueued on `stream`
+ * (NULL = the engine's) without synchronising; *out_total and *out_bad are device words the caller
+ * zeroes first (*out_bad != 0 afterwards: 2 a rank >= a_stride, 4 a repeated rank, 8 bad entry_off;
+ * such a request has the range (0, 0)); blocks are written only while offset + count <= cap.
+ * _host: host tables in, host rows out (staged, synchronous), errors as hm_store_missing_changes. */
+int hm_missing_changes_device(hm_engine *e, const hm_batch *b, const hm_results *r, const uint32_t *entry_off,
+                              const uint16_t *entry_actor, const uint32_t *entry_seq, uint32_t n_entries, uint32_t flags,
+                              uint32_t *out_closure, uint32_t *out_range, uint32_t *out_log_index, uint32_t cap,
+                              uint32_t *out_total, uint32_t *out_bad, void *stream);
+int hm_missing_changes_host(hm_engine *e, const hm_batch *b, const hm_results *r, const uint32_t *entry_off,
+                            const uint16_t *entry_actor, const uint32_t *entry_seq, uint32_t flags,
+                            uint32_t *out_closure, uint32_t *out_range, uint32_t *out_log_index, uint32_t cap,
+                            uint32_t *out_total);
+
 /* minimumClock row of a document (rank-indexed, 0 = absent); used for the
  * min_cmp of the next merges (Clock.cmp(DocBackend.clock, minimumClock)). */
 int hm_doc_set_min_clock(hm_store *s, uint32_t doc, const uint32_t *clock);
@@ -614,6 +659,16 @@ int hm_docset_blocked(hm_docset *ds, uint32_t *out_docs, uint32_t cap, uint32_t 
  * "missing":{"<actorId>":seq}} (Automerge getMissingDeps; hm_store_waiting + hm_store_read_queue
  * per class, ranks mapped back to actor ids) */
 int hm_docset_waiting(hm_docset *ds, uint32_t n, const uint32_t *docs, hm_text **out);
+/* the changes a peer lacks (hm_store_missing_changes per stride class): request i = document docs[i]
+ * (may repeat) with the have-clock entries entry_off[i] .. entry_off[i+1]-1 in the clock's key order;
+ * entry k = the actor id string actor_ids[actor_off[k] .. actor_off[k+1]) with seqs[k] (a JS number:
+ * NaN and negatives read 0, clamped to 2^32-1, fractions truncated).  An id the document has never
+ * seen is dropped (it names none of its changes); an id listed twice in a request is
+ * HM_ERR_INVALID.  Result text = JSON [[log indices in history order], ...], one array per request
+ * (a document not placed yet: []).  flags: HM_MC_*. */
+int hm_docset_missing_changes(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off,
+                              const char *actor_ids, const uint32_t *actor_off, const double *seqs,
+                              uint32_t flags, hm_text **out);
 /* the merged document: {uuid: {"type", "keys": [[key, entry]], "elems": [[elemId, entry]]}} */
 int hm_docset_view(hm_docset *ds, uint32_t doc, hm_text **out);
 /* counters: calls, documents, class moves, net patches from the hit registers, net patches from every

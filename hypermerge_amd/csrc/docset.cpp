@@ -1132,7 +1132,9 @@ bool same_register(const DocSt &d, uint32_t g, const hm_reg_result &r, const hm_
 }
 
 // the document as the patch base holds it: {uuid: {type, keys: [[key, entry]], elems: [[elemId, entry]]}}
-void render_view(std::string &o, const DocSt &d, const hm_reg_result *rows, const hm_surv_result *surv, uint32_t n_regs) {
+// (created: per object, 1 = it exists in the rendered state; NULL = every object the document knows)
+void render_view(std::string &o, const DocSt &d, const hm_reg_result *rows, const hm_surv_result *surv, uint32_t n_regs,
+                 const uint8_t *created = nullptr) {
     std::vector<std::string> keys(d.obj_type.size()), elems(d.obj_type.size());
     std::vector<std::vector<std::pair<int32_t, uint32_t>>> order(d.obj_type.size());
     std::string tmp;
@@ -1150,9 +1152,11 @@ void render_view(std::string &o, const DocSt &d, const hm_reg_result *rows, cons
         k += "}]";
     }
     o += '{';
+    const size_t start = o.size();
     for (uint32_t ob = 0; ob < d.obj_type.size(); ob++) {
         if (d.obj_type[ob] == NO_TYPE && keys[ob].empty() && order[ob].empty()) continue;
-        if (o.size() > 1) o += ',';
+        if (created && !created[ob]) continue;
+        if (o.size() > start) o += ',';
         jstr(o, d.objs.ptr(ob), d.objs.len(ob));
         const uint8_t t = d.obj_type[ob] == NO_TYPE ? HM_MAKE_MAP : d.obj_type[ob];
         o += ":{\"type\":\""; o += TYPE_NAME[t & 3]; o += "\",\"keys\":[";
@@ -2023,6 +2027,125 @@ int hm_docset_missing_changes(hm_docset *ds, uint32_t n, const uint32_t *docs, c
         return HM_OK;
     } catch (...) {
         return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_missing_changes");
+    }
+}
+
+int hm_docset_materialize(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, const uint32_t *entry_off,
+                          const char *actor_ids, const uint32_t *actor_off, const double *seqs, hm_text **out) {
+    if (!ds || !out || (n && !docs)) return HM_ERR_INVALID;
+    *out = nullptr;
+    if ((hist_len != nullptr) == (entry_off != nullptr))
+        return hm_engine_fail(ds->e, HM_ERR_INVALID, "exactly one of hist_len and the clock entries");
+    Busy b(ds);
+    if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
+    try {
+        const uint32_t nd = ds->n_docs.load();
+        for (uint32_t i = 0; i < n; i++) {
+            if (docs[i] >= nd) return hm_engine_fail(ds->e, HM_ERR_INVALID, "bad docset document");
+            if (entry_off && entry_off[i + 1] < entry_off[i]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "entry_off must not decrease");
+        }
+        if (entry_off && n && entry_off[n] - entry_off[0] && (!actor_ids || !actor_off || !seqs)) return HM_ERR_INVALID;
+        std::vector<std::string> js(n);
+        for (uint32_t i = 0; i < n; i++) {                       // (a document not placed yet: Backend.init())
+            DocSt &d = ds->doc(docs[i]);
+            if (d.cls != NO_CLASS) continue;
+            if (!d.ready) d.setup();
+            js[i] = "{\"doc\":" + std::to_string(docs[i]) + ",\"clock\":{},\"deps\":{},\"history\":0,\"view\":";
+            render_view(js[i], d, nullptr, nullptr, 0);
+            js[i] += '}';
+        }
+        for (uint32_t c = 0; c < N_CLASS; c++) {
+            const uint32_t S = STRIDES[c];
+            std::vector<uint32_t> idx, hs, sel;
+            for (uint32_t i = 0; i < n; i++) {
+                const DocSt &d = ds->doc(docs[i]);
+                if (d.cls != c) continue;
+                idx.push_back(i); hs.push_back(d.handle);
+                if (hist_len) { sel.push_back(hist_len[i]); continue; }
+                sel.resize(sel.size() + S, 0u);
+                uint32_t *row = sel.data() + sel.size() - S;
+                for (uint32_t k = entry_off[i]; k < entry_off[i + 1]; k++) {
+                    if (actor_off[k + 1] < actor_off[k]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease");
+                    const uint32_t a = d.actors.find(actor_ids + actor_off[k], actor_off[k + 1] - actor_off[k], 0);
+                    if (a == HM_NONE || a >= d.rank_of.size() || d.rank_of[a] >= S) continue;   // (an actor the document has never seen)
+                    const double v = seqs[k];
+                    row[d.rank_of[a]] = !(v > 0) ? 0u : v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v;
+                }
+            }
+            if (idx.empty()) continue;
+            const uint32_t k = (uint32_t)idx.size();
+            hm_store *st = ds->stores[c];
+            const uint32_t *hl = hist_len ? sel.data() : nullptr, *rows = hist_len ? nullptr : sel.data();
+            // the tables are sized once the count pass has run (one count pass per class)
+            struct Tables {
+                uint32_t k, S;
+                std::vector<hm_doc_row> rows_d;
+                std::vector<hm_op_row> ops;
+                std::vector<uint32_t> op_log, clock, heads;
+                std::vector<hm_doc_result> res;
+                std::vector<hm_reg_result> regs;
+                std::vector<hm_surv_result> surv;
+                hm_past_out po;
+            } T;
+            T.k = k; T.S = S;
+            const hm_past_alloc alloc = [](void *ctx, const uint64_t *tot) -> const hm_past_out * {
+                Tables &t = *(Tables *)ctx;
+                if (tot[2] > 0xFFFFFFFFull || tot[3] > 0xFFFFFFFFull) return nullptr;
+                try {
+                    t.rows_d.resize(t.k); t.res.resize(t.k);
+                    t.clock.resize((size_t)t.k * t.S); t.heads.resize((size_t)t.k * t.S);
+                    t.ops.resize(tot[2] + 1); t.op_log.resize(tot[2] + 1); t.surv.resize(tot[2] + 1); t.regs.resize(tot[3] + 1);
+                } catch (...) { return nullptr; }
+                t.po = hm_past_out{};
+                t.po.cap_ops = (uint32_t)tot[2]; t.po.cap_regs = (uint32_t)tot[3];
+                t.po.docs = t.rows_d.data(); t.po.ops = t.ops.data(); t.po.op_log = t.op_log.data();
+                t.po.res.docs = t.res.data(); t.po.res.clock = t.clock.data(); t.po.res.heads = t.heads.data();
+                t.po.res.regs = t.regs.data(); t.po.res.surv = t.surv.data();
+                return &t.po;
+            };
+            int rc = hm_store_materialize_sized(st, k, hs.data(), hl, rows, alloc, &T, nullptr);
+            if (rc) return rc;
+            std::vector<hm_doc_row> &rows_d = T.rows_d;
+            std::vector<hm_op_row> &ops = T.ops;
+            std::vector<uint32_t> &op_log = T.op_log, &clock = T.clock, &heads = T.heads;
+            std::vector<hm_doc_result> &res = T.res;
+            std::vector<hm_reg_result> &regs = T.regs;
+            std::vector<hm_surv_result> &surv = T.surv;
+            std::vector<uint8_t> created;
+            for (uint32_t j = 0; j < k; j++) {
+                DocSt &d = ds->doc(docs[idx[j]]);
+                if (!d.ready) d.setup();
+                const hm_doc_row &r = rows_d[j];
+                std::string &o = js[idx[j]];
+                o = "{\"doc\":" + std::to_string(docs[idx[j]]) + ",\"clock\":";
+                jclock(o, d, clock.data() + (size_t)j * S, std::min<size_t>(d.actors.size(), S));
+                o += ",\"deps\":";
+                jclock(o, d, heads.data() + (size_t)j * S, std::min<size_t>(d.actors.size(), S));
+                o += ",\"history\":" + std::to_string(res[j].hist_len) + ",\"view\":";
+                if (res[j].status != HM_OK) { o += "null}"; continue; }
+                // the objects the gathered ops create, and the survivors' ops as the document's own log indices
+                created.assign(std::max<size_t>(d.obj_type.size(), 1), 0);
+                created[0] = 1;
+                for (uint32_t x = r.op_off; x < r.op_off + r.n_ops; x++)
+                    if (ops[x].action <= HM_MAKE_TEXT && ops[x].obj < created.size()) created[ops[x].obj] = 1;
+                const uint32_t ns = std::min(res[j].n_surv, r.n_ops);
+                for (uint32_t x = 0; x < ns; x++) {
+                    hm_surv_result &sv = surv[r.op_off + x];
+                    sv.op = sv.op < r.n_ops ? op_log[r.op_off + sv.op] : HM_NONE;
+                }
+                render_view(o, d, regs.data() + r.reg_off, surv.data() + r.op_off, std::min<uint32_t>(r.n_regs, (uint32_t)d.regs.size()),
+                            created.data());
+                o += '}';
+            }
+        }
+        std::unique_ptr<hm_text> t(new hm_text());
+        t->s = "[";
+        for (uint32_t i = 0; i < n; i++) { if (i) t->s += ','; t->s += js[i]; }
+        t->s += ']';
+        *out = t.release();
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_materialize");
     }
 }
 

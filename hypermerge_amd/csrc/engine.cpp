@@ -17,6 +17,7 @@
 #include "engine_internal.h"
 #include "waiting_kernels.h"
 #include "changes_kernels.h"
+#include "past_kernels.h"
 
 struct hm_engine {
     int device = 0;
@@ -494,6 +495,48 @@ int hm_missing_changes_device(hm_engine *e, const hm_batch *b, const hm_results 
         return hr == hipSuccess ? HM_OK : hip_fail(e, hr, "changes_batch_kernel launch");
     } catch (...) {
         return fail(e, HM_ERR_DEVICE, "exception in hm_missing_changes_device");
+    }
+}
+
+size_t hm_materialize_work_bytes(uint32_t n) {
+    // [counts 4n][offsets 4n][objects and flags 2n] u32, then the scan's per-chunk words
+    return ((((size_t)n * 40) + 255) & ~(size_t)255) + (size_t)hm_past_scan_chunks(n) * HM_PAST_PART * 8;
+}
+
+int hm_materialize_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                          const uint32_t *hist_len, const uint32_t *clock_rows, const hm_past_out *out,
+                          hm_past_summary *out_summary, void *work, void *stream) {
+    try {
+        if (!e || !r || !out || !out_summary) return HM_ERR_INVALID;
+        int st = check_batch(e, b);
+        if (st) return st;
+        if ((hist_len != nullptr) == (clock_rows != nullptr))
+            return fail(e, HM_ERR_INVALID, "hm_materialize: exactly one of hist_len and clock_rows");
+        if (n && (!work || !out->docs)) return fail(e, HM_ERR_INVALID, "hm_materialize: work or out->docs missing");
+        if (((uintptr_t)work | (uintptr_t)out->ops) & 15u)     // (the counts and the op rows move as 16-byte words)
+            return fail(e, HM_ERR_INVALID, "hm_materialize: work and out->ops must be 16-byte aligned");
+        if ((out->cap_changes && (!out->changes || !out->change_log)) || (out->cap_deps && !out->deps) ||
+            (out->cap_ops && (!out->ops || !out->op_log)))
+            return fail(e, HM_ERR_INVALID, "hm_materialize: an output table with a capacity is missing");
+        if (!r->docs || (b->n_changes && !r->hist)) return fail(e, HM_ERR_INVALID, "hm_materialize needs the results' docs and hist tables");
+        HIPCHK(e, hipSetDevice(e->device));
+        hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+        PastArgs A = {};
+        A.n = n; A.handles = doc_index; A.docs = b->docs; A.res = r->docs; A.n_docs = b->n_docs; A.S = b->a_stride;
+        A.changes = b->changes; A.hist = r->hist; A.deps = b->deps; A.ops = b->ops;
+        A.lim_c = b->n_changes; A.lim_d = b->n_deps; A.lim_o = b->n_ops;
+        A.hist_len = hist_len; A.clock_rows = clock_rows;
+        A.cnt = (uint32_t *)work; A.off = A.cnt + 4 * (size_t)n; A.aux = A.off + 4 * (size_t)n;
+        A.part = (unsigned long long *)((char *)work + ((((size_t)n * 40) + 255) & ~(size_t)255));
+        A.sum = out_summary;
+        A.cap[0] = out->cap_changes; A.cap[1] = out->cap_deps; A.cap[2] = out->cap_ops; A.cap[3] = out->cap_regs;
+        A.out_docs = out->docs; A.out_changes = out->changes; A.out_deps = out->deps; A.out_ops = out->ops;
+        A.out_change_log = out->change_log; A.out_op_log = out->op_log;
+        hipError_t hr = hm_launch_past_count(A, s);
+        if (hr == hipSuccess) hr = hm_launch_past_fill(A, s);
+        return hr == hipSuccess ? HM_OK : hip_fail(e, hr, "past kernels launch");
+    } catch (...) {
+        return fail(e, HM_ERR_DEVICE, "exception in hm_materialize_device");
     }
 }
 

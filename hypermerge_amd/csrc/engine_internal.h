@@ -14,3 +14,10 @@ int hm_engine_launch_merge(hm_engine *e, const hm_batch *b, const hm_results *o,
 hipStream_t hm_engine_stream(hm_engine *e);
 int hm_engine_device(hm_engine *e);
 int hm_engine_fail(hm_engine *e, int status, const char *msg);
+
+// hm_store_materialize for a caller that allocates by the totals: after the count pass alloc(ctx,
+// totals[4]) returns the outputs (NULL: HM_ERR_NOMEM), then fill and merge run; one count pass
+typedef const hm_past_out *(*hm_past_alloc)(void *ctx, const uint64_t *totals);
+struct hm_store;
+int hm_store_materialize_sized(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *hist_len,
+                               const uint32_t *clock_rows, hm_past_alloc alloc, void *ctx, uint64_t *out_totals);

@@ -1,0 +1,71 @@
+// past_kernels.h — launch interface of past_kernels.hip (store.cpp, engine.cpp)
+#pragma once
+#include <hip/hip_runtime.h>
+#include "../../include/hypermerge_amd.h"
+#include "store_kernels.h"
+
+// history positions per bitmap tile of the fill pass (a longer selection takes several tiles, each
+// a pass over the document's hist rows); the wave strides the rows 64 at a time
+#define HM_PAST_TILE 512u
+// the scan's chunks: requests per lane of a 1024-lane workgroup, and the u64 words a chunk leaves in
+// `part` (4 sums, 5 maxima, the flags)
+#define HM_PAST_SCAN_ITEMS 4u
+#define HM_PAST_PART 10u
+inline uint32_t hm_past_scan_chunks(uint32_t n) { return (uint32_t)(((unsigned long long)n + 4095ull) / 4096ull); }
+
+// A document as it was: request i = (handles[i], selector), a handle may repeat.  The selector is
+// hist_len[i] (the applied changes at history positions below it) or the clock row
+// clock_rows[i * S ..] (the applied changes with seq <= clock[actor]); exactly one is not NULL.
+// Queued (hist -1) and duplicate (hist -2) changes are never selected.
+//
+//   count  one wave per request: cnt[4i ..] = changes, deps, ops of the selection and the
+//          document's registers; aux[2i ..] = its objects and flags
+//   scan   off[4i ..] = exclusive prefix sums of cnt in request order (the requests' output blocks are
+//          reserved by this scan over the counts, no atomics: the gathered tables lie in request
+//          order, as every encoder here lays a batch out), sum = totals + launch hints; two launches
+//          over chunks of 4096 requests, part = hm_past_scan_chunks(n) * HM_PAST_PART words between them
+//   fill   one wave per request, nothing written when a total exceeds its cap: the hm_doc_row, the
+//          change rows in history order with dep_off / op_first rewritten to the gathered tables,
+//          the dep and op rows, out_change_log[j] = document-local log index of gathered change j,
+//          out_op_log[k] = document-local log op index of gathered op k
+//
+// The source is a resident store (dm, handles checked against n_handles) or a merged cold batch
+// (docs / res; handles = document indices, NULL = request i is document i; a document whose merge
+// threw offers nothing).  A handle outside the source sets HM_PAST_BAD_HANDLE in sum->bad and gets
+// empty ranges; a change row whose dep / op range leaves its document's segment sets
+// HM_PAST_BAD_ROWS and is gathered without those rows.  lim_*: rows of the source tables; no row
+// past them is read.
+#define HM_PAST_BAD_HANDLE 1u
+#define HM_PAST_BAD_ROWS 2u
+
+struct PastArgs {
+    uint32_t n;
+    const uint32_t *handles;
+    const DevDoc *dm;                          // resident store ...
+    uint32_t n_handles;
+    const hm_doc_row *docs;                    // ... or a merged cold batch
+    const hm_doc_result *res;
+    uint32_t n_docs;
+    uint32_t S;
+    const hm_change_row *changes;
+    const int32_t *hist;
+    const hm_dep_row *deps;
+    const hm_op_row *ops;
+    unsigned long long lim_c, lim_d, lim_o;
+    const uint32_t *hist_len;                  // [n] or NULL
+    const uint32_t *clock_rows;                // [n * S] or NULL
+    uint32_t *cnt, *aux, *off;                 // [4n], [2n], [4n]
+    unsigned long long *part;                  // [hm_past_scan_chunks(n) * HM_PAST_PART]
+    hm_past_summary *sum;
+    // fill pass
+    uint32_t cap[4];                           // rows of out_changes (and the logs), out_deps, out_ops; regs
+    hm_doc_row *out_docs;
+    hm_change_row *out_changes;
+    hm_dep_row *out_deps;
+    hm_op_row *out_ops;
+    uint32_t *out_change_log, *out_op_log;
+    uint32_t log_only;                         // 1: only out_docs and out_change_log are written (cap[0] alone counts)
+};
+// count + scan (sum need not be zeroed; n == 0: sum is zeroed and nothing else is read or written)
+hipError_t hm_launch_past_count(const PastArgs &a, hipStream_t s);
+hipError_t hm_launch_past_fill(const PastArgs &a, hipStream_t s);

@@ -1,0 +1,341 @@
+// past_kernels.hip — a document as it was: the applied changes below a history position, or at or
+// below a clock, selected and compacted on the device, in history order, into a cold batch the merge
+// kernels take unchanged (RepoBackend's MaterializeMsg: history.slice(0, n) replayed from
+// Backend.init(); loadDocument's changes.slice(0, cursor[actor])).  No merge path is touched.
+//
+//  past_count_kernel  one wavefront per request (four to a workgroup, no LDS): the lanes stride the
+//                     document's hist rows coalesced; a selected change adds its dep / op rows
+//  past_scan_kernel   exclusive prefix sums of the four count columns in request order, in two launches
+//                     of one 1024-lane workgroup per chunk of 4096 requests (a lane four requests, a
+//                     shuffle scan per wave, the waves' sums through LDS): the chunks' sums and maxima,
+//                     then each chunk's offsets on the sum of the chunks before it; the last chunk
+//                     leaves the totals and the launch hints of the gathered batch
+//  past_fill_kernel   one wavefront per request, a 64-lane workgroup of its own; per tile of
+//                     HM_PAST_TILE history positions:
+//    mark     the lanes stride hist; a selected change sets the bit of its history position
+//    rank     popcount prefix over the tile's words, on a running base across tiles
+//    scatter  the rows stride again: a marked change leaves its log index, its dep / op counts and
+//             its first source op row in LDS at its slot (= its rank within the tile)
+//    scan     the slots' dep / op counts become offsets (a shuffle scan, 64 slots a step)
+//    write    a lane per slot: the change row with dep_off / op_first rewritten, its dep rows, its log
+//             index; then the tile's op rows with the whole wave: a lane per OUTPUT op row finds its
+//             change by binary search over the slots' op offsets and moves the 32-byte row as two
+//             16-byte words, so the stores are contiguous and the loads contiguous within a change
+//
+// Nothing inside a row is remapped: register, object and rank ids are the document's own.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/hypermerge_amd.h"
+#include "past_kernels.h"
+
+namespace hmp {
+
+#define PWG 64
+#define PTILE HM_PAST_TILE
+#define PWORDS (PTILE / 32u)
+static_assert(PWORDS <= 64u && PTILE % 64u == 0u, "a tile's bitmap words fit one per lane");
+static_assert(sizeof(hm_op_row) == 32 && sizeof(hm_change_row) == 24 && sizeof(hm_doc_row) == 48, "row sizes");
+
+// the request's source document: its segments (clamped to the tables), totals and selector
+struct Src {
+    uint32_t c_off, n_c, d_off, n_d, o_off, n_o, n_r, n_objs, n_actors, flags;
+    uint32_t npre;                             // prefix selector (clock selector: unused)
+    const uint32_t *clk;                       // clock selector's row, or NULL
+    bool bad;
+};
+
+__device__ __forceinline__ Src source_of(const PastArgs &A, unsigned long long q) {
+    Src s = {};
+    s.n_objs = 1u;                             // (ROOT: an empty document)
+    const uint32_t h = A.handles ? A.handles[q] : (uint32_t)q;
+    if (A.dm) {
+        if (h >= A.n_handles) { s.bad = true; return s; }
+        const DevDoc m = A.dm[h];
+        s.c_off = m.c_off; s.n_c = m.n_c; s.d_off = m.d_off; s.n_d = m.n_d; s.o_off = m.o_off; s.n_o = m.n_o;
+        s.n_r = m.n_r; s.n_objs = m.n_objs; s.n_actors = m.n_actors; s.flags = m.flags;
+    } else {
+        if (h >= A.n_docs) { s.bad = true; return s; }
+        const hm_doc_row r = A.docs[h];
+        s.n_r = r.n_regs; s.n_objs = r.n_objs; s.n_actors = r.n_actors; s.flags = r.flags;
+        if (A.res[h].status == HM_OK) {        // (a document whose merge threw has no history)
+            s.c_off = r.change_off; s.n_c = r.n_changes; s.d_off = r.dep_off; s.n_d = r.n_deps;
+            s.o_off = r.op_off; s.n_o = r.n_ops;
+        }
+    }
+    if ((unsigned long long)s.c_off + s.n_c > A.lim_c) { s.c_off = 0; s.n_c = 0; }
+    if ((unsigned long long)s.d_off + s.n_d > A.lim_d) { s.d_off = 0; s.n_d = 0; }
+    if ((unsigned long long)s.o_off + s.n_o > A.lim_o) { s.o_off = 0; s.n_o = 0; }
+    s.npre = A.hist_len ? A.hist_len[q] : 0u;
+    s.clk = A.clock_rows ? A.clock_rows + q * A.S : nullptr;
+    return s;
+}
+
+// is log row i selected?  p = its history position
+__device__ __forceinline__ bool selected(const Src &s, const PastArgs &A, uint32_t i, uint32_t &p) {
+    const int32_t hp = A.hist[s.c_off + i];
+    if (hp < 0 || (uint32_t)hp >= s.n_c) return false;
+    p = (uint32_t)hp;
+    if (!s.clk) return p < s.npre;
+    const hm_change_row *c = A.changes + s.c_off + i;
+    const uint32_t a = c->actor;
+    return a < A.S && c->seq <= s.clk[a];
+}
+
+// the change's dep / op rows, none where the range leaves the document's segment
+__device__ __forceinline__ bool rows_of(const Src &s, const hm_change_row &c, uint32_t &nd, uint32_t &no) {
+    bool ok = true;
+    nd = c.n_deps; no = c.n_ops;
+    if (nd && (c.dep_off < s.d_off || (unsigned long long)c.dep_off + nd > (unsigned long long)s.d_off + s.n_d)) { nd = 0; ok = false; }
+    if (no && (c.op_first < s.o_off || (unsigned long long)c.op_first + no > (unsigned long long)s.o_off + s.n_o)) { no = 0; ok = false; }
+    return ok;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+    for (uint32_t d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+#define PCWG 256
+__global__ __launch_bounds__(PCWG) void past_count_kernel(PastArgs A) {
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const unsigned long long step = (unsigned long long)gridDim.x * (PCWG / 64);
+    for (unsigned long long q = (unsigned long long)blockIdx.x * (PCWG / 64) + wv; q < A.n; q += step) {
+        const Src s = source_of(A, q);
+        uint32_t nc = 0, nd = 0, no = 0;
+        bool ok = true;
+        for (uint32_t i = lane; i < s.n_c; i += 64u) {
+            uint32_t p;
+            if (!selected(s, A, i, p)) continue;
+            uint32_t d, o;
+            ok &= rows_of(s, A.changes[s.c_off + i], d, o);
+            nc++; nd += d; no += o;
+        }
+        nc = wave_sum(nc); nd = wave_sum(nd); no = wave_sum(no);
+        const bool any_bad = __ballot(!ok) != 0ull;
+        if (lane == 0) {
+            *(uint4 *)(A.cnt + 4 * q) = make_uint4(nc, nd, no, s.n_r);
+            *(uint2 *)(A.aux + 2 * q) = make_uint2(s.n_objs, s.flags);
+            const uint32_t b = (s.bad ? HM_PAST_BAD_HANDLE : 0u) | (any_bad ? HM_PAST_BAD_ROWS : 0u);
+            if (b) atomicOr(&A.sum->bad, b);
+        }
+    }
+}
+
+#define PSWG 1024
+#define PSITEMS HM_PAST_SCAN_ITEMS
+// One chunk of PSWG * PSITEMS requests per workgroup, a lane PSITEMS consecutive requests (64 contiguous
+// bytes of counts).  FINAL = false: the chunk's sums and maxima go to part[chunk]; FINAL = true: the
+// chunk's base is the sum of the earlier chunks' parts, the offsets are written, and the last chunk
+// leaves the totals and the launch hints in the summary.
+template <bool FINAL>
+__global__ __launch_bounds__(PSWG) void past_scan_kernel(PastArgs A) {
+    __shared__ unsigned long long s_w[PSWG / 64][4];
+    __shared__ unsigned long long s_carry[4];
+    __shared__ uint32_t s_mx[6];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6, j = blockIdx.x;
+    const bool last = j == gridDim.x - 1u;
+    if (tid < 4) s_carry[tid] = 0ull;
+    if (tid < 6) s_mx[tid] = 0u;
+    __syncthreads();
+    if (FINAL) {
+        unsigned long long acc[4] = {0, 0, 0, 0};
+        for (uint32_t jj = tid; jj < j; jj += PSWG)
+            for (int k = 0; k < 4; k++) acc[k] += A.part[(size_t)jj * HM_PAST_PART + k];
+        for (int k = 0; k < 4; k++) if (acc[k]) atomicAdd(&s_carry[k], acc[k]);
+    }
+    const unsigned long long i0 = (unsigned long long)j * (PSWG * PSITEMS) + (unsigned long long)tid * PSITEMS;
+    uint4 v[PSITEMS];
+    unsigned long long in[4] = {0, 0, 0, 0};
+    uint32_t mx[5] = {0, 0, 0, 0, 0}, fl = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < PSITEMS; x++) {
+        v[x] = make_uint4(0, 0, 0, 0);
+        if (i0 + x < A.n) {
+            v[x] = *(const uint4 *)(A.cnt + 4 * (i0 + x));
+            if (!FINAL) {
+                const uint2 o = *(const uint2 *)(A.aux + 2 * (i0 + x));
+                mx[0] = max(mx[0], v[x].x); mx[1] = max(mx[1], v[x].z); mx[2] = max(mx[2], v[x].w); mx[3] = max(mx[3], o.x);
+                mx[4] = max(mx[4], v[x].y); fl |= o.y;
+            }
+        }
+        in[0] += v[x].x; in[1] += v[x].y; in[2] += v[x].z; in[3] += v[x].w;
+    }
+    const unsigned long long own[4] = {in[0], in[1], in[2], in[3]};
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const unsigned long long up = __shfl_up(in[k], d);
+            if (lane >= d) in[k] += up;
+        }
+    if (lane == 63u)
+        for (int k = 0; k < 4; k++) s_w[wv][k] = in[k];
+    __syncthreads();                                           // (s_w, and the chunk's base in s_carry)
+    if (tid < 4) {                                             // the waves' sums -> their bases, on the chunk's base
+        unsigned long long run = s_carry[tid];
+        for (uint32_t w = 0; w < PSWG / 64; w++) { const unsigned long long t = s_w[w][tid]; s_w[w][tid] = run; run += t; }
+        s_carry[tid] = run;
+    }
+    __syncthreads();
+    if (!FINAL) {
+        if (tid < 4) A.part[(size_t)j * HM_PAST_PART + tid] = s_carry[tid];
+        for (int k = 0; k < 5; k++) if (mx[k]) atomicMax(&s_mx[k], mx[k]);
+        if (fl) atomicOr(&s_mx[5], fl);
+        __syncthreads();
+        if (tid < 6) A.part[(size_t)j * HM_PAST_PART + 4 + tid] = s_mx[tid];
+        return;
+    }
+    unsigned long long run[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) run[k] = s_w[wv][k] + in[k] - own[k];
+#pragma unroll
+    for (uint32_t x = 0; x < PSITEMS; x++) {
+        if (i0 + x < A.n)
+            *(uint4 *)(A.off + 4 * (i0 + x)) = make_uint4((uint32_t)run[0], (uint32_t)run[1], (uint32_t)run[2], (uint32_t)run[3]);
+        run[0] += v[x].x; run[1] += v[x].y; run[2] += v[x].z; run[3] += v[x].w;
+    }
+    if (!last) return;
+    for (uint32_t jj = tid; jj < gridDim.x; jj += PSWG) {
+        for (int k = 0; k < 5; k++) mx[k] = max(mx[k], (uint32_t)A.part[(size_t)jj * HM_PAST_PART + 4 + k]);
+        fl |= (uint32_t)A.part[(size_t)jj * HM_PAST_PART + 9];
+    }
+    for (int k = 0; k < 5; k++) if (mx[k]) atomicMax(&s_mx[k], mx[k]);
+    if (fl) atomicOr(&s_mx[5], fl);
+    __syncthreads();
+    if (tid == 0) {
+        hm_past_summary *o = A.sum;
+        for (int k = 0; k < 4; k++) o->totals[k] = s_carry[k];
+        o->max_changes = s_mx[0]; o->max_ops = s_mx[1]; o->max_regs = s_mx[2]; o->max_objs = s_mx[3]; o->max_deps = s_mx[4];
+        o->doc_flags = s_mx[5];
+    }
+}
+
+struct Lds {
+    uint32_t bits[64], pre[64];
+    uint32_t src[PTILE];                       // per slot: the change's log row (document-local)
+    uint32_t dp[PTILE], op[PTILE];             // per slot: dep / op rows, then their offsets within the tile
+    uint32_t of[PTILE];                        // per slot: the change's first source op row
+};
+
+__global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
+    __shared__ Lds L;
+    const uint32_t lane = threadIdx.x;
+    {
+        const hm_past_summary *t = A.sum;                      // (one decision for the whole grid)
+        if (t->totals[0] > A.cap[0]) return;
+        if (!A.log_only && (t->totals[1] > A.cap[1] || t->totals[2] > A.cap[2] || t->totals[3] > A.cap[3])) return;
+    }
+    for (unsigned long long q = blockIdx.x; q < A.n; q += gridDim.x) {
+        const Src s = source_of(A, q);
+        const uint4 cn = *(const uint4 *)(A.cnt + 4 * q), of = *(const uint4 *)(A.off + 4 * q);
+        if (lane == 0) {
+            hm_doc_row r;
+            r.change_off = of.x; r.n_changes = cn.x; r.dep_off = of.y; r.n_deps = cn.y; r.op_off = of.z; r.n_ops = cn.z;
+            r.reg_off = of.w; r.n_regs = cn.w; r.n_objs = s.n_objs; r.n_actors = (uint16_t)s.n_actors; r.flags = (uint16_t)s.flags;
+            r.reserved[0] = r.reserved[1] = 0;
+            A.out_docs[q] = r;
+        }
+        if (!cn.x) continue;
+        const uint32_t n_tiles = (s.n_c + PTILE - 1u) / PTILE;
+        uint32_t base = 0, dbase = 0, obase = 0;               // changes / deps / ops gathered by the earlier tiles
+        for (uint32_t t = 0; t < n_tiles && base < cn.x; t++) {
+            L.bits[lane] = 0u;
+            __syncthreads();
+            for (uint32_t i = lane; i < s.n_c; i += 64u) {     // mark
+                uint32_t p;
+                if (selected(s, A, i, p) && p / PTILE == t) atomicOr(&L.bits[(p % PTILE) >> 5], 1u << (p & 31u));
+            }
+            __syncthreads();
+            const uint32_t w = L.bits[lane], c1 = (uint32_t)__popc(w);   // rank
+            uint32_t incl = c1;
+            for (uint32_t d = 1; d < 64u; d <<= 1) {
+                const uint32_t up = __shfl_up(incl, d);
+                if (lane >= d) incl += up;
+            }
+            L.pre[lane] = incl - c1;
+            const uint32_t tile_n = __shfl(incl, 63);
+            __syncthreads();
+            if (!tile_n) continue;
+            for (uint32_t i = lane; i < s.n_c; i += 64u) {     // scatter
+                const int32_t hp = A.hist[s.c_off + i];
+                if (hp < 0 || (uint32_t)hp >= s.n_c || (uint32_t)hp / PTILE != t) continue;
+                const uint32_t b = (uint32_t)hp % PTILE, wd = L.bits[b >> 5], bit = 1u << (b & 31u);
+                if (!(wd & bit)) continue;
+                const uint32_t k = L.pre[b >> 5] + (uint32_t)__popc(wd & (bit - 1u));
+                const hm_change_row c = A.changes[s.c_off + i];
+                uint32_t nd, no;
+                rows_of(s, c, nd, no);
+                L.src[k] = i; L.dp[k] = nd; L.op[k] = no; L.of[k] = c.op_first;
+            }
+            __syncthreads();
+            uint32_t dsum = 0, osum = 0;                        // scan
+            for (uint32_t k0 = 0; k0 < tile_n; k0 += 64u) {
+                const uint32_t k = k0 + lane;
+                const uint32_t vd = k < tile_n ? L.dp[k] : 0u, vo = k < tile_n ? L.op[k] : 0u;
+                uint32_t id = vd, io = vo;
+                for (uint32_t d = 1; d < 64u; d <<= 1) {
+                    const uint32_t ud = __shfl_up(id, d), uo = __shfl_up(io, d);
+                    if (lane >= d) { id += ud; io += uo; }
+                }
+                if (k < tile_n) { L.dp[k] = dsum + id - vd; L.op[k] = osum + io - vo; }
+                dsum += __shfl(id, 63); osum += __shfl(io, 63);
+            }
+            __syncthreads();
+            for (uint32_t k = lane; k < tile_n; k += 64u) {    // write: change rows, dep rows, the change log
+                const uint32_t j = base + k;
+                if (j >= cn.x) continue;
+                const uint32_t i = L.src[k];
+                A.out_change_log[of.x + j] = i;
+                if (A.log_only) continue;
+                hm_change_row c = A.changes[s.c_off + i];
+                uint32_t nd, no;
+                rows_of(s, c, nd, no);
+                const uint32_t d0 = dbase + L.dp[k], src_d = c.dep_off;
+                if ((unsigned long long)d0 + nd > cn.y) nd = 0;
+                c.n_deps = (uint16_t)nd; c.n_ops = no;
+                c.dep_off = of.y + d0; c.op_first = of.z + obase + L.op[k];
+                A.out_changes[of.x + j] = c;
+                for (uint32_t x = 0; x < nd; x++) A.out_deps[of.y + d0 + x] = A.deps[src_d + x];
+            }
+            for (uint32_t k = lane; k < (A.log_only ? 0u : osum); k += 64u) {   // write: the tile's op rows, a lane per output row
+                uint32_t lo = 0, hi = tile_n;                  // the last slot whose op offset is <= k
+                while (hi - lo > 1u) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (L.op[mid] <= k) lo = mid; else hi = mid;
+                }
+                const uint32_t o = obase + k;
+                if (o >= cn.z) continue;
+                const uint32_t srow = L.of[lo] + (k - L.op[lo]);
+                const uint4 *sp = (const uint4 *)(A.ops + srow);
+                uint4 *dp = (uint4 *)(A.out_ops + of.z + o);
+                const uint4 x0 = sp[0], x1 = sp[1];
+                dp[0] = x0; dp[1] = x1;
+                A.out_op_log[of.z + o] = srow - s.o_off;
+            }
+            base += tile_n; dbase += dsum; obase += osum;
+            __syncthreads();
+        }
+    }
+}
+
+}  // namespace hmp
+
+hipError_t hm_launch_past_count(const PastArgs &a, hipStream_t s) {
+    hipError_t r = hipMemsetAsync(a.sum, 0, sizeof(hm_past_summary), s);
+    if (r != hipSuccess || !a.n) return r;                     // (no request: the zero summary is the answer, nothing else is touched)
+    {
+        const unsigned long long wgs = ((unsigned long long)a.n + PCWG / 64 - 1) / (PCWG / 64);
+        hipLaunchKernelGGL(hmp::past_count_kernel, dim3((uint32_t)(wgs < 65535ull ? wgs : 65535ull)), dim3(PCWG), 0, s, a);
+        if ((r = hipGetLastError()) != hipSuccess) return r;
+    }
+    const dim3 chunks(hm_past_scan_chunks(a.n));
+    hipLaunchKernelGGL(hmp::past_scan_kernel<false>, chunks, dim3(PSWG), 0, s, a);
+    if ((r = hipGetLastError()) != hipSuccess) return r;
+    hipLaunchKernelGGL(hmp::past_scan_kernel<true>, chunks, dim3(PSWG), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t hm_launch_past_fill(const PastArgs &a, hipStream_t s) {
+    if (!a.n) return hipSuccess;
+    hipLaunchKernelGGL(hmp::past_fill_kernel, dim3(a.n < 65535u ? a.n : 65535u), dim3(PWG), 0, s, a);
+    return hipGetLastError();
+}

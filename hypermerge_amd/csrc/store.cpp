@@ -41,6 +41,7 @@
 #include "store_kernels.h"
 #include "waiting_kernels.h"
 #include "changes_kernels.h"
+#include "past_kernels.h"
 
 namespace {
 
@@ -97,6 +98,7 @@ struct hm_store {
     uint32_t stamp = 0;
     // staging (device)
     DBuf<uint8_t> stage;
+    DBuf<uint8_t> past;                           // hm_store_materialize: the gathered batch and its merge
     // in-flight batch
     std::atomic<bool> pending{false};             // a submitted batch not yet waited for (other threads may read it)
     uint64_t next_id = 1, pending_id = 0;
@@ -459,7 +461,7 @@ void hm_store_destroy(hm_store *s) {
     void *bufs[] = {s->changes, s->hist, s->ckey, s->all_deps, s->deps, s->ops, s->surv, s->smeta, s->ist, s->ldir, s->regs, s->epos,
                     s->epar, s->ekey, s->lorder, s->res_docs, s->clock,
                     s->back_clock, s->heads, s->min_clock, s->stored, s->stage.p, s->dm, s->seen, s->plan.p, s->descs.p,
-                    s->bdescs.p, s->list.p, s->blist.p, s->alist.p, s->remap.p, s->inv.p, s->rows.p, s->undo_handles.p, s->klist.p, s->mpart.p, s->st};
+                    s->bdescs.p, s->list.p, s->blist.p, s->alist.p, s->remap.p, s->inv.p, s->rows.p, s->undo_handles.p, s->klist.p, s->mpart.p, s->past.p, s->st};
     for (void *b : bufs) if (b) (void)hipFree(b);
     for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
     if (s->h_st) (void)hipHostFree(s->h_st);
@@ -1148,21 +1150,165 @@ int hm_store_missing_changes(hm_store *s, uint32_t n, const uint32_t *doc_handle
     }
 }
 
+static_assert(sizeof(PlanStats) >= sizeof(hm_past_summary), "the summary is read back through h_st");
+
+// The count pass of n staged requests: handles and the selector go to the stage buffer, the counts,
+// offsets and summary stay there (P.cnt / P.off / P.sum); *sum = the summary, read back.
+static int past_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *hist_len,
+                      const uint32_t *clock_rows, PastArgs &P, hm_past_summary *sum) {
+    const uint32_t S = s->S;
+    hipStream_t st = hm_engine_stream(s->e);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t sel_b = hist_len ? 4 * (size_t)n : 4 * (size_t)n * S;
+    const size_t o_sum = 0, o_h = 256, o_sel = o_h + al(4 * (size_t)n), o_cnt = o_sel + al(sel_b), o_off = o_cnt + al(16 * (size_t)n),
+                 o_aux = o_off + al(16 * (size_t)n), o_part = o_aux + al(8 * (size_t)n),
+                 total = o_part + al((size_t)hm_past_scan_chunks(n) * HM_PAST_PART * 8);
+    int rc = ensure_stage(s, total);
+    if (rc) return rc;
+    uint8_t *sp = s->stage.p;
+    SCHK(s, hipMemcpyAsync(sp + o_h, doc_handles, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    SCHK(s, hipMemcpyAsync(sp + o_sel, hist_len ? hist_len : clock_rows, sel_b, hipMemcpyHostToDevice, st));
+    P = PastArgs{};
+    P.n = n; P.handles = (const uint32_t *)(sp + o_h); P.dm = s->dm; P.n_handles = s->n_handles; P.S = S;
+    P.changes = s->changes; P.hist = s->hist; P.deps = s->deps; P.ops = s->ops;
+    P.lim_c = s->cap_c; P.lim_d = s->cap_d; P.lim_o = s->cap_o;
+    if (hist_len) P.hist_len = (const uint32_t *)(sp + o_sel); else P.clock_rows = (const uint32_t *)(sp + o_sel);
+    P.cnt = (uint32_t *)(sp + o_cnt); P.off = (uint32_t *)(sp + o_off); P.aux = (uint32_t *)(sp + o_aux);
+    P.part = (unsigned long long *)(sp + o_part);
+    P.sum = (hm_past_summary *)(sp + o_sum);
+    SCHK(s, hm_launch_past_count(P, st));
+    SCHK(s, hipMemcpyAsync(s->h_st, P.sum, sizeof(hm_past_summary), hipMemcpyDeviceToHost, st));
+    SCHK(s, hipStreamSynchronize(st));
+    memcpy(sum, s->h_st, sizeof *sum);
+    if (sum->bad & HM_PAST_BAD_HANDLE) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad handle");
+    if (sum->bad) return hm_engine_fail(s->e, HM_ERR_INVALID, "a change row outside its document's segments");
+    return HM_OK;
+}
+
+int hm_store_past_sizes(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *hist_len,
+                        const uint32_t *clock_rows, uint32_t *out_counts, uint64_t *out_totals) {
+    if (!s || (n && !doc_handles)) return HM_ERR_INVALID;
+    if ((hist_len != nullptr) == (clock_rows != nullptr))
+        return hm_engine_fail(s->e, HM_ERR_INVALID, "exactly one of hist_len and clock_rows");
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        if (!n) { if (out_totals) memset(out_totals, 0, 4 * sizeof(uint64_t)); return HM_OK; }
+        PastArgs P;
+        hm_past_summary sum;
+        int rc = past_count(s, n, doc_handles, hist_len, clock_rows, P, &sum);
+        if (rc) return rc;
+        if (out_totals) memcpy(out_totals, sum.totals, sizeof sum.totals);
+        if (out_counts) {
+            hipStream_t st = hm_engine_stream(s->e);
+            SCHK(s, hipMemcpyAsync(out_counts, P.cnt, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
+            SCHK(s, hipStreamSynchronize(st));
+        }
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_past_sizes");
+    }
+}
+
+int hm_store_materialize(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *hist_len,
+                         const uint32_t *clock_rows, const hm_past_out *out, uint64_t *out_totals) {
+    if (!out) return HM_ERR_INVALID;
+    return hm_store_materialize_sized(s, n, doc_handles, hist_len, clock_rows,
+                                      [](void *ctx, const uint64_t *) { return (const hm_past_out *)ctx; }, (void *)out, out_totals);
+}
+
+}  // extern "C"
+
+// (engine_internal.h) the outputs are asked for once the count pass has sized them: one count pass
+// for a caller that allocates by the totals
+int hm_store_materialize_sized(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *hist_len,
+                               const uint32_t *clock_rows, hm_past_alloc alloc, void *ctx, uint64_t *out_totals) {
+    if (!s || !alloc || (n && !doc_handles)) return HM_ERR_INVALID;
+    if ((hist_len != nullptr) == (clock_rows != nullptr))
+        return hm_engine_fail(s->e, HM_ERR_INVALID, "exactly one of hist_len and clock_rows");
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        if (!n) { if (out_totals) memset(out_totals, 0, 4 * sizeof(uint64_t)); return HM_OK; }
+        const uint32_t S = s->S;
+        hipStream_t st = hm_engine_stream(s->e);
+        PastArgs P;
+        hm_past_summary sum;
+        int rc = past_count(s, n, doc_handles, hist_len, clock_rows, P, &sum);
+        if (rc) return rc;
+        if (out_totals) memcpy(out_totals, sum.totals, sizeof sum.totals);
+        const uint64_t tc = sum.totals[0], td = sum.totals[1], to = sum.totals[2], tr = sum.totals[3];
+        const hm_past_out *out = alloc(ctx, sum.totals);
+        if (!out) return hm_engine_fail(s->e, HM_ERR_NOMEM, "no outputs for the materialized documents");
+        const hm_results &R = out->res;
+        // a table nobody asked for needs no capacity
+        const bool want_c = out->changes || out->change_log || R.hist || R.all_deps, want_d = out->deps != nullptr,
+                   want_o = out->ops || out->op_log || R.surv, want_r = R.regs != nullptr;
+        if ((want_c && tc > out->cap_changes) || (want_d && td > out->cap_deps) || (want_o && to > out->cap_ops) ||
+            (want_r && tr > out->cap_regs))
+            return hm_engine_fail(s->e, HM_ERR_NOMEM, "a capacity below the rows of the materialized documents");
+        if (std::max(std::max(tc, td), std::max(to, tr)) > 0xFFFFFFFFull)
+            return hm_engine_fail(s->e, HM_ERR_NOMEM, "a call's rows stay below 2^32");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        // [docs][changes][deps][ops][change_log][op_log] the gathered batch, then its merge's tables
+        const size_t sz[14] = {n * sizeof(hm_doc_row), tc * sizeof(hm_change_row), td * sizeof(hm_dep_row), to * sizeof(hm_op_row),
+                               tc * 4, to * 4, n * sizeof(hm_doc_result), (size_t)n * S * 4, (size_t)n * S * 4, (size_t)n * S * 4,
+                               tc * 4, tc * S * 4, tr * sizeof(hm_reg_result), to * sizeof(hm_surv_result)};
+        size_t o[14], total = 0;
+        for (int i = 0; i < 14; i++) { o[i] = total; total += al(sz[i] + 1); }
+        if ((rc = ensure_buf(s, s->past, total))) return rc;
+        uint8_t *bp = s->past.p;
+        P.cap[0] = (uint32_t)tc; P.cap[1] = (uint32_t)td; P.cap[2] = (uint32_t)to; P.cap[3] = (uint32_t)tr;
+        P.out_docs = (hm_doc_row *)(bp + o[0]); P.out_changes = (hm_change_row *)(bp + o[1]); P.out_deps = (hm_dep_row *)(bp + o[2]);
+        P.out_ops = (hm_op_row *)(bp + o[3]); P.out_change_log = (uint32_t *)(bp + o[4]); P.out_op_log = (uint32_t *)(bp + o[5]);
+        SCHK(s, hm_launch_past_fill(P, st));
+        hm_batch b = {};
+        b.a_stride = S; b.n_docs = n;
+        b.n_changes = (uint32_t)tc; b.n_deps = (uint32_t)td; b.n_ops = (uint32_t)to; b.n_regs = (uint32_t)tr;
+        b.max_changes = sum.max_changes; b.max_ops = sum.max_ops; b.max_regs = sum.max_regs; b.max_objs = sum.max_objs;
+        b.max_deps = sum.max_deps; b.doc_flags = sum.doc_flags;
+        if (!b.max_changes && !b.max_ops && !b.max_regs && !b.max_objs) b.max_objs = 1;   // device hints present
+        b.docs = P.out_docs; b.changes = P.out_changes; b.deps = P.out_deps; b.ops = P.out_ops;
+        hm_results d;
+        d.docs = (hm_doc_result *)(bp + o[6]); d.clock = (uint32_t *)(bp + o[7]); d.back_clock = (uint32_t *)(bp + o[8]);
+        d.heads = (uint32_t *)(bp + o[9]); d.hist = (int32_t *)(bp + o[10]); d.all_deps = (uint32_t *)(bp + o[11]);
+        d.regs = (hm_reg_result *)(bp + o[12]); d.surv = (hm_surv_result *)(bp + o[13]);
+        if ((rc = hm_engine_launch_merge(s->e, &b, &d, nullptr, nullptr))) return rc;
+        void *dst[14] = {out->docs, out->changes, out->deps, out->ops, out->change_log, out->op_log, R.docs, R.clock, R.back_clock,
+                         R.heads, R.hist, R.all_deps, R.regs, R.surv};
+        for (int i = 0; i < 14; i++)
+            if (dst[i] && sz[i]) SCHK(s, hipMemcpyAsync(dst[i], bp + o[i], sz[i], hipMemcpyDeviceToHost, st));
+        SCHK(s, hipStreamSynchronize(st));
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_materialize");
+    }
+}
+
+extern "C" {
+
+// (the selection of one prefix request of the past kernels: out_change_log, nothing else gathered)
 int hm_doc_history_prefix(hm_store *s, uint32_t doc, uint32_t n, uint32_t *out) {
     if (!s || doc >= s->n_handles || (n && !out)) return HM_ERR_INVALID;
     if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
-    int rc = HM_OK;
-    const DevDoc m = read_doc(s, doc, &rc);
-    if (rc) return -rc;
-    std::vector<int32_t> h(m.n_c);
-    if (m.n_c) SCHK(s, hipMemcpy(h.data(), s->hist + m.c_off, m.n_c * 4, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> by_pos(m.n_c, HM_NONE);
-    uint32_t H = 0;
-    for (uint32_t i = 0; i < m.n_c; i++)
-        if (h[i] >= 0 && (uint32_t)h[i] < m.n_c) { by_pos[h[i]] = i; H = std::max(H, (uint32_t)h[i] + 1); }
-    const uint32_t k = std::min(n, H);
-    for (uint32_t i = 0; i < k; i++) out[i] = by_pos[i];
-    return (int)k;
+    try {
+        hipStream_t st = hm_engine_stream(s->e);
+        PastArgs P;
+        hm_past_summary sum;
+        int rc = past_count(s, 1, &doc, &n, nullptr, P, &sum);
+        if (rc) return -rc;
+        const uint32_t k = (uint32_t)sum.totals[0];
+        if (!k) return 0;
+        if ((rc = ensure_buf(s, s->past, sizeof(hm_doc_row) + 256 + 4 * (size_t)k))) return -rc;
+        P.log_only = 1u;
+        P.cap[0] = k;
+        P.out_docs = (hm_doc_row *)s->past.p;
+        P.out_change_log = (uint32_t *)(s->past.p + 256);
+        SCHK(s, hm_launch_past_fill(P, st));
+        SCHK(s, hipMemcpyAsync(out, P.out_change_log, 4 * (size_t)k, hipMemcpyDeviceToHost, st));
+        SCHK(s, hipStreamSynchronize(st));
+        return (int)k;
+    } catch (...) {
+        return -hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_doc_history_prefix");
+    }
 }
 
 int hm_doc_set_min_clock(hm_store *s, uint32_t doc, const uint32_t *clock) {

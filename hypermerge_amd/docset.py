@@ -155,6 +155,38 @@ class DocSet:
         s, _ = _text(self._L, t)
         return json.loads(s)
 
+    def materialize(self, docs: Sequence[int], history: Optional[Sequence[int]] = None,
+                    clocks: Optional[Sequence[Dict[str, float]]] = None) -> List[Dict[str, Any]]:
+        """Documents as they were (RepoBackend's MaterializeMsg, many per call): docs[i] at history
+        length history[i] (history.slice(0, n) replayed from Backend.init()), or at the clock clocks[i]
+        ({actorId: seq}: each actor's changes up to that seq).  Per request {"doc", "clock", "deps",
+        "history", "view"}, the view as ``view`` gives it (hm_docset_materialize)."""
+        ids = np.ascontiguousarray(docs, np.uint32)
+        hl = eoff = data = aoff = sq = None
+        if history is not None:
+            hl = np.ascontiguousarray(np.minimum(np.asarray(history, np.int64), 0xFFFFFFFF), np.uint32)
+            assert len(hl) == len(ids)
+        if clocks is not None:
+            assert len(clocks) == len(ids)
+            eoff = np.zeros(len(ids) + 1, np.uint32)
+            names: List[bytes] = []
+            seqs: List[float] = []
+            for i, clock in enumerate(clocks):
+                for a, q in clock.items():
+                    names.append(a.encode("utf-8", "surrogatepass"))
+                    seqs.append(float(q))
+                eoff[i + 1] = len(names)
+            aoff = np.zeros(len(names) + 1, np.uint32)
+            np.cumsum([len(x) for x in names], out=aoff[1:])
+            data = np.frombuffer(b"".join(names) + b"\0", np.uint8)
+            sq = np.array(seqs + [0.0], np.float64)
+        p = lambda a: None if a is None else a.ctypes.data
+        t = ctypes.c_void_p()
+        self.engine._check(self._L.hm_docset_materialize(self._h, len(ids), ids.ctypes.data, p(hl), p(eoff), p(data), p(aoff),
+                                                         p(sq), ctypes.byref(t)), "hm_docset_materialize")
+        s, _ = _text(self._L, t)
+        return json.loads(s)
+
     def handles(self, a_stride: int) -> Dict[str, int]:
         """hm_docset_handles: handles opened in the a_stride store and released ones awaiting reuse."""
         o, f = ctypes.c_uint32(), ctypes.c_uint32()

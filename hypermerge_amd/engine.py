@@ -38,7 +38,9 @@ EXPORTS = ("hm_abi_version", "hm_status_message", "hm_engine_create", "hm_engine
            "hm_docset_stats", "hm_docset_routing", "hm_docset_handles", "hm_sync_ranges_host", "hm_batch_submit_device", "hm_batch_wait_device",
            "hm_batch_undo", "hm_store_blocked", "hm_store_waiting", "hm_store_read_queue", "hm_missing_deps_device",
            "hm_missing_deps_host", "hm_docset_blocked", "hm_docset_waiting", "hm_store_missing_changes",
-           "hm_missing_changes_device", "hm_missing_changes_host", "hm_docset_missing_changes")
+           "hm_missing_changes_device", "hm_missing_changes_host", "hm_docset_missing_changes",
+           "hm_store_past_sizes", "hm_store_materialize", "hm_materialize_work_bytes", "hm_materialize_device",
+           "hm_docset_materialize")
 
 _lib = None
 
@@ -123,6 +125,11 @@ def lib():
             "hm_missing_changes_host": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), vp, vp, vp, u32,
                                         vp, vp, vp, u32, vp],
             "hm_docset_missing_changes": [vp, u32, vp, vp, vp, vp, vp, u32, vp],
+            "hm_store_past_sizes": [vp, u32, vp, vp, vp, vp, vp],
+            "hm_store_materialize": [vp, u32, vp, vp, vp, vp, vp],
+            "hm_materialize_work_bytes": [u32],
+            "hm_docset_materialize": [vp, u32, vp, vp, vp, vp, vp, vp, vp],
+            "hm_materialize_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, vp],
         }
         for f, a in sig.items():
             getattr(L, f).argtypes = a
@@ -137,6 +144,7 @@ def lib():
         L.hm_decoded_reg.restype = ctypes.c_void_p
         L.hm_decoded_free.restype = None
         L.hm_clock_records_scratch_bytes.restype = ctypes.c_size_t
+        L.hm_materialize_work_bytes.restype = ctypes.c_size_t
         L.hm_docset_destroy.restype = None
         L.hm_docset_engine.restype = ctypes.c_void_p
         L.hm_text_data.restype = ctypes.c_void_p
@@ -147,6 +155,23 @@ def lib():
 
 
 MC_RAW, MC_ONLY_LISTED = 1, 2   # HM_MC_*
+
+
+class CPastOut(ctypes.Structure):
+    """struct hm_past_out"""
+    _fields_ = [("cap_changes", ctypes.c_uint32), ("cap_deps", ctypes.c_uint32), ("cap_ops", ctypes.c_uint32),
+                ("cap_regs", ctypes.c_uint32), ("docs", ctypes.c_void_p), ("changes", ctypes.c_void_p),
+                ("deps", ctypes.c_void_p), ("ops", ctypes.c_void_p), ("change_log", ctypes.c_void_p),
+                ("op_log", ctypes.c_void_p), ("res", CResults)]
+
+
+class CPastSummary(ctypes.Structure):
+    """struct hm_past_summary"""
+    _fields_ = [("totals", ctypes.c_uint64 * 4)] + [(f, ctypes.c_uint32) for f in (
+        "max_changes", "max_ops", "max_regs", "max_objs", "max_deps", "doc_flags", "bad", "pad")]
+
+
+assert ctypes.sizeof(CPastSummary) == 64
 
 
 def pack_entries(have, n: int):
@@ -274,6 +299,16 @@ class Engine:
                                                       p(entry_actor), p(entry_seq), n_entries, flags, p(out_closure),
                                                       p(out_range), p(out_log), cap, p(out_total), p(out_bad), p(stream)),
                     "hm_missing_changes_device")
+
+    def materialize_device(self, cbatch: CBatch, cresults: CResults, n: int, doc_index: int, hist_len: int,
+                           clock_rows: int, out: "CPastOut", out_summary: int, work: int, stream: int = 0) -> None:
+        """hm_materialize_device: documents of a merged cold batch gathered as they were at a history
+        length or a clock, every table in device memory (pointers; `out` a CPastOut of device tables,
+        `work` of work_bytes(n) bytes; enqueued, not synchronised)."""
+        p = lambda x: ctypes.c_void_p(x) if x else None
+        self._check(self._L.hm_materialize_device(self._h, ctypes.byref(cbatch), ctypes.byref(cresults), n, p(doc_index),
+                                                  p(hist_len), p(clock_rows), ctypes.byref(out), p(out_summary), p(work),
+                                                  p(stream)), "hm_materialize_device")
 
     def small_occupancy(self, batch: Batch) -> Sequence[int]:
         """(resident one-wave workgroups per CU, CUs, op rows per lane, size class, lists, counters) of

@@ -340,6 +340,49 @@ function missingIndices(ds, ids, clocks, flags) {
 }
 const missingOf = (state, clock, flags) => missingIndices(state.ds, [state.id], [clock], flags)[0].map((i) => state.change(i))
 
+// documents as they were (RepoBackend's MaterializeMsg, many per device call): ids[i] at the history
+// length reqs[i].history (history.slice(0, n) replayed from Backend.init()) or at the clock
+// reqs[i].clock ({actorId: seq}: each actor's changes up to that seq, loadDocument's cursor).  The
+// selection, its compaction in history order and the merge run on the device over the rows the store
+// already holds; no change is re-encoded.  Per request {clock, deps, history, doc}: opSet.clock,
+// opSet.deps, history.size and the plain document.  Reads the rounds already applied.
+function plainOf(view, uuid) {
+  const ov = view[uuid]
+  if (!ov) return {}
+  const val = (e) => (e.link ? plainOf(view, e.value) : e.value)
+  if (ov.type === 'list' || ov.type === 'text') return ov.elems.map(([, e]) => val(e))
+  const o = {}
+  for (const [k, e] of ov.keys) o[k] = val(e)
+  return o
+}
+function materializeAtMany(ds, ids, reqs) {
+  const out = new Array(ids.length)
+  const byHist = [], byClock = []
+  reqs.forEach((r, i) => { (r.clock !== undefined && r.clock !== null ? byClock : byHist).push(i) })
+  const take = (at, text) => JSON.parse(text).forEach((g, j) => {
+    out[at[j]] = { clock: g.clock, deps: g.deps, history: g.history, doc: g.view === null ? null : plainOf(g.view, ROOT_UUID) }
+  })
+  if (byHist.length) {
+    const hl = Uint32Array.from(byHist.map((i) => Math.min(Math.max(Math.floor(Number(reqs[i].history) || 0), 0), 0xffffffff)))
+    take(byHist, addon.docsetMaterialize(ds, Uint32Array.from(byHist.map((i) => ids[i])), hl, null, null, null, null))
+  }
+  if (byClock.length) {
+    const eoff = new Uint32Array(byClock.length + 1)
+    const names = [], seqs = []
+    byClock.forEach((i, j) => {
+      const c = plainClock(reqs[i].clock)
+      for (const a of Object.keys(c)) { names.push(Buffer.from(a, 'utf8')); seqs.push(Number(c[a])) }
+      eoff[j + 1] = names.length
+    })
+    const aoff = new Uint32Array(names.length + 1)
+    names.forEach((b, k) => { aoff[k + 1] = aoff[k] + b.length })
+    take(byClock, addon.docsetMaterialize(ds, Uint32Array.from(byClock.map((i) => ids[i])), null, eoff, Buffer.concat(names),
+      aoff, Float64Array.from(seqs)))
+  }
+  return out
+}
+const ROOT_UUID = '00000000-0000-0000-0000-000000000000'
+
 // FNV-1a 64 over the UTF-8 bytes of an id string: the shard key (and the clock exchange's
 // record key) of hypermerge_amd/exchange.py and include/hypermerge_amd.h.
 // Computed on two 32-bit halves in plain Numbers (h * prime = h * 0x1b3 + h << 40; every partial
@@ -396,6 +439,7 @@ class GpuBackendState {
     this.ds = engine.docsets[this.shard]
     this.id = addon.docsetOpen(this.ds, 1)
     engine.states[this.shard].set(this.id, this)    // (docset id -> state: GpuEngine.blocked names documents)
+    if (docId !== undefined) engine.byDocId[this.shard].set(docId, this)   // (docId -> state: GpuEngine.materialize by id)
     this.log = []
     this.histLen = 0
     this.nQueued = 0
@@ -447,6 +491,7 @@ class GpuEngine {
     this.docsets = this.devices.map((d) => addon.docsetCreate(d, o.threads || 0, this.patches, o.binary !== false,
       this.diffs === 'net'))
     this.states = this.docsets.map(() => new Map())     // per docset: document id -> state
+    this.byDocId = this.docsets.map(() => new Map())    // per docset: docId given to init -> its latest state
     this.queues = new Map()          // state -> FIFO of jobs
     this.flushing = false
     this.scheduled = false
@@ -503,6 +548,30 @@ class GpuEngine {
       at.forEach((i, j) => { out[i] = idx[j].map((x) => states[i].change(x)) })
     })
     return out
+  }
+
+  // documents as they were, many at once: reqs[i] = {state | id, history: n} or {state | id, clock:
+  // {actorId: seq}} (id: the docId given to init; a request may repeat a document) -> per request
+  // {clock, deps, history, doc} with the plain document (one or two device calls per docset: the
+  // selection, its compaction in history order and the merge run there).  Reflects the rounds
+  // already applied: in 'async' mode await idle() first.
+  materialize(reqs) {
+    const states = reqs.map((r) => r.state || this.stateOf(r.id))
+    const out = new Array(reqs.length)
+    this.docsets.forEach((ds, k) => {
+      const at = []
+      states.forEach((st, i) => { if (st.shard === k) at.push(i) })
+      if (!at.length) return
+      const got = materializeAtMany(ds, at.map((i) => states[i].id), at.map((i) => reqs[i]))
+      at.forEach((i, j) => { out[i] = got[j] })
+    })
+    return out
+  }
+
+  stateOf(docId) {
+    const st = this.byDocId[this.shardOf(docId)].get(docId)
+    if (st) return st
+    throw new Error(`GpuEngine.materialize: no document ${docId}`)
   }
 
   // job: {entries|null, done(payload|null), fail(err)}
@@ -952,6 +1021,13 @@ class DocBackend {
   // what this document's queued changes wait for, {actorId: seq} ({} before init; of the rounds
   // already applied: in 'async' mode await engine.idle() first)
   missingDeps() { return this.back ? waitingOf(this.back).missing : {} }
+
+  // the document as it was when its history had n entries (Repo.materialize(url, n)): {clock, deps,
+  // history, doc}, doc = the plain document that materializing Backend.applyChanges(Backend.init(),
+  // history.slice(0, n)) gives, computed on the device from the resident log (undefined before init;
+  // of the rounds already applied: in 'async' mode await engine.idle() first).  The patch-shaped
+  // MaterializeMsg reply still replays history.slice(0, n) on the host.
+  materializeAt(n) { return this.back ? this.engine.materialize([{ state: this.back, history: n }])[0] : undefined }
 
   // changes: Change objects (the reference's), or raw hypercore blocks / JSON texts of them
   applyRemoteChanges(changes) { this.remoteChangesQ.push(changes) }

@@ -1003,6 +1003,43 @@ static napi_value DocsetMissingChanges(napi_env env, napi_callback_info info) {
     return js;
 }
 
+/* docsetMaterialize(docset, ids Uint32Array, histLen Uint32Array | null, entryOff Uint32Array [n + 1] | null,
+ * actorIds Buffer, actorOff Uint32Array [entries + 1], seqs Float64Array) -> JSON text, per request
+ * {"doc", "clock", "deps", "history", "view"}: the documents as they were at a history length, or at a
+ * clock given as docsetMissingChanges takes one (exactly one of histLen and entryOff; refused while
+ * a call on the docset is in flight) */
+static napi_value DocsetMaterialize(napi_env env, napi_callback_info info) {
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return NULL;
+    Docset *d = get_docset(env, argv[0]);
+    if (!d) return NULL;
+    void *p[6]; size_t len[6];
+    for (int i = 0; i < 6; i++)
+        if (!get_bytes(env, argv[1 + i], &p[i], &len[i])) return NULL;
+    const uint32_t n = (uint32_t)(len[0] / 4);
+    const uint32_t *hl = (const uint32_t *)p[1], *eoff = (const uint32_t *)p[2], *aoff = (const uint32_t *)p[4];
+    const uint32_t zero[1] = {0};
+    int ok = (hl != NULL) != (eoff != NULL);
+    uint32_t ne = 0;
+    if (ok && hl) ok = len[1] / 4 == n;
+    if (ok && eoff) {
+        ok = len[2] / 4 == (size_t)n + 1 && eoff[0] == 0;
+        ne = ok ? eoff[n] : 0;
+        ok = ok && len[5] / 8 >= ne && (ne == 0 || (len[4] / 4 >= (size_t)ne + 1 && aoff[ne] <= len[3]));
+    }
+    if (!ok) { napi_throw_type_error(env, NULL, "docsetMaterialize: one selector, and table lengths that agree"); return NULL; }
+    hm_text *t = NULL;
+    int st = hm_docset_materialize(d->ds, n, (const uint32_t *)p[0], hl, eoff, p[3] ? (const char *)p[3] : "",
+                                   ne ? aoff : zero, ne ? (const double *)p[5] : NULL, &t);
+    if (st) return throw_status(env, d->engine, st, "hm_docset_materialize");
+    size_t tl = 0;
+    const char *s = hm_text_data(t, &tl);
+    napi_value js;
+    napi_create_string_utf8(env, s, tl, &js);
+    hm_text_free(t);
+    return js;
+}
+
 /* docsetInfo(docset, doc) ->{aStride, nChanges, nOps, nActors, nObjs, nRegs, histLen, nQueued} */
 static napi_value DocsetInfo(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -1264,7 +1301,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"docsetCreate", DocsetCreate}, {"docsetOpen", DocsetOpen}, {"docsetApply", DocsetApply}, {"docsetApplyPacked", DocsetApplyPacked},
         {"docsetHistoryPrefix", DocsetHistoryPrefix}, {"docsetClockUpdate", DocsetClockUpdate},
         {"docsetView", DocsetView}, {"docsetBlocked", DocsetBlocked}, {"docsetWaiting", DocsetWaiting},
-        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
+        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetMaterialize", DocsetMaterialize}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
         {"cursorsCreate", CursorsCreate}, {"cursorsReserve", CursorsReserve}, {"cursorsUpdate", CursorsUpdate},
         {"cursorsGet", CursorsGet}, {"cursorsEntry", CursorsEntry}, {"cursorsDocsWithActors", CursorsDocsWithActors},
         {"syncRanges", SyncRanges}, {"decodeBlocks", DecodeBlocks}, {"commCreateLocalDocsets", CommCreateLocalDocsets},

@@ -23,7 +23,7 @@ from .columnar import (ACTIONS, CHANGE_DT, DEP_DT, DOC_DT, DOC_RESULT_DT, OP_DT,
                        SURV_RESULT_DT, DATATYPES, DOC_HAS_COUNTERS, DOC_HAS_LISTS, DT_COUNTER, HEAD,
                        INC, INS, LINK, MAKE_LIST, MAKE_TEXT, NONE, ROOT_ID, SET, DEL, V_NULL, V_OBJ,
                        Batch, CBatch, Results, _value, content_key, js_key)
-from .engine import MC_ONLY_LISTED, MC_RAW, Engine, EngineError, lib, pack_entries
+from .engine import MC_ONLY_LISTED, MC_RAW, CPastOut, Engine, EngineError, lib, pack_entries
 
 
 class StringPool:
@@ -465,6 +465,67 @@ class DocStore:
     def changes_for_actor(self, h: int, actor: str, after: int = 0) -> List[int]:
         """Backend.getChangesForActor: the actor's applied changes with seq > after, history order."""
         return self.missing_changes([h], [{actor: after}], MC_RAW | MC_ONLY_LISTED)[0]
+
+    # -- a document as it was (MaterializeMsg / loadDocument at a clock) ------------------------------
+    def _selector(self, hs: np.ndarray, history, clocks):
+        n = len(hs)
+        if (history is None) == (clocks is None):
+            return None, None                          # (the library refuses it: HM_ERR_INVALID)
+        if history is not None:
+            hl = np.ascontiguousarray(np.minimum(np.asarray(history, np.int64), 0xFFFFFFFF), np.uint32)
+            assert hl.shape == (n,), hl.shape
+            return hl, None
+        if isinstance(clocks, np.ndarray):
+            rows = np.ascontiguousarray(clocks, np.uint32)
+        else:                                          # {actorId: seq} per request (ids the document never saw: dropped)
+            rows = np.zeros((n, self.S), np.uint32)
+            for i, (h, clock) in enumerate(zip(hs, clocks)):
+                if h >= len(self.enc):                 # (a RowStore keeps no actor tables: rank rows there)
+                    raise EngineError(f"clocks by actor id need the document's host encoder (handle {int(h)} has none): "
+                                      "pass [n, a_stride] rank rows")
+                rank = {a: r for r, a in enumerate(self.enc[h].actors)}
+                for a, q in clock.items():
+                    if a in rank:
+                        rows[i, rank[a]] = min(max(int(q), 0), 0xFFFFFFFF)
+        assert rows.shape == (n, self.S), rows.shape
+        return None, rows
+
+    def past_sizes(self, handles, history=None, clocks=None) -> Tuple[np.ndarray, np.ndarray]:
+        """hm_store_past_sizes: ([n, 4] changes / deps / ops / registers per request, their [4] totals) of
+        the documents `handles` as they were at history length history[i] or at the clock clocks[i]
+        (an [n, S] array of rank-indexed rows, or {actorId: seq} per request)."""
+        hs = np.ascontiguousarray(handles, np.uint32)
+        n = len(hs)
+        hl, rows = self._selector(hs, history, clocks)
+        cnt = np.zeros((max(n, 1), 4), np.uint32)
+        tot = np.zeros(4, np.uint64)
+        self._check(self._L.hm_store_past_sizes(self._h, n, _p(hs), _p(hl), _p(rows), _p(cnt), _p(tot)),
+                    "hm_store_past_sizes")
+        return cnt[:n], tot
+
+    def materialize(self, handles, history=None, clocks=None) -> Tuple[Batch, Results, np.ndarray, np.ndarray]:
+        """hm_store_materialize: the documents `handles` (a handle may repeat) as they were at history
+        length history[i] (clamped, as history.slice(0, n) clamps) or at the clock clocks[i]: the
+        applied changes selected, gathered on the device in history order into a cold batch (request
+        i = document i) and merged from Backend.init().  Returns (the gathered Batch, its Results,
+        change_log, op_log): change_log[j] / op_log[k] = the document-local log index of gathered
+        change j / op k.  The resident documents are only read.  (The sizes are asked first, to allocate
+        the tables: a caller that keeps buffers calls hm_store_materialize with its capacities.)"""
+        hs = np.ascontiguousarray(handles, np.uint32)
+        n, S = len(hs), self.S
+        hl, rows = self._selector(hs, history, clocks)
+        _, tot = self.past_sizes(hs, hl, rows) if (hl is not None or rows is not None) else (None, np.zeros(4, np.uint64))
+        nc, nd, no, nr = (int(x) for x in tot)
+        b = Batch(np.zeros(n, DOC_DT), np.zeros(nc, CHANGE_DT), np.zeros(nd, DEP_DT), np.zeros(no, OP_DT), S)
+        r = Results(np.zeros(n, DOC_RESULT_DT), np.zeros(n * S, np.uint32), np.zeros(n * S, np.uint32),
+                    np.zeros(n * S, np.uint32), np.zeros(nc, np.int32), np.zeros(nc * S, np.uint32),
+                    np.zeros(nr, REG_RESULT_DT), np.zeros(no, SURV_RESULT_DT))
+        clog, olog = np.zeros(nc, np.uint32), np.zeros(no, np.uint32)
+        out = CPastOut(nc, nd, no, nr, b.docs.ctypes.data, b.changes.ctypes.data, b.deps.ctypes.data, b.ops.ctypes.data,
+                       clog.ctypes.data, olog.ctypes.data, r.c_struct())
+        self._check(self._L.hm_store_materialize(self._h, n, _p(hs), _p(hl), _p(rows), ctypes.byref(out), None),
+                    "hm_store_materialize")
+        return b, r, clog, olog
 
     def set_min_clock(self, h: int, clock: Dict[str, int]) -> None:
         """minimumClock (actor id -> seq); its actors must already be in the document's actor table."""

@@ -403,7 +403,11 @@ int hm_store_read_regs(hm_store *s, uint32_t n, const uint32_t *doc_handles, con
 int hm_doc_log(hm_store *s, uint32_t doc, hm_change_row *changes, hm_dep_row *deps, hm_op_row *ops);
 
 /* history.slice(0, n): log indices of the first n applied changes, in history
- * order (src/RepoBackend.ts:572-576).  Returns the count written (<= n). */
+ * order (src/RepoBackend.ts:572-576).  Returns the count written (<= n): the applied changes at
+ * history positions below n (on a consistent document min(n, history.size)).  One prefix request of
+ * the past kernels (hm_store_materialize's selection, the change map alone): per call two small
+ * host-to-device copies, a memset, four kernel launches and two stream synchronisations, so a caller
+ * with many documents asks hm_store_materialize / hm_store_past_sizes once instead. */
 int hm_doc_history_prefix(hm_store *s, uint32_t doc, uint32_t n, uint32_t *out_log_index);
 
 /* history.slice(from[i], to[i]) of many documents at once (the changes one applyChanges round
@@ -484,6 +488,69 @@ int hm_missing_changes_host(hm_engine *e, const hm_batch *b, const hm_results *r
                             const uint16_t *entry_actor, const uint32_t *entry_seq, uint32_t flags,
                             uint32_t *out_closure, uint32_t *out_range, uint32_t *out_log_index, uint32_t cap,
                             uint32_t *out_total);
+
+/* A document as it was: resident documents materialized at a past history point, many per call
+ * (src/RepoBackend.ts:570-579 MaterializeMsg: Backend.applyChanges(Backend.init(), history.slice(0, n));
+ * src/RepoBackend.ts:238-257 loadDocument: each actor's changes.slice(0, cursor[actor])).
+ * Request i = document doc_handles[i] (a handle may repeat) with one selector; exactly one of the
+ * two arrays is not NULL:
+ *   hist_len[i]                   the applied changes at history positions < min(hist_len[i], history.size)
+ *   clock_rows[i*a_stride ..]     the applied changes with seq <= clock[actor rank] (0 = none of that actor)
+ * Queued (hist -1) and duplicate (hist -2) changes are never selected.  The selected changes are
+ * compacted on the device in history order, whatever order the log arrived in, into a cold batch
+ * (request i = document i, tables in request order, dep_off / op_first rewritten; register, object
+ * and rank ids are the document's own, so n_regs / n_objs / n_actors / flags are the document's
+ * totals) and that batch is merged from Backend.init() with the batch kernels.  The resident state
+ * is only read.  A clock that is not causally closed leaves queued changes in the result
+ * (n_queued > 0), as applyChanges would. */
+typedef struct {          /* 64 B */
+    uint64_t totals[4];   /* changes, deps, ops, registers of all requests */
+    uint32_t max_changes, max_ops, max_regs, max_objs, max_deps, doc_flags;  /* hm_batch launch hints */
+    uint32_t bad;         /* _device form: 1 a handle outside the source, 2 a change row outside its document */
+    uint32_t pad;
+} hm_past_summary;
+typedef struct {
+    uint32_t cap_changes, cap_deps, cap_ops, cap_regs;   /* rows the per-change / dep / op / register tables hold */
+    /* the gathered batch (each may be NULL) */
+    hm_doc_row    *docs;        /* [n] every range of request i */
+    hm_change_row *changes;     /* [cap_changes] */
+    hm_dep_row    *deps;        /* [cap_deps] */
+    hm_op_row     *ops;         /* [cap_ops] */
+    uint32_t      *change_log;  /* [cap_changes] log index of gathered change j (hm_doc_log's rows) */
+    uint32_t      *op_log;      /* [cap_ops] the document's log op index of gathered op k */
+    /* its merge (each may be NULL): docs / clock / back_clock / heads per request, hist / all_deps per
+     * gathered change, regs [cap_regs], surv [cap_ops]; a survivor's `op` indexes the gathered ops */
+    hm_results res;
+} hm_past_out;
+/* The count pass alone: out_counts [4n] = n_changes, n_deps, n_ops, n_regs per request, out_totals [4]
+ * their sums (either may be NULL).  HM_ERR_INVALID: a handle outside the store, both or neither
+ * selector.  No batch in flight. */
+int hm_store_past_sizes(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *hist_len,
+                        const uint32_t *clock_rows, uint32_t *out_counts, uint64_t *out_totals);
+/* Gather + merge on the engine stream, results as host tables.  out_totals [4] (optional) = rows
+ * needed per table; HM_ERR_NOMEM with out_totals filled and no other output written when one
+ * exceeds its capacity.  HM_ERR_INVALID (outputs untouched): a handle outside the store, both or
+ * neither selector; a call between submit and wait is refused.  The totals are read back once
+ * between the count and the fill pass (the merge launch is sized by them); the call synchronises
+ * once more at its end. */
+int hm_store_materialize(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *hist_len,
+                         const uint32_t *clock_rows, const hm_past_out *out, uint64_t *out_totals);
+/* The gather alone over the tables of a merged cold batch (b's docs / changes / deps / ops, r's docs /
+ * hist), everything in device memory, enqueued on `stream` (NULL = the engine's) without
+ * synchronising.  Request i = document doc_index[i] of b (NULL: document i); hist_len / clock_rows
+ * as above (device).  out's docs / changes / deps / ops / change_log / op_log are required device
+ * tables of the given capacities (out->res is not read): the gathered batch is left there for the
+ * caller's own hm_merge_device, sized by *out_summary (device; read it after synchronising).  `work`
+ * and out->ops must be 16-byte aligned (the counts and the op rows move as 16-byte words; hipMalloc
+ * memory is; HM_ERR_INVALID otherwise).  n == 0: *out_summary is zeroed and nothing else is touched
+ * (work may be NULL).  When
+ * a total exceeds its capacity nothing is gathered.  `work` = device memory of
+ * hm_materialize_work_bytes(n) bytes; afterwards its first 4n words are the per-request counts and
+ * the next 4n their offsets.  A document of b whose status is not HM_OK offers nothing. */
+size_t hm_materialize_work_bytes(uint32_t n);
+int hm_materialize_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                          const uint32_t *hist_len, const uint32_t *clock_rows, const hm_past_out *out,
+                          hm_past_summary *out_summary, void *work, void *stream);
 
 /* minimumClock row of a document (rank-indexed, 0 = absent); used for the
  * min_cmp of the next merges (Clock.cmp(DocBackend.clock, minimumClock)). */
@@ -669,6 +736,15 @@ int hm_docset_waiting(hm_docset *ds, uint32_t n, const uint32_t *docs, hm_text *
 int hm_docset_missing_changes(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off,
                               const char *actor_ids, const uint32_t *actor_off, const double *seqs,
                               uint32_t flags, hm_text **out);
+/* documents as they were (hm_store_materialize per stride class): request i = document docs[i] (may
+ * repeat) at history length hist_len[i], or at the clock given as hm_docset_missing_changes takes one
+ * (entries entry_off[i] .. entry_off[i+1]-1 of actor id strings and seqs; an id the document has
+ * never seen is dropped); exactly one of hist_len and entry_off is not NULL.  Result text = JSON array,
+ * per request {"doc": id, "clock": {actorId: seq}, "deps": {actorId: seq}, "history": history.size,
+ * "view": the document as hm_docset_view renders it} (a document not placed yet: Backend.init()). */
+int hm_docset_materialize(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len,
+                          const uint32_t *entry_off, const char *actor_ids, const uint32_t *actor_off,
+                          const double *seqs, hm_text **out);
 /* the merged document: {uuid: {"type", "keys": [[key, entry]], "elems": [[elemId, entry]]}} */
 int hm_docset_view(hm_docset *ds, uint32_t doc, hm_text **out);
 /* counters: calls, documents, class moves, net patches from the hit registers, net patches from every

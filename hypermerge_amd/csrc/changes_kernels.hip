@@ -1,9 +1,9 @@
 // changes_kernels.hip — which of a document's changes a peer lacks (Automerge 0.12 getMissingChanges /
 // getChanges / getChangesForActor), read from the resident state; no merge path is touched.
 //
-//  changes_store_kernel  one wavefront (a 64-lane workgroup) per request: a document — by handle
-//  changes_batch_kernel  through DevDoc and the store arenas / by hm_doc_row of a merged batch — and
-//                        the peer's clock as ordered (actor rank, seq) entries.
+//  changes_kernel  one wavefront (a 64-lane workgroup) per request: a document — of a resident store
+//                  or of a merged batch: doc_source.h finds its rows — and the peer's clock as
+//                  ordered (actor rank, seq) entries.
 //    locate   the lanes stride the document's change rows; an applied change (hist >= 0) that an
 //             entry names leaves its log slot in a per-rank LDS row
 //    fold     transitiveDeps: the entries in order, the lanes stride the S columns of the closure
@@ -11,8 +11,8 @@
 //             row, then the entry's own column is SET (it can lower what an earlier entry merged
 //             in: the result depends on the entries' order when the clock is not causally closed)
 //    mark     the rows stride again: an applied change with seq > closure[actor] sets the bit of its
-//             history position in an LDS bitmap tile (CTILE positions; longer histories take
-//             several tiles, each a pass over the rows)
+//             history position in an LDS bitmap tile (wave.h HistTile, CTILE positions; longer
+//             histories take several tiles, each a pass over the rows)
 //    rank     popcount prefix over the tile's words, on a running base across tiles
 //    write    one atomicAdd reserves the request's block; a marked row's log index lands at
 //             block + base + prefix + bits below its own, i.e. in history order
@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include "../../include/hypermerge_amd.h"
 #include "changes_kernels.h"
+#include "wave.h"
 
 namespace hmc {
 
@@ -32,7 +33,7 @@ struct Lds {
     uint32_t slot[HM_MAX_STRIDE];      // per rank: log slot of the applied change its entry names
     uint32_t want[HM_MAX_STRIDE];      // per rank: its entry's seq
     uint32_t listed[HM_MAX_STRIDE];    // per rank: entries that name it
-    uint32_t bits[64], pre[64];
+    HistTile<CTILE> tile;
     uint32_t err;
 };
 
@@ -99,7 +100,7 @@ __device__ __forceinline__ void changes_core(uint32_t lane, const hm_change_row 
     bool wr = false;
     if (!n_tiles && lane == 0) { range_out[0] = 0u; range_out[1] = 0u; }
     for (uint32_t t = 0; t < n_tiles; t++) {
-        L.bits[lane] = 0u;
+        L.tile.clear(lane);
         __syncthreads();
         for (uint32_t i0 = 0; i0 < n_c; i0 += 64u) {
             const uint32_t i = i0 + lane;
@@ -114,17 +115,10 @@ __device__ __forceinline__ void changes_core(uint32_t lane, const hm_change_row 
                 }
             }
             if (t == 0) count += (uint32_t)__popcll(__ballot(miss));
-            if (miss && p / CTILE == t) atomicOr(&L.bits[(p % CTILE) >> 5], 1u << (p & 31u));
+            if (miss && p / CTILE == t) L.tile.mark(p);
         }
         __syncthreads();
-        const uint32_t w = L.bits[lane], c1 = (uint32_t)__popc(w);
-        uint32_t incl = c1;
-        for (uint32_t d = 1; d < 64u; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
-        L.pre[lane] = incl - c1;
-        const uint32_t tile_n = __shfl(incl, 63);
+        const uint32_t tile_n = L.tile.rank(lane);
         if (t == 0) {
             if (lane == 0) {
                 if (count) off = atomicAdd(total, count);
@@ -138,10 +132,9 @@ __device__ __forceinline__ void changes_core(uint32_t lane, const hm_change_row 
             for (uint32_t i = lane; i < n_c; i += 64u) {
                 const int32_t hp = hist[i];
                 if (hp < 0 || (uint32_t)hp >= n_c || (uint32_t)hp / CTILE != t) continue;
-                const uint32_t b = (uint32_t)hp % CTILE, wd = L.bits[b >> 5], bit = 1u << (b & 31u);
-                if (!(wd & bit)) continue;
-                const uint32_t k = base + L.pre[b >> 5] + (uint32_t)__popc(wd & (bit - 1u));
-                if (k < count) out_log[off + k] = i;
+                uint32_t k;
+                if (!L.tile.slot((uint32_t)hp, k)) continue;
+                if (base + k < count) out_log[off + base + k] = i;
             }
         }
         base += tile_n;
@@ -149,53 +142,22 @@ __device__ __forceinline__ void changes_core(uint32_t lane, const hm_change_row 
     }
 }
 
-// the request's entries, checked against the entry tables' length
-__device__ __forceinline__ bool entries_of(const ChangesArgs &A, unsigned long long q, uint32_t lane, uint32_t &e0, uint32_t &n_e) {
-    e0 = A.entry_off[q];
-    const uint32_t e1 = A.entry_off[q + 1];
-    if (e1 < e0 || e1 > A.n_entries) {
-        if (lane == 0) { atomicOr(A.bad, HM_MC_BAD_ENTRIES); A.out_range[2 * q] = 0u; A.out_range[2 * q + 1] = 0u; }
-        return false;
-    }
-    n_e = e1 - e0;
-    return true;
-}
-
-__global__ __launch_bounds__(CWG) void changes_store_kernel(ChangesArgs A) {
+__global__ __launch_bounds__(CWG) void changes_kernel(ChangesArgs A) {
     __shared__ Lds L;
     const uint32_t lane = threadIdx.x;
-    const uint32_t S = A.S;
+    const DocSource &D = A.src;
+    const uint32_t S = D.S;
     for (unsigned long long q = blockIdx.x; q < A.n; q += gridDim.x) {
-        const uint32_t h = A.handles[q];
-        if (h >= A.n_handles) {
-            if (lane == 0) { atomicOr(A.bad, HM_MC_BAD_HANDLE); A.out_range[2 * q] = 0u; A.out_range[2 * q + 1] = 0u; }
+        const DocRef m = doc_of(D, q);
+        // the request's entries, checked against the entry tables' length
+        const uint32_t e0 = A.entry_off[q], e1 = A.entry_off[q + 1];
+        const uint32_t b = m.bad ? HM_MC_BAD_HANDLE : e1 < e0 || e1 > A.n_entries ? HM_MC_BAD_ENTRIES : 0u;
+        if (b) {
+            if (lane == 0) { atomicOr(A.bad, b); A.out_range[2 * q] = 0u; A.out_range[2 * q + 1] = 0u; }
             continue;
         }
-        uint32_t e0, n_e;
-        if (!entries_of(A, q, lane, e0, n_e)) continue;
-        const DevDoc m = A.dm[h];
-        uint32_t c_off = m.c_off, n_c = m.n_c;
-        if ((unsigned long long)c_off + n_c > A.lim_c) { c_off = 0; n_c = 0; }
-        changes_core(lane, A.changes + c_off, A.hist + c_off, A.all_deps + (size_t)c_off * S, n_c, S, A.entry_actor + e0,
-                     A.entry_seq + e0, n_e, A.flags, L, A.out_closure ? A.out_closure + q * S : nullptr, A.out_range + 2 * q,
-                     A.out_log, A.cap, A.total, A.bad);
-    }
-}
-
-__global__ __launch_bounds__(CWG) void changes_batch_kernel(ChangesArgs A) {
-    __shared__ Lds L;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t S = A.S;
-    for (unsigned long long d = blockIdx.x; d < A.n; d += gridDim.x) {
-        uint32_t e0, n_e;
-        if (!entries_of(A, d, lane, e0, n_e)) continue;
-        uint32_t c_off = 0, n_c = 0;
-        if (A.res[d].status == HM_OK) {                        // (a document whose merge threw has no changes to offer)
-            c_off = A.docs[d].change_off; n_c = A.docs[d].n_changes;
-            if ((unsigned long long)c_off + n_c > A.lim_c) { c_off = 0; n_c = 0; }
-        }
-        changes_core(lane, A.changes + c_off, A.hist + c_off, A.all_deps + (size_t)c_off * S, n_c, S, A.entry_actor + e0,
-                     A.entry_seq + e0, n_e, A.flags, L, A.out_closure ? A.out_closure + d * S : nullptr, A.out_range + 2 * d,
+        changes_core(lane, D.changes + m.c_off, D.hist + m.c_off, D.all_deps + (size_t)m.c_off * S, m.n_c, S, A.entry_actor + e0,
+                     A.entry_seq + e0, e1 - e0, A.flags, L, A.out_closure ? A.out_closure + q * S : nullptr, A.out_range + 2 * q,
                      A.out_log, A.cap, A.total, A.bad);
     }
 }
@@ -204,8 +166,6 @@ __global__ __launch_bounds__(CWG) void changes_batch_kernel(ChangesArgs A) {
 
 hipError_t hm_launch_missing_changes(const ChangesArgs &a, hipStream_t s) {
     if (!a.n) return hipSuccess;
-    const dim3 grid(a.n < 65535u ? a.n : 65535u);
-    if (a.handles) hipLaunchKernelGGL(hmc::changes_store_kernel, grid, dim3(CWG), 0, s, a);
-    else hipLaunchKernelGGL(hmc::changes_batch_kernel, grid, dim3(CWG), 0, s, a);
+    hipLaunchKernelGGL(hmc::changes_kernel, dim3(a.n < 65535u ? a.n : 65535u), dim3(CWG), 0, s, a);
     return hipGetLastError();
 }

@@ -409,6 +409,24 @@ static int check_waiting_batch(hm_engine *e, const hm_batch *b) {
     return HM_OK;
 }
 
+// a merged cold batch (device tables of b, device results r) as the device queries' document
+// source; request i is document i unless the caller sets handles
+static DocSource batch_source(const hm_batch *b, const hm_results *r) {
+    DocSource D = {};
+    D.docs = b->docs; D.res = r->docs; D.n_docs = b->n_docs; D.S = b->a_stride;
+    D.changes = b->changes; D.hist = r->hist; D.all_deps = r->all_deps; D.deps = b->deps; D.ops = b->ops;
+    D.clock = r->clock; D.back_clock = r->back_clock;
+    D.lim_c = b->n_changes; D.lim_d = b->n_deps; D.lim_o = b->n_ops;
+    return D;
+}
+
+// the missing row of every document of the batch ([n_docs * a_stride])
+static hipError_t launch_waiting_batch(const hm_batch *b, const hm_results *r, uint32_t *out_missing, hipStream_t s) {
+    WaitingArgs A = {};
+    A.n = b->n_docs; A.src = batch_source(b, r); A.out_missing = out_missing;
+    return hm_launch_waiting(A, s);
+}
+
 int hm_missing_deps_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t *out_missing, void *stream) {
     try {
         if (!e || !r) return HM_ERR_INVALID;
@@ -418,8 +436,8 @@ int hm_missing_deps_device(hm_engine *e, const hm_batch *b, const hm_results *r,
         if (!out_missing || !r->docs || !r->clock || (b->n_changes && !r->hist))
             return fail(e, HM_ERR_INVALID, "hm_missing_deps needs the results' docs, clock and hist tables");
         HIPCHK(e, hipSetDevice(e->device));
-        hipError_t hr = hm_launch_waiting_batch(b, r, out_missing, stream ? (hipStream_t)stream : e->stream);
-        return hr == hipSuccess ? HM_OK : hip_fail(e, hr, "waiting_batch_kernel launch");
+        hipError_t hr = launch_waiting_batch(b, r, out_missing, stream ? (hipStream_t)stream : e->stream);
+        return hr == hipSuccess ? HM_OK : hip_fail(e, hr, "waiting_kernel launch");
     } catch (...) {
         return fail(e, HM_ERR_DEVICE, "exception in hm_missing_deps_device");
     }
@@ -452,7 +470,7 @@ int hm_missing_deps_host(hm_engine *e, const hm_batch *hb, const hm_results *hr,
         hipError_t r = hipSuccess;
         for (int i = 0; i < 6 && r == hipSuccess; i++)
             if (sz[i]) r = hipMemcpyAsync(base + off[i], src[i], sz[i], hipMemcpyHostToDevice, s);
-        if (r == hipSuccess) r = hm_launch_waiting_batch(&b, &d, (uint32_t *)(base + off[6]), s);
+        if (r == hipSuccess) r = launch_waiting_batch(&b, &d, (uint32_t *)(base + off[6]), s);
         if (r == hipSuccess) r = hipMemcpyAsync(out_missing, base + off[6], sz[6], hipMemcpyDeviceToHost, s);
         if (r == hipSuccess) r = hipStreamSynchronize(s);
         (void)hipFree(base);
@@ -467,8 +485,7 @@ static ChangesArgs changes_batch_args(const hm_batch *b, const hm_results *r, co
                                       uint32_t flags, uint32_t *out_closure, uint32_t *out_range, uint32_t *out_log,
                                       uint32_t cap, uint32_t *total, uint32_t *bad) {
     ChangesArgs A = {};
-    A.n = b->n_docs; A.docs = b->docs; A.res = r->docs; A.n_docs = b->n_docs; A.S = b->a_stride;
-    A.changes = b->changes; A.hist = r->hist; A.all_deps = r->all_deps; A.lim_c = b->n_changes;
+    A.n = b->n_docs; A.src = batch_source(b, r);
     A.entry_off = entry_off; A.entry_actor = entry_actor; A.entry_seq = entry_seq; A.n_entries = n_entries; A.flags = flags;
     A.out_closure = out_closure; A.out_range = out_range; A.out_log = out_log; A.cap = cap; A.total = total; A.bad = bad;
     return A;
@@ -492,7 +509,7 @@ int hm_missing_changes_device(hm_engine *e, const hm_batch *b, const hm_results 
         const ChangesArgs A = changes_batch_args(b, r, entry_off, entry_actor, entry_seq, n_entries, flags, out_closure, out_range,
                                                  out_log_index, cap, out_total, out_bad);
         hipError_t hr = hm_launch_missing_changes(A, stream ? (hipStream_t)stream : e->stream);
-        return hr == hipSuccess ? HM_OK : hip_fail(e, hr, "changes_batch_kernel launch");
+        return hr == hipSuccess ? HM_OK : hip_fail(e, hr, "changes_kernel launch");
     } catch (...) {
         return fail(e, HM_ERR_DEVICE, "exception in hm_missing_changes_device");
     }
@@ -522,9 +539,7 @@ int hm_materialize_device(hm_engine *e, const hm_batch *b, const hm_results *r, 
         HIPCHK(e, hipSetDevice(e->device));
         hipStream_t s = stream ? (hipStream_t)stream : e->stream;
         PastArgs A = {};
-        A.n = n; A.handles = doc_index; A.docs = b->docs; A.res = r->docs; A.n_docs = b->n_docs; A.S = b->a_stride;
-        A.changes = b->changes; A.hist = r->hist; A.deps = b->deps; A.ops = b->ops;
-        A.lim_c = b->n_changes; A.lim_d = b->n_deps; A.lim_o = b->n_ops;
+        A.n = n; A.src = batch_source(b, r); A.src.handles = doc_index;
         A.hist_len = hist_len; A.clock_rows = clock_rows;
         A.cnt = (uint32_t *)work; A.off = A.cnt + 4 * (size_t)n; A.aux = A.off + 4 * (size_t)n;
         A.part = (unsigned long long *)((char *)work + ((((size_t)n * 40) + 255) & ~(size_t)255));

@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/hypermerge_amd.h"
-#include "store_kernels.h"
+#include "doc_source.h"
 
 // history positions per bitmap tile of the fill pass (a longer selection takes several tiles, each
 // a pass over the document's hist rows); the wave strides the rows 64 at a time
@@ -29,29 +29,16 @@ inline uint32_t hm_past_scan_chunks(uint32_t n) { return (uint32_t)(((unsigned l
 //          the dep and op rows, out_change_log[j] = document-local log index of gathered change j,
 //          out_op_log[k] = document-local log op index of gathered op k
 //
-// The source is a resident store (dm, handles checked against n_handles) or a merged cold batch
-// (docs / res; handles = document indices, NULL = request i is document i; a document whose merge
-// threw offers nothing).  A handle outside the source sets HM_PAST_BAD_HANDLE in sum->bad and gets
-// empty ranges; a change row whose dep / op range leaves its document's segment sets
-// HM_PAST_BAD_ROWS and is gathered without those rows.  lim_*: rows of the source tables; no row
-// past them is read.
+// The documents come from src (doc_source.h; it reads changes, hist, deps and ops).  A handle
+// outside the source sets HM_PAST_BAD_HANDLE in sum->bad and gets empty ranges; a change row whose
+// dep / op range leaves its document's segment sets HM_PAST_BAD_ROWS and is gathered without those
+// rows.
 #define HM_PAST_BAD_HANDLE 1u
 #define HM_PAST_BAD_ROWS 2u
 
 struct PastArgs {
     uint32_t n;
-    const uint32_t *handles;
-    const DevDoc *dm;                          // resident store ...
-    uint32_t n_handles;
-    const hm_doc_row *docs;                    // ... or a merged cold batch
-    const hm_doc_result *res;
-    uint32_t n_docs;
-    uint32_t S;
-    const hm_change_row *changes;
-    const int32_t *hist;
-    const hm_dep_row *deps;
-    const hm_op_row *ops;
-    unsigned long long lim_c, lim_d, lim_o;
+    DocSource src;
     const uint32_t *hist_len;                  // [n] or NULL
     const uint32_t *clock_rows;                // [n * S] or NULL
     uint32_t *cnt, *aux, *off;                 // [4n], [2n], [4n]

@@ -22,63 +22,43 @@
 //             change by binary search over the slots' op offsets and moves the 32-byte row as two
 //             16-byte words, so the stores are contiguous and the loads contiguous within a change
 //
-// Nothing inside a row is remapped: register, object and rank ids are the document's own.
+// Nothing inside a row is remapped: register, object and rank ids are the document's own.  The
+// request's document comes from doc_source.h; the bitmap tile and the wave scans are wave.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/hypermerge_amd.h"
 #include "past_kernels.h"
+#include "wave.h"
 
 namespace hmp {
 
 #define PWG 64
 #define PTILE HM_PAST_TILE
-#define PWORDS (PTILE / 32u)
-static_assert(PWORDS <= 64u && PTILE % 64u == 0u, "a tile's bitmap words fit one per lane");
 static_assert(sizeof(hm_op_row) == 32 && sizeof(hm_change_row) == 24 && sizeof(hm_doc_row) == 48, "row sizes");
 
-// the request's source document: its segments (clamped to the tables), totals and selector
-struct Src {
-    uint32_t c_off, n_c, d_off, n_d, o_off, n_o, n_r, n_objs, n_actors, flags;
+// the request's source document and its selector
+struct Src : DocRef {
     uint32_t npre;                             // prefix selector (clock selector: unused)
     const uint32_t *clk;                       // clock selector's row, or NULL
-    bool bad;
 };
 
 __device__ __forceinline__ Src source_of(const PastArgs &A, unsigned long long q) {
-    Src s = {};
-    s.n_objs = 1u;                             // (ROOT: an empty document)
-    const uint32_t h = A.handles ? A.handles[q] : (uint32_t)q;
-    if (A.dm) {
-        if (h >= A.n_handles) { s.bad = true; return s; }
-        const DevDoc m = A.dm[h];
-        s.c_off = m.c_off; s.n_c = m.n_c; s.d_off = m.d_off; s.n_d = m.n_d; s.o_off = m.o_off; s.n_o = m.n_o;
-        s.n_r = m.n_r; s.n_objs = m.n_objs; s.n_actors = m.n_actors; s.flags = m.flags;
-    } else {
-        if (h >= A.n_docs) { s.bad = true; return s; }
-        const hm_doc_row r = A.docs[h];
-        s.n_r = r.n_regs; s.n_objs = r.n_objs; s.n_actors = r.n_actors; s.flags = r.flags;
-        if (A.res[h].status == HM_OK) {        // (a document whose merge threw has no history)
-            s.c_off = r.change_off; s.n_c = r.n_changes; s.d_off = r.dep_off; s.n_d = r.n_deps;
-            s.o_off = r.op_off; s.n_o = r.n_ops;
-        }
-    }
-    if ((unsigned long long)s.c_off + s.n_c > A.lim_c) { s.c_off = 0; s.n_c = 0; }
-    if ((unsigned long long)s.d_off + s.n_d > A.lim_d) { s.d_off = 0; s.n_d = 0; }
-    if ((unsigned long long)s.o_off + s.n_o > A.lim_o) { s.o_off = 0; s.n_o = 0; }
+    Src s;
+    static_cast<DocRef &>(s) = doc_of(A.src, q);
     s.npre = A.hist_len ? A.hist_len[q] : 0u;
-    s.clk = A.clock_rows ? A.clock_rows + q * A.S : nullptr;
+    s.clk = A.clock_rows ? A.clock_rows + q * A.src.S : nullptr;
     return s;
 }
 
 // is log row i selected?  p = its history position
 __device__ __forceinline__ bool selected(const Src &s, const PastArgs &A, uint32_t i, uint32_t &p) {
-    const int32_t hp = A.hist[s.c_off + i];
+    const int32_t hp = A.src.hist[s.c_off + i];
     if (hp < 0 || (uint32_t)hp >= s.n_c) return false;
     p = (uint32_t)hp;
     if (!s.clk) return p < s.npre;
-    const hm_change_row *c = A.changes + s.c_off + i;
+    const hm_change_row *c = A.src.changes + s.c_off + i;
     const uint32_t a = c->actor;
-    return a < A.S && c->seq <= s.clk[a];
+    return a < A.src.S && c->seq <= s.clk[a];
 }
 
 // the change's dep / op rows, none where the range leaves the document's segment
@@ -88,11 +68,6 @@ __device__ __forceinline__ bool rows_of(const Src &s, const hm_change_row &c, ui
     if (nd && (c.dep_off < s.d_off || (unsigned long long)c.dep_off + nd > (unsigned long long)s.d_off + s.n_d)) { nd = 0; ok = false; }
     if (no && (c.op_first < s.o_off || (unsigned long long)c.op_first + no > (unsigned long long)s.o_off + s.n_o)) { no = 0; ok = false; }
     return ok;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (uint32_t d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 #define PCWG 256
@@ -107,7 +82,7 @@ __global__ __launch_bounds__(PCWG) void past_count_kernel(PastArgs A) {
             uint32_t p;
             if (!selected(s, A, i, p)) continue;
             uint32_t d, o;
-            ok &= rows_of(s, A.changes[s.c_off + i], d, o);
+            ok &= rows_of(s, A.src.changes[s.c_off + i], d, o);
             nc++; nd += d; no += o;
         }
         nc = wave_sum(nc); nd = wave_sum(nd); no = wave_sum(no);
@@ -162,11 +137,7 @@ __global__ __launch_bounds__(PSWG) void past_scan_kernel(PastArgs A) {
     }
     const unsigned long long own[4] = {in[0], in[1], in[2], in[3]};
 #pragma unroll
-    for (int k = 0; k < 4; k++)
-        for (uint32_t d = 1; d < 64u; d <<= 1) {
-            const unsigned long long up = __shfl_up(in[k], d);
-            if (lane >= d) in[k] += up;
-        }
+    for (int k = 0; k < 4; k++) in[k] = wave_incl_scan(in[k], lane);
     if (lane == 63u)
         for (int k = 0; k < 4; k++) s_w[wv][k] = in[k];
     __syncthreads();                                           // (s_w, and the chunk's base in s_carry)
@@ -210,8 +181,8 @@ __global__ __launch_bounds__(PSWG) void past_scan_kernel(PastArgs A) {
 }
 
 struct Lds {
-    uint32_t bits[64], pre[64];
-    uint32_t src[PTILE];                       // per slot: the change's log row (document-local)
+    HistTile<PTILE> tile;
+    uint32_t src[PTILE];                      // per slot: the change's log row (document-local)
     uint32_t dp[PTILE], op[PTILE];             // per slot: dep / op rows, then their offsets within the tile
     uint32_t of[PTILE];                        // per slot: the change's first source op row
 };
@@ -219,8 +190,9 @@ struct Lds {
 __global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
     __shared__ Lds L;
     const uint32_t lane = threadIdx.x;
+    const DocSource &D = A.src;
     {
-        const hm_past_summary *t = A.sum;                      // (one decision for the whole grid)
+        const hm_past_summary *t = A.sum;                     // (one decision for the whole grid)
         if (t->totals[0] > A.cap[0]) return;
         if (!A.log_only && (t->totals[1] > A.cap[1] || t->totals[2] > A.cap[2] || t->totals[3] > A.cap[3])) return;
     }
@@ -238,30 +210,22 @@ __global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
         const uint32_t n_tiles = (s.n_c + PTILE - 1u) / PTILE;
         uint32_t base = 0, dbase = 0, obase = 0;               // changes / deps / ops gathered by the earlier tiles
         for (uint32_t t = 0; t < n_tiles && base < cn.x; t++) {
-            L.bits[lane] = 0u;
+            L.tile.clear(lane);
             __syncthreads();
             for (uint32_t i = lane; i < s.n_c; i += 64u) {     // mark
                 uint32_t p;
-                if (selected(s, A, i, p) && p / PTILE == t) atomicOr(&L.bits[(p % PTILE) >> 5], 1u << (p & 31u));
+                if (selected(s, A, i, p) && p / PTILE == t) L.tile.mark(p);
             }
             __syncthreads();
-            const uint32_t w = L.bits[lane], c1 = (uint32_t)__popc(w);   // rank
-            uint32_t incl = c1;
-            for (uint32_t d = 1; d < 64u; d <<= 1) {
-                const uint32_t up = __shfl_up(incl, d);
-                if (lane >= d) incl += up;
-            }
-            L.pre[lane] = incl - c1;
-            const uint32_t tile_n = __shfl(incl, 63);
+            const uint32_t tile_n = L.tile.rank(lane);         // rank
             __syncthreads();
             if (!tile_n) continue;
             for (uint32_t i = lane; i < s.n_c; i += 64u) {     // scatter
-                const int32_t hp = A.hist[s.c_off + i];
+                const int32_t hp = D.hist[s.c_off + i];
                 if (hp < 0 || (uint32_t)hp >= s.n_c || (uint32_t)hp / PTILE != t) continue;
-                const uint32_t b = (uint32_t)hp % PTILE, wd = L.bits[b >> 5], bit = 1u << (b & 31u);
-                if (!(wd & bit)) continue;
-                const uint32_t k = L.pre[b >> 5] + (uint32_t)__popc(wd & (bit - 1u));
-                const hm_change_row c = A.changes[s.c_off + i];
+                uint32_t k;
+                if (!L.tile.slot((uint32_t)hp, k)) continue;
+                const hm_change_row c = D.changes[s.c_off + i];
                 uint32_t nd, no;
                 rows_of(s, c, nd, no);
                 L.src[k] = i; L.dp[k] = nd; L.op[k] = no; L.of[k] = c.op_first;
@@ -271,11 +235,7 @@ __global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
             for (uint32_t k0 = 0; k0 < tile_n; k0 += 64u) {
                 const uint32_t k = k0 + lane;
                 const uint32_t vd = k < tile_n ? L.dp[k] : 0u, vo = k < tile_n ? L.op[k] : 0u;
-                uint32_t id = vd, io = vo;
-                for (uint32_t d = 1; d < 64u; d <<= 1) {
-                    const uint32_t ud = __shfl_up(id, d), uo = __shfl_up(io, d);
-                    if (lane >= d) { id += ud; io += uo; }
-                }
+                const uint32_t id = wave_incl_scan(vd, lane), io = wave_incl_scan(vo, lane);
                 if (k < tile_n) { L.dp[k] = dsum + id - vd; L.op[k] = osum + io - vo; }
                 dsum += __shfl(id, 63); osum += __shfl(io, 63);
             }
@@ -286,7 +246,7 @@ __global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
                 const uint32_t i = L.src[k];
                 A.out_change_log[of.x + j] = i;
                 if (A.log_only) continue;
-                hm_change_row c = A.changes[s.c_off + i];
+                hm_change_row c = D.changes[s.c_off + i];
                 uint32_t nd, no;
                 rows_of(s, c, nd, no);
                 const uint32_t d0 = dbase + L.dp[k], src_d = c.dep_off;
@@ -294,7 +254,7 @@ __global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
                 c.n_deps = (uint16_t)nd; c.n_ops = no;
                 c.dep_off = of.y + d0; c.op_first = of.z + obase + L.op[k];
                 A.out_changes[of.x + j] = c;
-                for (uint32_t x = 0; x < nd; x++) A.out_deps[of.y + d0 + x] = A.deps[src_d + x];
+                for (uint32_t x = 0; x < nd; x++) A.out_deps[of.y + d0 + x] = D.deps[src_d + x];
             }
             for (uint32_t k = lane; k < (A.log_only ? 0u : osum); k += 64u) {   // write: the tile's op rows, a lane per output row
                 uint32_t lo = 0, hi = tile_n;                  // the last slot whose op offset is <= k
@@ -305,7 +265,7 @@ __global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
                 const uint32_t o = obase + k;
                 if (o >= cn.z) continue;
                 const uint32_t srow = L.of[lo] + (k - L.op[lo]);
-                const uint4 *sp = (const uint4 *)(A.ops + srow);
+                const uint4 *sp = (const uint4 *)(D.ops + srow);
                 uint4 *dp = (uint4 *)(A.out_ops + of.z + o);
                 const uint4 x0 = sp[0], x1 = sp[1];
                 dp[0] = x0; dp[1] = x1;

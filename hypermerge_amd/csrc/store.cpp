@@ -1019,6 +1019,16 @@ int hm_store_blocked(hm_store *s, uint32_t *out_handles, uint32_t cap, uint32_t 
     }
 }
 
+// the store as the device queries' document source; the caller sets handles (staged, device)
+static DocSource store_source(const hm_store *s) {
+    DocSource D = {};
+    D.dm = s->dm; D.n_handles = s->n_handles; D.S = s->S;
+    D.changes = s->changes; D.hist = s->hist; D.all_deps = s->all_deps; D.deps = s->deps; D.ops = s->ops;
+    D.clock = s->clock; D.back_clock = s->back_clock; D.min_clock = s->min_clock;
+    D.lim_c = s->cap_c; D.lim_d = s->cap_d; D.lim_o = s->cap_o;
+    return D;
+}
+
 // hm_store_waiting / hm_store_read_queue: one launch of the waiting pass over the staged requests
 static int waiting_impl(hm_store *s, uint32_t n, const uint32_t *doc_handles, uint32_t *out_missing, uint32_t *out_unmet,
                         uint32_t *out_nq, const uint32_t *q_off, uint32_t *out_queue) {
@@ -1037,9 +1047,7 @@ static int waiting_impl(hm_store *s, uint32_t n, const uint32_t *doc_handles, ui
     if (q_off) SCHK(s, hipMemcpyAsync(sp + o_off, q_off, 4 * ((size_t)n + 1), hipMemcpyHostToDevice, st));
     SCHK(s, hipMemsetAsync(sp + o_bad, 0, 4, st));
     WaitingArgs A;
-    A.n = n; A.handles = (const uint32_t *)(sp + o_h); A.dm = s->dm; A.n_handles = s->n_handles; A.S = S;
-    A.changes = s->changes; A.deps = s->deps; A.lim_c = s->cap_c; A.lim_d = s->cap_d; A.hist = s->hist;
-    A.clock = s->clock; A.back_clock = s->back_clock; A.min_clock = s->min_clock;
+    A.n = n; A.src = store_source(s); A.src.handles = (const uint32_t *)(sp + o_h);
     A.out_missing = out_missing ? (uint32_t *)(sp + o_miss) : nullptr;
     A.out_unmet = out_unmet ? (uint32_t *)(sp + o_unmet) : nullptr;
     A.out_nq = out_nq ? (uint32_t *)(sp + o_nq) : nullptr;
@@ -1050,8 +1058,8 @@ static int waiting_impl(hm_store *s, uint32_t n, const uint32_t *doc_handles, ui
     SCHK(s, hipMemcpyAsync(&s->h_cnt[7], sp + o_bad, 4, hipMemcpyDeviceToHost, st));
     SCHK(s, hipStreamSynchronize(st));
     const uint32_t bad = s->h_cnt[7];
-    if (bad & 1) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad handle");
-    if (bad & 2) return hm_engine_fail(s->e, HM_ERR_INVALID, "out_off does not match the documents' queue lengths");
+    if (bad & HM_WAIT_BAD_HANDLE) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad handle");
+    if (bad & HM_WAIT_BAD_QUEUE) return hm_engine_fail(s->e, HM_ERR_INVALID, "out_off does not match the documents' queue lengths");
     if (out_missing) SCHK(s, hipMemcpyAsync(out_missing, sp + o_miss, 4 * (size_t)n * S, hipMemcpyDeviceToHost, st));
     if (out_unmet) SCHK(s, hipMemcpyAsync(out_unmet, sp + o_unmet, 4 * (size_t)n * S, hipMemcpyDeviceToHost, st));
     if (out_nq) SCHK(s, hipMemcpyAsync(out_nq, sp + o_nq, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
@@ -1123,8 +1131,7 @@ int hm_store_missing_changes(hm_store *s, uint32_t n, const uint32_t *doc_handle
             SCHK(s, hipMemcpyAsync(sp + o_es, entry_seq, 4 * (size_t)ne, hipMemcpyHostToDevice, st));
         }
         ChangesArgs A = {};
-        A.n = n; A.handles = (const uint32_t *)(sp + o_h); A.dm = s->dm; A.n_handles = s->n_handles; A.S = S;
-        A.changes = s->changes; A.hist = s->hist; A.all_deps = s->all_deps; A.lim_c = s->cap_c;
+        A.n = n; A.src = store_source(s); A.src.handles = (const uint32_t *)(sp + o_h);
         A.entry_off = (const uint32_t *)(sp + o_off); A.entry_actor = (const uint16_t *)(sp + o_ea);
         A.entry_seq = (const uint32_t *)(sp + o_es); A.n_entries = ne; A.flags = flags;
         A.out_closure = out_closure ? (uint32_t *)(sp + o_cl) : nullptr;
@@ -1169,9 +1176,7 @@ static int past_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, cons
     SCHK(s, hipMemcpyAsync(sp + o_h, doc_handles, 4 * (size_t)n, hipMemcpyHostToDevice, st));
     SCHK(s, hipMemcpyAsync(sp + o_sel, hist_len ? hist_len : clock_rows, sel_b, hipMemcpyHostToDevice, st));
     P = PastArgs{};
-    P.n = n; P.handles = (const uint32_t *)(sp + o_h); P.dm = s->dm; P.n_handles = s->n_handles; P.S = S;
-    P.changes = s->changes; P.hist = s->hist; P.deps = s->deps; P.ops = s->ops;
-    P.lim_c = s->cap_c; P.lim_d = s->cap_d; P.lim_o = s->cap_o;
+    P.n = n; P.src = store_source(s); P.src.handles = (const uint32_t *)(sp + o_h);
     if (hist_len) P.hist_len = (const uint32_t *)(sp + o_sel); else P.clock_rows = (const uint32_t *)(sp + o_sel);
     P.cnt = (uint32_t *)(sp + o_cnt); P.off = (uint32_t *)(sp + o_off); P.aux = (uint32_t *)(sp + o_aux);
     P.part = (unsigned long long *)(sp + o_part);

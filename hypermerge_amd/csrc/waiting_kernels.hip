@@ -4,9 +4,9 @@
 //  blocked_kernel        grid-stride sweep over every handle's result row: the handles whose
 //                        opSet.queue is not empty (n_queued != 0), compacted with a wave ballot and
 //                        one atomicAdd per wave that found any.
-//  waiting_store_kernel  one wavefront per requested document (by handle, through DevDoc and the
-//  waiting_batch_kernel  store arenas / by hm_doc_row of a merged batch): the lanes stride the
-//                        document's history positions; a queued change (hist == -1) walks its dep rows
+//  waiting_kernel        one wavefront per requested document (of a resident store or of a merged
+//                        batch: doc_source.h finds its rows): the lanes stride the document's
+//                        history positions; a queued change (hist == -1) walks its dep rows
 //                        and raises, per actor, the largest seq opSet.clock has not reached — the
 //                        deps.set(actor, seq - 1) rule of causallyReady — in a per-wave LDS row; the
 //                        queue's log indices come out ascending (ballot prefix counts on a running base).
@@ -82,65 +82,40 @@ __device__ __forceinline__ uint32_t waiting_core(uint32_t lane, const hm_change_
     return base;
 }
 
-__global__ __launch_bounds__(WWG) void waiting_store_kernel(WaitingArgs A) {
+__global__ __launch_bounds__(WWG) void waiting_kernel(WaitingArgs A) {
     __shared__ uint32_t lds[WWAVES][HM_MAX_STRIDE];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t S = A.S;
+    const DocSource &D = A.src;
+    const uint32_t S = D.S;
     for (unsigned long long q0 = (unsigned long long)blockIdx.x * WWAVES; q0 < A.n; q0 += (unsigned long long)gridDim.x * WWAVES) {
         const unsigned long long q = q0 + wave;
         bool live = q < A.n;
-        uint32_t h = 0;
+        DocRef m = {};
         if (live) {
-            h = A.handles[q];
-            if (h >= A.n_handles) { if (lane == 0) atomicOr(A.bad, 1u); live = false; }
+            m = doc_of(D, q);
+            if (m.bad) { if (lane == 0 && A.bad) atomicOr(A.bad, HM_WAIT_BAD_HANDLE); live = false; }
         }
-        DevDoc m = {};
-        if (live) m = A.dm[h];
-        uint32_t n_c = m.n_c;
-        if ((unsigned long long)m.c_off + n_c > A.lim_c) n_c = 0;
         uint32_t q_at = 0, q_cap = 0;
         if (live && A.q_off) { q_at = A.q_off[q]; q_cap = A.q_off[q + 1] - q_at; }
         const bool rows = A.out_missing != nullptr;
-        const uint32_t nq = waiting_core(lane, A.changes + m.c_off, A.hist + m.c_off, n_c, A.deps, A.lim_d,
-                                         A.clock + (size_t)h * S, S, lds[wave], rows,
+        const uint32_t nq = waiting_core(lane, D.changes + m.c_off, D.hist + m.c_off, m.n_c, D.deps, D.lim_d,
+                                         D.clock + (size_t)m.index * S, S, lds[wave], rows,
                                          live && A.q_off ? A.out_queue + q_at : nullptr, q_cap);
         if (!live) continue;
-        if (A.q_off && nq != q_cap && lane == 0) atomicOr(A.bad, 2u);
+        if (A.q_off && nq != q_cap && lane == 0) atomicOr(A.bad, HM_WAIT_BAD_QUEUE);
         if (A.out_nq && lane == 0) A.out_nq[q] = nq;
-        const bool minc = (m.pad[0] & HM_DDOC_MINC) != 0;
+        const bool minc = (m.bits & HM_DDOC_MINC) != 0;
         for (uint32_t a = lane; a < S; a += 64u) {
             if (rows) A.out_missing[q * S + a] = lds[wave][a];
             if (A.out_unmet) {
                 uint32_t u = 0;
                 if (minc) {
-                    const uint32_t want = A.min_clock[(size_t)h * S + a];
-                    if (A.back_clock[(size_t)h * S + a] < want) u = want;
+                    const uint32_t want = D.min_clock[(size_t)m.index * S + a];
+                    if (D.back_clock[(size_t)m.index * S + a] < want) u = want;
                 }
                 A.out_unmet[q * S + a] = u;
             }
         }
-    }
-}
-
-__global__ __launch_bounds__(WWG) void waiting_batch_kernel(const hm_doc_row *docs, uint32_t n_docs, const hm_change_row *changes,
-                                                             const hm_dep_row *deps, unsigned long long lim_c,
-                                                             unsigned long long lim_d, const hm_doc_result *res,
-                                                             const int32_t *hist, const uint32_t *clock, uint32_t S,
-                                                             uint32_t *out_missing) {
-    __shared__ uint32_t lds[WWAVES][HM_MAX_STRIDE];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (unsigned long long d0 = (unsigned long long)blockIdx.x * WWAVES; d0 < n_docs; d0 += (unsigned long long)gridDim.x * WWAVES) {
-        const unsigned long long d = d0 + wave;
-        const bool live = d < n_docs;
-        uint32_t c_off = 0, n_c = 0;
-        if (live && res[d].status == HM_OK) {
-            c_off = docs[d].change_off; n_c = docs[d].n_changes;
-            if ((unsigned long long)c_off + n_c > lim_c) { c_off = 0; n_c = 0; }
-        }
-        waiting_core(lane, changes + c_off, hist + c_off, n_c, deps, lim_d, clock + (live ? d : 0) * S, S, lds[wave], true,
-                     nullptr, 0);
-        if (!live) continue;
-        for (uint32_t a = lane; a < S; a += 64u) out_missing[d * S + a] = lds[wave][a];
     }
 }
 
@@ -158,15 +133,6 @@ hipError_t hm_launch_blocked(const hm_doc_result *res_docs, uint32_t n_handles, 
 hipError_t hm_launch_waiting(const WaitingArgs &a, hipStream_t s) {
     if (!a.n) return hipSuccess;
     const uint32_t need = (a.n + WWAVES - 1) / WWAVES;
-    hipLaunchKernelGGL(hmw::waiting_store_kernel, dim3(need < 4096u ? need : 4096u), dim3(WWG), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t hm_launch_waiting_batch(const hm_batch *b, const hm_results *r, uint32_t *out_missing, hipStream_t s) {
-    if (!b->n_docs) return hipSuccess;
-    const uint32_t need = (b->n_docs + WWAVES - 1) / WWAVES;
-    hipLaunchKernelGGL(hmw::waiting_batch_kernel, dim3(need < 4096u ? need : 4096u), dim3(WWG), 0, s, b->docs, b->n_docs,
-                       b->changes, b->deps, (unsigned long long)b->n_changes, (unsigned long long)b->n_deps, r->docs, r->hist,
-                       r->clock, b->a_stride, out_missing);
+    hipLaunchKernelGGL(hmw::waiting_kernel, dim3(need < 4096u ? need : 4096u), dim3(WWG), 0, s, a);
     return hipGetLastError();
 }

@@ -249,11 +249,12 @@ struct SmallLds {
     LDS uint32_t *flags, *deps, *depinfo;
     LDS uint8_t *seglist;           // K3: visible flag per list position
     LDS uint16_t *survp;            // K3: visible elements before a position
-    LDS uint32_t *opmeta;           // action | datatype << 8 | vtag << 16
     LDS uint32_t *opro;             // reg | obj << 16 (clamped to 0xFFFF: >= any carve)
+    LDS uint32_t *opmeta;           // action | datatype << 8 | vtag << 16
     LDS uint32_t *opelem;           // ins element counter (list launches)
     LDS int32_t *hist_of;
-    LDS uint16_t *survop, *opbase, *oppar;
+    LDS uint16_t *survop, *opbase;
+    LDS uint16_t *oppar;            // ins parent (list launches)
     LDS uint8_t *h2a, *chactor, *objtype;
     LDS uint16_t *opchg;            // op -> arrival index of its change | actor rank << 8
     // K3 (RGA lists); carved only for launches with list documents
@@ -263,6 +264,20 @@ struct SmallLds {
     LDS u64 *stamps;                // HM_STAMPS builds: [HM_NSTAMP] cycle sums + last stamp
 };
 #define PAR_HEAD 0xFFFFu             // oppar of an insert after '_head'
+// Table strides.  A map launch (no K3 carve) interleaves the per-register and per-op tables, so what
+// one lane reads or writes together is one wide LDS access:
+//   survcnt, regoff, insmin, regobj  one 16-byte row per register in the order of hm_reg_result: a
+//                                    128-bit write initialises it, a 128-bit read feeds its store;
+//   segor, survpk                    one 16-byte row per register (K2 only), one write to clear it;
+//   opro, opmeta                     one 8-byte pair per op, staged and read as one.
+// A table is still named by its own pointer (its first entry) and indexed entry * stride.  The list
+// launches keep the tables apart (stride 1): they sit at their register limit, where the wider
+// lane-scaled addresses cost them spills.
+template <bool LISTS> struct Stride {
+    static constexpr uint32_t reg = LISTS ? 1 : 4;       // survcnt / regoff / insmin / regobj
+    static constexpr uint32_t seg = LISTS ? 1 : 2;       // segor / survpk
+    static constexpr uint32_t op = LISTS ? 1 : 2;        // opro / opmeta
+};
 
 // Size classes of the small kernel's carve (registers, objects, dep rows per document).
 template <int CLS> struct SizeClass;
@@ -289,9 +304,16 @@ __host__ __device__ inline size_t small_carve(P base, uint32_t NOp, uint32_t NR,
     // ---- live through the outputs (and the counters pass) ----
     TAKE(anc, u64, 64);          TAKE(chain, u64, NA_MAX);     TAKE(opval, u64, NOp);
     TAKE(errkey, u64, 1);        TAKE(base, uint32_t, NA_MAX * 3);
-    TAKE(survcnt, uint32_t, NR); TAKE(regoff, uint32_t, NR);   TAKE(regobj, uint32_t, NR);
-    TAKE(insmin, uint32_t, NR);  TAKE(flags, uint32_t, 2);
-    TAKE(opmeta, uint32_t, NOp); TAKE(opro, uint32_t, NOp);
+    if (lists) {
+        TAKE(survcnt, uint32_t, NR); TAKE(regoff, uint32_t, NR);   TAKE(regobj, uint32_t, NR);
+        TAKE(insmin, uint32_t, NR);  TAKE(flags, uint32_t, 2);
+        TAKE(opmeta, uint32_t, NOp); TAKE(opro, uint32_t, NOp);
+    } else {                                                       // interleaved (Stride<false>)
+        TAKE(survcnt, uint32_t, 4 * NR);                           TAKE(flags, uint32_t, 2);
+        L->regoff = L->survcnt + 1; L->insmin = L->survcnt + 2;    L->regobj = L->survcnt + 3;
+        TAKE(opro, uint32_t, 2 * NOp);
+        L->opmeta = L->opro + 1;
+    }
     TAKE(survop, uint16_t, NOp); TAKE(chactor, uint8_t, 64);   TAKE(objtype, uint8_t, NO);
     if (lists) {
         TAKE(opelem, uint32_t, NOp);
@@ -305,14 +327,17 @@ __host__ __device__ inline size_t small_carve(P base, uint32_t NOp, uint32_t NR,
     //      check) share one region; K3's tables overlay the whole part ----
     const size_t dead_at = o;
     TAKE(hist_of, int32_t, 64);  TAKE(cov, u64, 1);            TAKE(opbase, uint16_t, 64);
-    TAKE(oppar, uint16_t, NOp);  TAKE(h2a, uint8_t, 64);       TAKE(opchg, uint16_t, NOp);
+    TAKE(oppar, uint16_t, lists ? NOp : 0);                    // (a map launch hands every ins to the general kernel)
+    TAKE(h2a, uint8_t, 64);      TAKE(opchg, uint16_t, NOp);
     const size_t k1_at = o;
     TAKE(first, uint32_t, NA_MAX * 64);
     TAKE(deps, uint32_t, ND > NOp ? ND : NOp);                     // flags[1]: max n_deps
     TAKE(depinfo, uint32_t, ND);
     const size_t k1_end = o;
     o = k1_at;
-    TAKE(segor, u64, NR);        TAKE(survpk, u64, NR);        TAKE(segcnt, uint32_t, NR);
+    if (lists) { TAKE(segor, u64, NR);  TAKE(survpk, u64, NR); }
+    else { TAKE(segor, u64, 2 * NR);    L->survpk = L->segor + 1; }
+    TAKE(segcnt, uint32_t, NR);
     TAKE(objslot, uint32_t, NO);
     if (o < k1_end) o = k1_end;
     L->seglist = (decltype(L->seglist))L->first; L->survp = (decltype(L->survp))L->first;   // (K3's: below)
@@ -776,25 +801,44 @@ __device__ __forceinline__ void stage_op(const SmallLds &L, uint32_t k, uint32_t
     if (k >= m) return;
     // a = (obj, reg, parent, elem); b = (action | datatype << 8 | vtag << 16, key, value lo, value hi)
     const uint32_t obj = a.x < 0xFFFFu ? a.x : 0xFFFFu, reg = a.y < 0xFFFFu ? a.y : 0xFFFFu;
-    L.opro[k] = reg | (obj << 16);
-    L.oppar[k] = (uint16_t)(a.z == HM_HEAD ? PAR_HEAD : (a.z < 0xFFFEu ? a.z : 0xFFFEu));
-    L.opmeta[k] = b.x & 0xFFFFFFu;
-    L.opval[k] = ((u64)b.w << 32) | b.z;
-    if (LISTS) L.opelem[k] = a.w;
+    if constexpr (LISTS) {
+        L.opro[k] = reg | (obj << 16);
+        L.oppar[k] = (uint16_t)(a.z == HM_HEAD ? PAR_HEAD : (a.z < 0xFFFEu ? a.z : 0xFFFEu));
+        L.opmeta[k] = b.x & 0xFFFFFFu;
+        L.opval[k] = ((u64)b.w << 32) | b.z;
+        L.opelem[k] = a.w;
+    } else {
+        *(LDS uint2 *)(L.opro + 2 * k) = make_uint2(reg | (obj << 16), b.x & 0xFFFFFFu);
+        L.opval[k] = ((u64)b.w << 32) | b.z;
+    }
 }
-template <int OPL, bool LISTS, bool DIET>
-__device__ __forceinline__ void stage_rows(const SmallParams &p, const SmallLds &L, const hm_doc_row &doc, const Rows &r,
-                                           uint32_t cap_deps) {
+// Rows i = lane, lane + 64, ... below n of a table the launch's size class bounds (n <= CAP for every
+// document the kernel merges, see in_env): up to two rounds are predicated bodies, with no loop
+// counter, no exec-mask loop and no unrolled body for counts the carve cannot hold; larger carves
+// keep the loop, and so do the list launches (LOOP: at their register limit the flat form spilled).
+// A count past CAP only leaves rows out, it never reaches past the table.
+template <uint32_t CAP, bool LOOP, typename F>
+__device__ __forceinline__ void for_rows(uint32_t lane, uint32_t n, F f) {
+    if constexpr (CAP <= 2 * WAVE && !LOOP) {
+        if (lane < n) f(lane);
+        if constexpr (CAP > WAVE) { if (lane + WAVE < n) f(lane + WAVE); }
+    } else {
+        for (uint32_t i = lane; i < n; i += WAVE) f(i);
+    }
+}
+template <int OPL, bool LISTS, bool DIET, typename C>
+__device__ __forceinline__ void stage_rows(const SmallParams &p, const SmallLds &L, const hm_doc_row &doc, const Rows &r) {
     const uint32_t lane = lane_id<DIET>(), m = doc.n_ops;
     stage_op<LISTS>(L, lane, m, r.a0, r.b0);
     if (OPL > 1) stage_op<LISTS>(L, lane + WAVE, m, r.a1, r.b1);
     if (OPL > 2) stage_op<LISTS>(L, lane + 2 * WAVE, m, r.a2, r.b2);
     if (OPL > 3) stage_op<LISTS>(L, lane + 3 * WAVE, m, r.a3, r.b3);
-    const uint32_t nd = doc.n_deps < cap_deps ? doc.n_deps : cap_deps;
+    const uint32_t nd = doc.n_deps < C::ND ? doc.n_deps : C::ND;
     if (lane < nd) L.deps[lane] = pack_dep(r.d0);
     if (lane + WAVE < nd) L.deps[lane + WAVE] = pack_dep(r.d1);
-    for (uint32_t i = lane + 2 * WAVE; i < nd; i += WAVE)     // long dep tables: read on demand
-        L.deps[i] = pack_dep(*reinterpret_cast<const uint2 *>(p.deps + doc.dep_off + i));
+    if constexpr (C::ND > 2 * WAVE)
+        for (uint32_t i = lane + 2 * WAVE; i < nd; i += WAVE)     // long dep tables: read on demand
+            L.deps[i] = pack_dep(*reinterpret_cast<const uint2 *>(p.deps + doc.dep_off + i));
 }
 __device__ __forceinline__ hm_change_row change_of(uint2 w0, uint2 w1, uint2 w2) {
     hm_change_row c;
@@ -807,6 +851,7 @@ struct DocState {
     int32_t hist;             // per arrival lane
     uint32_t H, total;
     bool doc_lists;
+    bool counters;            // map launches: the document has counter ops and the launch the counter sums
 };
 
 // Per-op checks of K2 against the document's objects / elements: the first throw kind of the
@@ -816,18 +861,30 @@ struct DocState {
 // throws depends on the whole insertion chain, which merge_large_kernel climbs: the document
 // is deferred).  Reads only LDS (K2's tables), so the rare error-key pass can recompute it
 // instead of keeping it live.
+// A map launch (no K3 carve) has handed every document with an `ins` or an applied list / text
+// make op to the general kernel before this runs, so no op it checks touches a list: the only
+// throw left is the unknown object, and the element tables are not read.
 struct OpCheck { uint32_t err; bool surv, has_list, late; };
+template <bool LISTS>
 __device__ __forceinline__ OpCheck op_check(const SmallLds &L, int32_t ohv, uint32_t act, uint32_t obj, uint32_t reg,
                                             uint32_t par, uint32_t okey, uint32_t R, uint32_t O) {
     const bool asg = ohv >= 0 && act >= HM_INS && act <= HM_INC && reg < R;
     const uint32_t oi = obj < O ? obj : 0u, ri = reg < R ? reg : 0u;
-    const uint32_t pi = par < R ? par : 0u;
     const uint32_t os = obj < O ? L.objslot[oi] : 0xFFFFFFFFu;
-    const uint32_t ot = L.objtype[oi], im = L.insmin[ri], ip = L.insmin[pi];
-    const u64 so = L.segor[ri];
+    const uint32_t pi = par < R ? par : 0u;
+    uint32_t ot = 0, im = 0, ip = 0;                     // (read ahead of segor, as the list launches' register budget has it)
+    if constexpr (LISTS) { ot = L.objtype[oi]; im = L.insmin[ri]; ip = L.insmin[pi]; }
+    const u64 so = L.segor[Stride<LISTS>::seg * ri];
     const uint32_t h = ohv < 0 ? 0u : (uint32_t)ohv;
     const bool unknown = asg && (os == 0xFFFFFFFFu || os > okey);     // 'Modification of unknown object'
     const bool known = asg && !unknown;
+    if constexpr (!LISTS) {
+        OpCheck r;
+        r.has_list = false; r.late = false;
+        r.surv = known && (act == HM_SET || act == HM_LINK) && !((so >> h) & 1);
+        r.err = unknown ? (uint32_t)HM_ERR_UNKNOWN_OBJECT : 0u;
+        return r;
+    }
     const bool is_list = ot == HM_MAKE_LIST || ot == HM_MAKE_TEXT;
     const bool ins = known && act == HM_INS;
     const bool sl = known && (act == HM_SET || act == HM_LINK);
@@ -846,12 +903,13 @@ __device__ __forceinline__ OpCheck op_check(const SmallLds &L, int32_t ohv, uint
 }
 
 // Merge one document with the whole wave (no global stores).  Every return is wave-uniform.
-template <int OPL, bool LISTS, bool DIET>
+template <int OPL, bool LISTS, bool DIET, typename C>
 __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const SmallLds &L, const hm_doc_row &doc,
                                                    const uint2 w0, const uint2 w1, const uint2 w2, DocState &st) {
     uint32_t lane = lane_id<DIET>();          // (taken again at the phase boundaries below)
+    constexpr uint32_t RS = Stride<LISTS>::reg, SS = Stride<LISTS>::seg, OS = Stride<LISTS>::op;
     const uint32_t n = doc.n_changes, A = doc.n_actors, m = doc.n_ops, R = doc.n_regs, O = doc.n_objs;
-    st.hist = -1; st.H = 0; st.total = 0; st.doc_lists = false;
+    st.hist = -1; st.H = 0; st.total = 0; st.doc_lists = false; st.counters = false;
 
     // ---------------- the staged rows (lane = arrival index) ----------------
     if (HM_ABLATE & 8) return OUT_UNSUPPORTED;
@@ -903,7 +961,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     //             the batch's window of that actor, 0 for seq 0) | actor << 16
     {
         bool bad_dep = false;
-        for (uint32_t i = lane; i < ndep; i += WAVE) {
+        for_rows<C::ND, LISTS>(lane, ndep, [&](uint32_t i) {
             const uint32_t pk = L.deps[i];
             const uint32_t a = pk >> 24, s = pk & 0xFFFFFF;
             bad_dep |= pk == 0xFFFFFFFFu || a >= A;
@@ -913,7 +971,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
             const uint32_t f = L.first[fidx(ad, ((s - b) & 63))];
             const uint32_t rel = s == 0 ? 0u : (inwin ? s - b + 1 : 0x7Fu);
             L.depinfo[i] = (inwin && f < 64 ? f : 0x7Fu) | (rel << 8) | (ad << 16);
-        }
+        });
         if (__ballot(bad_dep)) return OUT_UNSUPPORTED;
     }
     const uint32_t first_me = act ? L.first[fidx(actor, slot)] : lane;
@@ -1379,13 +1437,36 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     // compare that literal fold with the closure and leave the envelope only when they differ.
     // Necessary condition (cheap): a listed non-own dep is an ancestor of another listed
     // non-own dep, or the own actor appears as a deps key (then seq-1 is folded in place).
+    // A strict ancestor precedes its descendant in history, so the lowest listed dep has no other
+    // listed dep among its ancestors: with two listed deps (the common case) only the upper one's
+    // set is read, by every lane at once (a clamped index, the test predicated) and with no per-lane
+    // walk over the bits; the walk over a third and further listed deps is exact behind a
+    // wave-uniform branch.  (The list launches keep the plain walk over every listed dep: the
+    // two ballots cost them scalar-register spills.)
     bool suspect = false;
-    if (hv && (Dnp & (Dnp - 1))) {
-        u64 x = Dnp;
-        while (x) {
-            const uint32_t i2 = (uint32_t)__builtin_ctzll(x);
-            x &= x - 1;
-            if (L.anc[i2] & Dnp) suspect = true;
+    if constexpr (LISTS) {
+        if (hv && (Dnp & (Dnp - 1))) {
+            u64 x = Dnp;
+            while (x) {
+                const uint32_t i2 = (uint32_t)__builtin_ctzll(x);
+                x &= x - 1;
+                if (L.anc[i2] & Dnp) suspect = true;
+            }
+        }
+    } else {
+        const u64 rest = Dnp & (Dnp - 1);                 // the listed deps above the lowest
+        const bool two = hv && rest != 0;
+        if (__ballot(two)) {
+            const u64 a1 = L.anc[two ? (uint32_t)__builtin_ctzll(rest) : 0u];
+            u64 x = two ? rest & (rest - 1) : 0ull;
+            suspect = two && (a1 & Dnp) != 0;
+            if (__ballot(x != 0)) {
+                while (x) {
+                    const uint32_t i2 = (uint32_t)__builtin_ctzll(x);
+                    x &= x - 1;
+                    if (L.anc[i2] & Dnp) suspect = true;
+                }
+            }
         }
     }
     uint32_t h_own_row = own_row ? 1u : 0u, h_dep0 = my_dep0, h_nd = c.n_deps;
@@ -1401,10 +1482,20 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
         if (fold_differs(fv, h_dep0, h_nd, hactor, hseq)) lds_or(L.flags, FL_UNSUPPORTED);
     }
     if (hv && !((covered >> lane) & 1)) L.headv[hactor] = hseq;     // opSet.deps
-    for (uint32_t i = lane; i < O; i += WAVE) { L.objslot[i] = i == 0 ? 0u : 0xFFFFFFFFu; L.objtype[i] = i == 0 ? HM_MAKE_MAP : 0xFF; }
-    for (uint32_t i = lane; i < R; i += WAVE) {
-        L.segor[i] = 0; L.segcnt[i] = 0; L.survpk[i] = 0; L.insmin[i] = 0xFFFFFFFFu; L.regobj[i] = HM_NONE;
-    }
+    for_rows<C::NO, LISTS>(lane, O, [&](uint32_t i) {
+        L.objslot[i] = i == 0 ? 0u : 0xFFFFFFFFu;
+        if constexpr (LISTS) L.objtype[i] = i == 0 ? HM_MAKE_MAP : 0xFF;      // (a map launch never reads the types)
+    });
+    for_rows<C::NR, LISTS>(lane, R, [&](uint32_t i) {
+        if constexpr (LISTS) {
+            L.segor[i] = 0; L.segcnt[i] = 0; L.survpk[i] = 0; L.insmin[i] = 0xFFFFFFFFu; L.regobj[i] = HM_NONE;
+        } else {                                                   // the two rows of the register, whole
+            static_assert(Stride<false>::reg == 4 && Stride<false>::seg == 2, "row widths");
+            *(LDS uint4 *)(L.survcnt + 4 * i) = make_uint4(0u, 0u, 0xFFFFFFFFu, HM_NONE);
+            *(LDS uint4 *)(L.segor + 2 * i) = make_uint4(0u, 0u, 0u, 0u);
+            L.segcnt[i] = 0;
+        }
+    });
     wave_sync();
 
     STAMP(L, 5);
@@ -1416,6 +1507,55 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     uint32_t oreg[OPL], oobj[OPL], opar[OPL], oact[OPL], okey[OPL], oarr[OPL], oelem[OPL], oactor[OPL];
     int32_t oh[OPL];
     bool counter_ops = false, malformed = false;
+    if constexpr (!LISTS) {
+        // Map launch.  Every op slot of the lane in one predicated pass: the staged word pair and
+        // the change word of all slots are requested together (slots past m read inside the
+        // tables and are masked), then what hangs on the change (its op base, its history position,
+        // its ancestor set), and the fields are decided with selects; only the LDS atomics sit
+        // under a predicate, one each.  A document with an `ins` (applied or not: its parent is
+        // not staged here) or an applied list / text make op goes to the general kernel with the
+        // malformed ones, before any error key is formed: no op that is checked below touches
+        // a list, so neither the element tables nor the object types are kept.
+        uint2 ow[OPL];
+        uint32_t cw[OPL], ob[OPL];
+        int32_t hr[OPL];
+        u64 an[OPL];
+#pragma unroll
+        for (int t = 0; t < OPL; t++) { ow[t] = *(LDS uint2 *)(L.opro + 2 * (lane + WAVE * t)); cw[t] = L.opchg[lane + WAVE * t]; }
+#pragma unroll
+        for (int t = 0; t < OPL; t++) {
+            const uint32_t ch = lane + WAVE * t < m ? cw[t] & 0xFFu : 0u;
+            oarr[t] = ch; oactor[t] = (cw[t] >> 8) & (NA_MAX - 1);
+            ob[t] = L.opbase[ch];
+            hr[t] = identity ? (int32_t)ch : L.hist_of[ch];
+        }
+#pragma unroll
+        for (int t = 0; t < OPL; t++) {
+            oh[t] = lane + WAVE * t < m ? hr[t] : -1;
+            an[t] = L.anc[oh[t] < 0 ? 0 : oh[t]];
+        }
+        bool listy = false;
+#pragma unroll
+        for (int t = 0; t < OPL; t++) {
+            const uint32_t k = lane + WAVE * t;
+            const bool live = k < m, applied = oh[t] >= 0;
+            const uint32_t a = live ? ow[t].y & 0xFF : 0xFFu;
+            oact[t] = a; oreg[t] = ow[t].x & 0xFFFFu; oobj[t] = ow[t].x >> 16; opar[t] = 0; oelem[t] = 0;
+            okey[t] = ((uint32_t)(applied ? oh[t] : 0) << 16) | (k - ob[t]);
+            // (bitwise, not short-circuit: every term is a compare or a select, none worth a branch)
+            counter_ops |= live & ((a == HM_INC) | (((ow[t].y >> 8) & 0xFF) == HM_DT_COUNTER));
+            const bool make = a <= HM_MAKE_TEXT;
+            // malformed rows (any op, applied or not) put the whole document outside the envelope
+            const bool bad = live & (make ? oobj[t] >= O : ((a > HM_INC) | (oreg[t] >= R)));
+            malformed |= bad;
+            listy |= (a == HM_INS) | (applied & ((a == HM_MAKE_LIST) | (a == HM_MAKE_TEXT)));
+            const bool asg = applied & !bad & !make & (a != HM_INS) & (oobj[t] < O);
+            if (applied & !bad & make) lds_min(&L.objslot[oobj[t]], okey[t] + 1);
+            if (asg) { L.regobj[4 * oreg[t]] = oobj[t]; lds_add(&L.segcnt[oreg[t]], 1u); }
+            if (asg && a != HM_INC) lds_or(&L.segor[2 * oreg[t]], an[t]);
+        }
+        malformed |= listy;
+    } else {
 #pragma unroll
     for (int t = 0; t < OPL; t++) {
         const uint32_t k = lane + WAVE * t;
@@ -1450,12 +1590,22 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
             }
         }
     }
+    }
     STAMP(L, 6);
     if constexpr (DIET) lane = fresh_lane();
     if (HM_ABLATE & 128) return OUT_UNSUPPORTED;
     if (__ballot(malformed)) return OUT_UNSUPPORTED;
-    // counter sums need the carve's survsum table (launches flagged HM_DOC_HAS_COUNTERS)
-    if (!p.counters && __ballot(counter_ops)) lds_or(L.flags, FL_UNSUPPORTED);
+    // counter sums need the carve's survsum table (launches flagged HM_DOC_HAS_COUNTERS).  The ballot
+    // first: a document without counter ops (most) then never waits for the launch's flag to load,
+    // and its survivors carry no counter tags (only a counter set, itself a counter op, reads them).
+    // (The list launches test the flag first, as before: the other order spills scalar registers there.)
+    bool doc_counters = false;
+    if constexpr (LISTS) {
+        if (!p.counters && __ballot(counter_ops)) lds_or(L.flags, FL_UNSUPPORTED);
+    } else if (__ballot(counter_ops)) {
+        if (p.counters) doc_counters = true;
+        else lds_or(L.flags, FL_UNSUPPORTED);
+    }
     wave_sync();
     // objects: the earliest make op creates, later ones throw 'Duplicate creation of object'
 #pragma unroll
@@ -1463,7 +1613,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
         if (oh[t] >= 0 && oact[t] <= HM_MAKE_TEXT && oobj[t] < O) {
             if (L.objslot[oobj[t]] != okey[t] + 1)
                 lds_min(L.errkey, err_key((uint32_t)oh[t], (okey[t] & 0xFFFF) + 1, oarr[t], HM_ERR_DUPLICATE_OBJECT));
-            else L.objtype[oobj[t]] = (uint8_t)oact[t];
+            else if constexpr (LISTS) L.objtype[oobj[t]] = (uint8_t)oact[t];
         }
     wave_sync();
     bool surv[OPL];
@@ -1471,29 +1621,28 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
 #pragma unroll
     for (int t = 0; t < OPL; t++) {
         // predicated: every lane reads (clamped) and decides with selects, no per-op branches
-        const OpCheck ck = op_check(L, oh[t], oact[t], oobj[t], oreg[t], opar[t], okey[t], R, O);
+        const OpCheck ck = op_check<LISTS>(L, oh[t], oact[t], oobj[t], oreg[t], opar[t], okey[t], R, O);
         has_list |= ck.has_list;
         anyerr |= ck.err != 0;
         late |= ck.late;
         surv[t] = ck.surv;
         // survivors counted per (register, actor rank): the rank below needs no survivor list
-        if (surv[t]) lds_add(&L.survpk[oreg[t]], 1ull << (8 * oactor[t]));
+        if (surv[t]) lds_add(&L.survpk[SS * oreg[t]], 1ull << (8 * oactor[t]));
     }
-    if (__ballot(late)) return OUT_UNSUPPORTED;                  // the general kernel climbs the chains
+    if (LISTS && __ballot(late)) return OUT_UNSUPPORTED;         // the general kernel climbs the chains
     if (__ballot(anyerr)) {
         // a throw: its key (history position, op, arrival) orders it against the others
         u64 errk = ~0ull;                // this lane's earliest throw (one wave-wide min below)
 #pragma unroll
         for (int t = 0; t < OPL; t++) {
-            const OpCheck ck = op_check(L, oh[t], oact[t], oobj[t], oreg[t], opar[t], okey[t], R, O);
+            const OpCheck ck = op_check<LISTS>(L, oh[t], oact[t], oobj[t], oreg[t], opar[t], okey[t], R, O);
             const uint32_t h = oh[t] < 0 ? 0u : (uint32_t)oh[t], kk = (okey[t] & 0xFFFF) + 1;
             const u64 ek = ck.err ? err_key(h, kk, oarr[t], ck.err) : ~0ull;
             errk = errk < ek ? errk : ek;
         }
         lds_min(L.errkey, errk);
     }
-    const bool doc_lists = __ballot(has_list) != 0;
-    if (!LISTS && doc_lists) lds_or(L.flags, FL_UNSUPPORTED);   // launched without the K3 carve
+    const bool doc_lists = LISTS && __ballot(has_list) != 0;     // (a map launch: such documents left above)
     wave_sync();
     if (*L.errkey != ~0ull) return OUT_ERROR;                    // the first throw wins
     if (*L.flags & FL_UNSUPPORTED) return OUT_UNSUPPORTED;
@@ -1506,13 +1655,19 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     // survivor offsets: exclusive scan over register ids (a register's count = its byte sum)
     uint32_t total = 0;
     const uint32_t lane_s = LISTS ? lane : fresh_lane();     // (list launches: no spill there; A/B C5 +2 % with it)
-    for (uint32_t r0 = 0; r0 < R; r0 += WAVE) {
-        const uint32_t r = r0 + lane_s;
+    auto offsets = [&](uint32_t r) {
         uint32_t tot;
-        const uint32_t cnt = r < R ? bytesum64(L.survpk[r]) : 0u;
+        const uint32_t cnt = r < R ? bytesum64(L.survpk[SS * r]) : 0u;
         const uint32_t ex = wave_excl_scan(cnt, &tot);
-        if (r < R) { L.regoff[r] = total + ex; L.survcnt[r] = cnt; }
+        if constexpr (LISTS) { if (r < R) { L.regoff[r] = total + ex; L.survcnt[r] = cnt; } }
+        else if (r < R) *(LDS uint2 *)(L.survcnt + 4 * r) = make_uint2(cnt, total + ex);      // (count, offset: one pair)
         total += tot;
+    };
+    if constexpr (C::NR <= 2 * WAVE && !LISTS) {                      // (R <= C::NR: one or two rounds, no loop)
+        offsets(lane_s);
+        if constexpr (C::NR > WAVE) { if (R > WAVE) offsets(lane_s + WAVE); }
+    } else {
+        for (uint32_t r0 = 0; r0 < R; r0 += WAVE) offsets(r0 + lane_s);
     }
     wave_sync();
     // rank: actor rank descending = the survivors of higher actors on the register (bytes above
@@ -1523,8 +1678,8 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     for (int t = 0; t < OPL; t++) {
         const uint32_t ri = surv[t] ? oreg[t] : 0u;
         my_act[t] = surv[t] ? oactor[t] : 0u;
-        rb0[t] = L.regoff[ri];
-        const u64 pk = L.survpk[ri];
+        rb0[t] = L.regoff[RS * ri];
+        const u64 pk = L.survpk[SS * ri];
         const uint32_t sh = 8 * (my_act[t] + 1);
         rank[t] = surv[t] ? bytesum64(sh >= 64 ? 0ull : pk >> sh) : 0u;
         tie[t] = surv[t] && ((pk >> (8 * my_act[t])) & 0xFF) > 1;
@@ -1584,8 +1739,8 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
         if (!surv[t]) continue;
         const uint32_t pos = rb0[t] + rank[t];
         uint32_t tag = 0;
-        if (p.counters) {
-            const uint32_t mt = L.opmeta[lane + WAVE * t], vt = (mt >> 16) & 0xFF;
+        if (LISTS ? p.counters != 0 : doc_counters) {
+            const uint32_t mt = L.opmeta[OS * (lane + WAVE * t)], vt = (mt >> 16) & 0xFF;
             const bool cset = (mt & 0xFF) == HM_SET && ((mt >> 8) & 0xFF) == HM_DT_COUNTER && (vt == HM_V_INT || vt == HM_V_FLOAT);
             tag = cset ? (0x8000u | (vt == HM_V_INT ? 0x4000u : 0u) | ((uint32_t)oh[t] << 8)) : 0u;
             L.survsum[pos] = 0;
@@ -1608,7 +1763,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     // JS numbers: an integer counter is exact only while |base| + sum|inc| <= 2^53; with at
     // most 256 ops per document, |inc| < 2^44 and |base| < 2^52 guarantee it (larger
     // values go to merge_large_kernel, which tracks sum|inc| exactly).
-    if (p.counters && __ballot(counter_ops)) {
+    if (LISTS ? (p.counters && __ballot(counter_ops)) : doc_counters) {
         bool outside = false;
         // every inc's value load issued before the first is used (they are L2 round trips)
         // and the base values of surviving integer counter sets (the 2^52 envelope check)
@@ -1628,9 +1783,9 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
         for (int t = 0; t < OPL; t++) {
             if (oh[t] < 0 || oact[t] != HM_INC) continue;
             const uint32_t k = lane + WAVE * t;
-            const uint32_t reg = oreg[t], b0 = L.regoff[reg], cnt = L.survcnt[reg];
+            const uint32_t reg = oreg[t], b0 = L.regoff[RS * reg], cnt = L.survcnt[RS * reg];
             const u64 an = L.anc[oh[t]];
-            const uint32_t my_vtag = (L.opmeta[k] >> 16) & 0xFF;
+            const uint32_t my_vtag = (L.opmeta[OS * k] >> 16) & 0xFF;
             const int64_t v = incv[t];
             for (uint32_t q = 0; q < cnt; q++) {
                 const uint32_t sw = L.survop[b0 + q];
@@ -1649,7 +1804,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
         if (__ballot(outside)) return OUT_UNSUPPORTED;
         wave_sync();
     }
-    st.hist = hist; st.H = H; st.total = total; st.doc_lists = doc_lists;
+    st.hist = hist; st.H = H; st.total = total; st.doc_lists = doc_lists; st.counters = doc_counters;
     return OUT_OK;
 }
 
@@ -1675,10 +1830,12 @@ __device__ __forceinline__ SurvRows<OPL> surv_rows(const SmallParams &p, const S
 #pragma unroll
     for (int t = 0; t < OPL; t++) {
         const uint32_t q = lane + WAVE * t;
-        const uint32_t k = q < st.total ? (L.survop[q] & 0xFFu) : 0u, mt = L.opmeta[k];
+        const uint32_t k = q < st.total ? (L.survop[q] & 0xFFu) : 0u, mt = L.opmeta[Stride<LISTS>::op * k];
         hm_surv_result sr;
         sr.op = k; sr.vtag = (mt >> 16) & 0xFF; sr.value = op_value(L, k);
-        if (p.counters && q < st.total && (mt & 0xFF) == HM_SET && ((mt >> 8) & 0xFF) == HM_DT_COUNTER && sr.vtag == HM_V_INT)
+        // (a map launch knows from the merge whether the document has counters at all: no launch
+        // parameter is loaded, and waited for, ahead of the survivor rows of the others)
+        if ((LISTS ? p.counters != 0 : st.counters) && q < st.total && (mt & 0xFF) == HM_SET && ((mt >> 8) & 0xFF) == HM_DT_COUNTER && sr.vtag == HM_V_INT)
             sr.value = (u64)((int64_t)sr.value + L.survsum[q]);
         o.r[t] = sr;
     }
@@ -1713,26 +1870,32 @@ __device__ __forceinline__ void put_status_row(hm_doc_result *dres, uint32_t sta
     r.hist_len = zero; r.n_queued = zero; r.n_surv = zero; r.min_cmp = zero; r.pad = zero;
     *dres = r;
 }
-template <int OPL, bool LISTS, bool DIET>
+template <int OPL, bool LISTS, bool DIET, typename C>
 __device__ __forceinline__ void write_outputs(const SmallParams &p, const SmallLds &L, uint32_t d, uint32_t ds,
                                               const hm_doc_row &doc, Outcome oc, const DocState &st, uint32_t mcmp,
                                               const SurvRows<OPL> &sv, uint32_t lane) {
     const uint32_t S = p.a_stride;
     const uint32_t n = doc.n_changes, A = doc.n_actors, R = doc.n_regs;
-    hm_doc_result *dres = p.res_docs + ds;      // ds: row of the per-document outputs
+    // ds: row of the per-document outputs.  The five-wave instantiations form the row's address
+    // where a path stores to it: formed here, ahead of the branches, the table's base was a scalar
+    // load waited for at once on every document, ahead of the batch of parameter loads the merged
+    // document's path starts with.  (The others keep it here: moved, they spill scalar registers.)
+    hm_doc_result *dres_here = nullptr;
+    if constexpr (!DIET) dres_here = p.res_docs + ds;
+    auto dres_of = [&]() { if constexpr (DIET) return p.res_docs + ds; else return dres_here; };
     if (oc == OUT_ERROR) {
         // an Automerge throw aborted this document's Backend.applyChanges
         const u64 ek = *L.errkey;
         if (lane == 0) {
             const uint32_t status = (uint32_t)(ek & 0xFF), opp1 = (uint32_t)((ek >> 24) & 0xFFFF);
             const bool uns = status == HM_ERR_UNSUPPORTED;
-            put_status_row(dres, status, uns ? HM_NONE : (uint32_t)((ek >> 8) & 0xFFFF), (uns || !opp1) ? HM_NONE : opp1 - 1);
+            put_status_row(dres_of(), status, uns ? HM_NONE : (uint32_t)((ek >> 8) & 0xFFFF), (uns || !opp1) ? HM_NONE : opp1 - 1);
         }
         return;
     }
     if (oc == OUT_INVALID) {
         // malformed row (ranges outside the batch tables): nothing of it is read or written
-        if (lane == 0) put_status_row(dres, (uint32_t)HM_ERR_INVALID, HM_NONE, HM_NONE);
+        if (lane == 0) put_status_row(dres_of(), (uint32_t)HM_ERR_INVALID, HM_NONE, HM_NONE);
         uint32_t *ck = p.res_clock + (size_t)ds * S, *hd = p.res_heads + (size_t)ds * S, *bk = p.res_back_clock + (size_t)ds * S;
         for (uint32_t a = lane; a < S; a += WAVE) { ck[a] = 0u; hd[a] = 0u; bk[a] = 0u; }
         return;
@@ -1740,7 +1903,7 @@ __device__ __forceinline__ void write_outputs(const SmallParams &p, const SmallL
     if (oc == OUT_UNSUPPORTED) {
         // outside this kernel's envelope: merge_large_kernel finds the status and takes the document
         if (lane == 0) {
-            put_status_row(dres, (uint32_t)HM_DEFERRED, HM_NONE, HM_NONE);
+            put_status_row(dres_of(), (uint32_t)HM_DEFERRED, HM_NONE, HM_NONE);
 #if !HM_ABLATE
             p.deferred[atomicAdd(p.n_deferred, 1u)] = d;     // merge_large_kernel's work list
 #endif
@@ -1756,10 +1919,18 @@ __device__ __forceinline__ void write_outputs(const SmallParams &p, const SmallL
                      "s"(p.res_all_deps), "s"(p.res_regs), "s"(p.res_surv));     // (see the document loop)
 #endif
     hm_reg_result *regs = p.res_regs + doc.reg_off;
-    for (uint32_t r = lane; r < R; r += WAVE) {
-        const int32_t li = (LISTS && st.doc_lists) ? (int32_t)L.insmin[r] : -1;
-        st16(regs + r, make_uint4(L.survcnt[r], L.regoff[r], (uint32_t)li, L.regobj[r]));
-    }
+    for_rows<C::NR, LISTS>(lane, R, [&](uint32_t r) {
+        if constexpr (LISTS) {
+            const int32_t li = st.doc_lists ? (int32_t)L.insmin[r] : -1;
+            st16(regs + r, make_uint4(L.survcnt[r], L.regoff[r], (uint32_t)li, L.regobj[r]));
+        } else {
+            // a map launch: the register's LDS row is its output row (no `ins` was applied, so the
+            // list index word still holds the all ones, -1, it was cleared to)
+            static_assert(sizeof(hm_reg_result) == 16 && Stride<false>::reg == 4, "register rows are stored whole");
+            // (the row's byte offset as a 32-bit lane part of the scalar base: r < 2^16)
+            st16(reinterpret_cast<char *>(regs) + r * 16u, *(LDS uint4 *)(L.survcnt + 4 * r));
+        }
+    });
     // allDeps rows: lane = arrival index writes its change's row (zeros if not applied;
     // chain[a] is empty for a >= A)
     if (lane < n) {
@@ -1791,7 +1962,7 @@ __device__ __forceinline__ void write_outputs(const SmallParams &p, const SmallL
         r.status = HM_OK; r.err_change = HM_NONE; r.err_op = HM_NONE;
         r.hist_len = st.H; r.n_queued = (uint32_t)__popcll(q); r.n_surv = st.total;
         r.min_cmp = mcmp;
-        *dres = r;
+        *dres_of() = r;
     }
 #pragma unroll
     for (int t = 0; t < OPL; t++) {
@@ -1863,7 +2034,7 @@ void merge_small_kernel(SmallParams p) {
     uint2 w0, w1, w2;                        // this document's change row (lane = arrival index)
     {
         const Rows r = load_rows<OPL>(p, doc);
-        stage_rows<OPL, LISTS, DIET>(p, L, doc, r, C::ND);
+        stage_rows<OPL, LISTS, DIET, C>(p, L, doc, r);
         w0 = make_uint2(r.c01.x, r.c01.y); w1 = make_uint2(r.c01.z, r.c01.w); w2 = r.c2;
     }
     wave_sync();
@@ -1924,7 +2095,7 @@ void merge_small_kernel(SmallParams p) {
             for (uint32_t a = WAVE + threadIdx.x; a < p.a_stride; a += WAVE) extra |= p.min_clock[(size_t)ds * p.a_stride + a];
             if (__ballot(extra != 0) && threadIdx.x == NA_MAX) mc |= 1u;
         }
-        const Outcome oc = !dok ? OUT_INVALID : in_env ? merge_doc_small<OPL, LISTS, DIET>(p, L, doc, w0, w1, w2, st) : OUT_UNSUPPORTED;
+        const Outcome oc = !dok ? OUT_INVALID : in_env ? merge_doc_small<OPL, LISTS, DIET, C>(p, L, doc, w0, w1, w2, st) : OUT_UNSUPPORTED;
         STAMP(L, 9);
         // One lane index for the whole output phase, taken here: between the next document's row
         // loads and its wait (take_rows_async) no statement may make the compiler wait for memory,
@@ -1970,15 +2141,15 @@ void merge_small_kernel(SmallParams p) {
         // staging after the stores waited for all of them; now nothing waits for the stores
         // until the next document's merge has run
         wave_sync();
-        if (more) stage_rows<OPL, LISTS, DIET>(p, L, docn, next, C::ND);
+        if (more) stage_rows<OPL, LISTS, DIET, C>(p, L, docn, next);
         STAMP(L, 11);
-        write_outputs<OPL, LISTS, DIET>(p, L, d, ds, doc, oc, st, mcmp, sv, lane_io);
+        write_outputs<OPL, LISTS, DIET, C>(p, L, d, ds, doc, oc, st, mcmp, sv, lane_io);
         if (HM_PRIO_IO) __builtin_amdgcn_s_setprio(0);
         wave_sync();
         STAMP(L, 10);
         if (!more) break;
 #else
-        write_outputs<OPL, LISTS, DIET>(p, L, d, ds, doc, oc, st, mcmp, sv, lane_io);
+        write_outputs<OPL, LISTS, DIET, C>(p, L, d, ds, doc, oc, st, mcmp, sv, lane_io);
 #if HM_ASYNC_NEXT
         if constexpr (ASY) { if (more) pad_stores<OPL>(p, doc, st, ds, oc == OUT_OK); }
 #endif
@@ -1993,7 +2164,7 @@ void merge_small_kernel(SmallParams p) {
 #endif
         }
 #endif
-        stage_rows<OPL, LISTS, DIET>(p, L, docn, next, C::ND);
+        stage_rows<OPL, LISTS, DIET, C>(p, L, docn, next);
         if (HM_PRIO_IO) __builtin_amdgcn_s_setprio(0);
         wave_sync();
         STAMP(L, 11);

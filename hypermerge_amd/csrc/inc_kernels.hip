@@ -901,17 +901,11 @@ __device__ int inc_doc_tiled(const AppendDesc &D, const IncArgs &A, uint4 *ssv, 
 
 // TL: the launch for rounds that need tiles (a separate instantiation: the tile loop around
 // inc_doc costs the common round's register allocation half its occupancy)
-#ifndef HM_INC_KARG_RELOAD
-#define HM_INC_KARG_RELOAD 1 // inc_group_kernel: launch parameters re-read per document (see the kernel)
-#endif
-#ifndef HM_INC_WAVES
-#define HM_INC_WAVES 1       // dev A/B: waves per SIMD the G = 8 / 16 instantiations are compiled for
-#endif
 // LS (G = 8 / 16, HM_INC_LIST_GROUPS): the instantiation for documents with lists (HM_DINC_LISTS);
 // the other takes the map documents at the register budget the list code would cost them (116 vs
 // 141 VGPRs: 4 waves per SIMD instead of 3)
 template <int G, bool TL, bool LS = false>
-__global__ __launch_bounds__(256, (G < 64 ? HM_INC_WAVES : 1)) void inc_group_kernel(IncArgs A_in) {
+__global__ __launch_bounds__(256, 1) void inc_group_kernel(IncArgs A_in) {
     constexpr uint32_t NG = 256 / G;
     __shared__ uint4 s_sv[NG][2 * G];
     __shared__ uint2 s_mt[NG][2 * G];
@@ -927,8 +921,8 @@ __global__ __launch_bounds__(256, (G < 64 ? HM_INC_WAVES : 1)) void inc_group_ke
     typedef __attribute__((address_space(4))) const IncArgs KArgs;
     KArgs *kp = (KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
     for (uint32_t q = blockIdx.x * NG + grp; q < n; q += gridDim.x * NG) {
-        if (HM_INC_KARG_RELOAD) asm volatile("" : "+s"(kp));
-        const IncArgs &A = HM_INC_KARG_RELOAD ? *(const IncArgs *)kp : A_in;
+        asm volatile("" : "+s"(kp));
+        const IncArgs &A = *(const IncArgs *)kp;
         const uint32_t di = A.list ? A.list[1 + q] : q;
         const AppendDesc D = A.descs[di];
         const uint32_t route = D.inc & HM_DINC_ROUTE;

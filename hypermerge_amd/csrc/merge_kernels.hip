@@ -35,6 +35,7 @@
 #include <stdint.h>
 #include "../../include/hypermerge_amd.h"
 #include "merge_kernels.h"
+#include "wave.h"
 
 #ifndef HM_ABLATE
 #define HM_ABLATE 0     // dev-only builds: stop (defer the doc) after a phase — 16 validate, 32 deps, 64 push,
@@ -45,9 +46,6 @@
 #define HM_STAMPS 0     // diagnostic builds only: per-phase s_memtime shares (tools/stamps.py); never timed
 #endif
 #define HM_NSTAMP 20
-#ifndef HM_PREFETCH_EARLY
-#define HM_PREFETCH_EARLY 0 // 1: the next document's rows are loaded before this document's merge
-#endif
 #ifndef HM_WAVES_PER_EU_OPL4
 #define HM_WAVES_PER_EU_OPL4 3  // 256 ops per document: the op arrays need a larger register budget (measured:
                                 // C2 0.87 -> 0.65 ms at 3 waves/SIMD; list launches (C5) best at 2: 3.99 -> 3.25 ms)
@@ -72,63 +70,24 @@
 #ifndef HM_PRIO_RANK
 #define HM_PRIO_RANK 2      // through the survivor offsets, ranks and ties: C4 2.42 -> 2.39 ms
 #endif
-#ifndef HM_PRIO_FOLD
-#define HM_PRIO_FOLD 0      // dev A/B: the push's priority held through the fold check and table init
-#endif
-#ifndef HM_PRIO_K3
-#define HM_PRIO_K3 0        // dev A/B: priority through K3 (list order)
-#endif
 #ifndef HM_PRIO_K2
 #define HM_PRIO_K2 2        // through the K2 op scan and survivor tests: C4 2.22 -> 2.16 ms, actor-major 3.32 -> 3.28, C5 0.630 -> 0.621 (r05 ab_prio2)
-#endif
-#ifndef HM_PUSH_BPERM
-#define HM_PUSH_BPERM 0     // K1b's ancestor push broadcasts through ds_bpermute instead of v_readlane
-#endif
-#ifndef HM_KARG_RELOAD
-#define HM_KARG_RELOAD 1    // merge_small_kernel: launch parameters re-read per document (see the kernel)
-#endif
-#ifndef HM_KARG_BATCH
-#define HM_KARG_BATCH 1     // five-wave instantiations: the fields a phase reads are requested in one batch where it begins
-#endif
-#ifndef HM_HIST_DP
-#define HM_HIST_DP 1        // queued documents: history by the parallel (t, pass, pos) solve before the pass loop
-#endif
-#ifndef HM_HIST_REGS
-#define HM_HIST_REGS 1      // ... iterated in registers (cross-lane reads) when every change has <= 4 dependency lanes
 #endif
 #ifndef HM_PRIO_K1
 #define HM_PRIO_K1 3        // through validation and the dependency pre-pass: C4 2.41 -> 2.37 ms
 #endif
-#ifndef HM_FENCE_MCMP
-#define HM_FENCE_MCMP 1     // pin Clock.cmp(DocBackend.clock, minimumClock) ahead of the next document's row loads
-#endif
-#ifndef HM_STAGE_FIRST
-#define HM_STAGE_FIRST 0    // 1: stage the next document's rows before this document's stores (A/B: C4 2.38 -> 2.44 ms, the
-                            // store outputs then waited in write_outputs on reused registers)
-#endif
-#ifndef HM_ASYNC_NEXT
-#define HM_ASYNC_NEXT 1     // the next document's rows by inline-asm loads, waited for by a counted vmcnt that
-                            // leaves this document's stores in flight (a compiler-counted load is waited for
-                            // with vmcnt(0): the stores' count varies by path, so the staging waited for them)
-#endif
 #ifndef HM_ASYNC_MAX_OPL
-#define HM_ASYNC_MAX_OPL 2  // instantiations (op rows per lane) that load the next document's rows by asm
+#define HM_ASYNC_MAX_OPL 2  // instantiations (op rows per lane) that load the next document's rows by inline-asm loads,
+                            // waited for by a counted vmcnt that leaves this document's stores in flight (a
+                            // compiler-counted load is waited for with vmcnt(0): the stores' count varies by
+                            // path, so the staging waited for them); the others load them with counted loads
 #endif
 #ifndef HM_ASYNC_STORES
 #define HM_ASYNC_STORES 10  // store instructions an OK document's write_outputs issues at least (padded)
 #endif
-#ifndef HM_NT_OUT
-#define HM_NT_OUT 0         // dev A/B: the output rows (allDeps, history, registers, survivors) as non-temporal stores
-#endif
-#ifndef HM_NT_IN
-#define HM_NT_IN 0          // dev A/B: the next document's rows as non-temporal loads (read once)
-#endif
 #ifndef HM_ASYNC_CHECK
 #define HM_ASYNC_CHECK 0    // check builds (libhmgpu_check.so): every asynchronously loaded set of rows is re-read
                             // with counted loads and compared (hm_debug_async_check counts the differences)
-#endif
-#ifndef HM_OPAQUE_LANE
-#define HM_OPAQUE_LANE 1    // per-document lane index the compiler cannot hoist out of the document loop
 #endif
 #ifndef HM_WAVES_PER_EU
 #define HM_WAVES_PER_EU 5   // map documents of <= 128 ops in the two small carves (classes 0 and 2): 96 VGPRs, no
@@ -165,13 +124,8 @@ __device__ __forceinline__ u64 wave_or64(u64 v) {
     for (int o = 1; o < WAVE; o <<= 1) v |= shfl64(v, (int)(threadIdx.x ^ o));
     return v;
 }
-// DPP lane moves (gfx9 encodings): lanes without a source read 0
-#define DPP_ROW_SHR(n) (0x110 + (n))
-#define DPP_WAVE_SHR1 0x138
-#define DPP_ROW_BCAST15 0x142
-#define DPP_ROW_BCAST31 0x143
 // exclusive prefix sum across the wave; *total = sum over all lanes.  Row-local shifts and
-// the gfx9 row broadcasts (VALU only: no LDS round trip as a bpermute ladder would need).
+// the gfx9 row broadcasts (wave.h's DPP lane moves; VALU only: no LDS round trip as a bpermute ladder would need).
 __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t *total) {
     uint32_t x = v;
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, DPP_ROW_SHR(1), 0xF, 0xF, false);
@@ -208,13 +162,9 @@ __device__ __forceinline__ uint32_t prev_lane(uint32_t v) {
 // its reload (a global-latency round trip, s_waitcnt vmcnt(0)) sat in the survivor-offset scan
 // of every document.  An address built from this value is recomputed where it is used.
 __device__ __forceinline__ uint32_t fresh_lane() {
-#if HM_OPAQUE_LANE
     uint32_t l;
     asm volatile("v_mov_b32 %0, %1" : "=v"(l) : "v"((uint32_t)threadIdx.x));
     return l;
-#else
-    return threadIdx.x;
-#endif
 }
 // The instantiations held to 96 VGPRs (five waves per SIMD) take a fresh lane index in every
 // phase: whatever a phase derives from it (byte offsets, lane masks, comparisons) then lives
@@ -690,7 +640,6 @@ __device__ __forceinline__ void async_check(const SmallParams &p, const hm_doc_r
     }
 }
 #endif
-#if HM_ASYNC_NEXT
 // The next document's rows issued as inline-asm loads: hipcc does not count them, so the staging
 // waits with an explicit vmcnt(N) — N the store instructions write_outputs is certain to issue
 // after them on the path taken — instead of the vmcnt(0) a counted load gets, which also waited
@@ -701,22 +650,18 @@ __device__ __forceinline__ void async_check(const SmallParams &p, const hm_doc_r
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 struct AsyncRows { u32x2 c0, c1, c2; u32x4 a0, b0, a1, b1, a2, b2, a3, b3; u32x2 d0, d1; };
-#if HM_NT_IN
-#define HM_AL_POL " nt"
-#else
-#define HM_AL_POL ""
-#endif
 // Scalar-base form: a table's base plus the document's offset is wave-uniform (an SGPR pair), the
 // lane's part a 32-bit byte offset (row index x row size, < 2^16), the second half of a row an
 // immediate offset: no 64-bit address arithmetic and no address register pairs per lane.
+// (Plain loads: as non-temporal loads the rows, though read once, measured 11 % slower.)
 template <int IMM> __device__ __forceinline__ u32x2 aload2(const void *base, uint32_t off) {
     u32x2 v;
-    asm volatile("global_load_dwordx2 %0, %1, %2 offset:%3" HM_AL_POL : "=v"(v) : "v"(off), "s"(base), "n"(IMM) : "memory");
+    asm volatile("global_load_dwordx2 %0, %1, %2 offset:%3" : "=v"(v) : "v"(off), "s"(base), "n"(IMM) : "memory");
     return v;
 }
 template <int IMM> __device__ __forceinline__ u32x4 aload4(const void *base, uint32_t off) {
     u32x4 v;
-    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" HM_AL_POL : "=v"(v) : "v"(off), "s"(base), "n"(IMM) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(v) : "v"(off), "s"(base), "n"(IMM) : "memory");
     return v;
 }
 template <int OPL, bool LISTS>
@@ -787,7 +732,6 @@ __device__ __forceinline__ Rows take_rows_async(AsyncRows &r, const hm_doc_row &
     o.d0 = make_uint2(r.d0.x, r.d0.y); o.d1 = make_uint2(r.d1.x, r.d1.y);
     return o;
 }
-#endif
 // an op's 8-byte value, staged in LDS with its row (an L2 re-read would put a global-load
 // round trip on the output phase's critical path)
 __device__ __forceinline__ u64 op_value(const SmallLds &L, uint32_t k) { return L.opval[k]; }
@@ -1065,7 +1009,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
         u64 applied = 0, queue = 0;                       // applied keys; queued lanes
         bool copy_applied = false;                        // a duplicate copy stands for its key
         bool solved = false;
-        if (HM_HIST_DP) {
+        {
             // Every change's place in history in parallel, per (actor, seq) key (its first
             // arrival's lane; copies of a key have equal content, hence equal deps).  The arrival
             // whose processing applies key K is t(K) = max(first arrival of K, t(deps)) = the
@@ -1088,7 +1032,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
             // deps and the predecessor) iterate in registers: the lanes a change reads are fixed,
             // so each round is 4 cross-lane reads (ds_bpermute) and a ballot, with no LDS round
             // trip (the copies of a duplicated key still meet in LDS for their minimum).
-            const bool regdp = HM_HIST_REGS && __ballot(act && __popcll(dall) > 4) == 0;
+            const bool regdp = __ballot(act && __popcll(dall) > 4) == 0;
             uint32_t sl0 = lane, sl1 = lane, sl2 = lane, sl3 = lane;
             if (regdp) {
                 u64 m = dall;
@@ -1392,14 +1336,9 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
         const uint32_t Hs = (uint32_t)__builtin_amdgcn_readfirstlane((int)H);
         const uint32_t Dlo = (uint32_t)D, Dhi = (uint32_t)(D >> 32);
         const uint32_t H1 = Hs < 32 ? Hs : 32;
-#if HM_PUSH_BPERM
-        // lane k's set broadcast by ds_bpermute (the LDS pipe) instead of v_readlane (a VALU
-        // instruction and an SGPR hazard): the kernel is VALU-issue bound, the push a quarter of
-        // its VALU instructions
-#define PUSH_BC(v, k) ((uint32_t)__builtin_amdgcn_ds_bpermute((k) << 2, (int)(v)))
-#else
+        // lane k's set by v_readlane (through ds_bpermute the push has a third fewer VALU
+        // instructions, but each step waits on an LDS round trip: no gain)
 #define PUSH_BC(v, k) ((uint32_t)__builtin_amdgcn_readlane((int)(v), (int)(k)))
-#endif
 #define PUSH_LO(k) alo |= PUSH_BC(alo, (k)) & (uint32_t)__builtin_amdgcn_sbfe((int)Dlo, (k), 1)
 #define PUSH_HI(k) do { const uint32_t m_ = (uint32_t)__builtin_amdgcn_sbfe((int)Dhi, (k) - 32, 1);          \
                         const uint32_t bl_ = PUSH_BC(alo, (k)), bh_ = PUSH_BC(ahi, (k));                   \
@@ -1423,7 +1362,7 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
 #undef PUSH_LO
 #undef PUSH_HI
 #undef PUSH_BC
-        if (HM_PRIO_PUSH && !HM_PRIO_FOLD) __builtin_amdgcn_s_setprio(0);
+        if (HM_PRIO_PUSH) __builtin_amdgcn_s_setprio(0);
     }
     const u64 anc = hv ? ((((u64)ahi << 32) | alo) & ~(1ull << lane)) : 0ull;   // strict ancestors
     if (hv) L.anc[lane] = anc;
@@ -1474,9 +1413,6 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
         h_own_row = shfl32(h_own_row, (int)ai); h_dep0 = shfl32(my_dep0, (int)ai); h_nd = shfl32(c.n_deps, (int)ai);
     }
     suspect |= hv && h_own_row != 0;
-#ifdef HM_DEV_NOFOLD
-    suspect = false;                    // dev-only timing build: skips the literal-fold check
-#endif
     if (suspect) {
         const FoldView fv = {L.anc, L.chain, L.first, L.base, L.deps, L.hist_of};
         if (fold_differs(fv, h_dep0, h_nd, hactor, hseq)) lds_or(L.flags, FL_UNSUPPORTED);
@@ -1500,7 +1436,6 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
 
     STAMP(L, 5);
     if constexpr (DIET) lane = fresh_lane();
-    if (HM_PRIO_FOLD && !HM_PRIO_K2) __builtin_amdgcn_s_setprio(0);
     if (HM_PRIO_K2) __builtin_amdgcn_s_setprio(HM_PRIO_K2);
     if (HM_ABLATE & 2) return OUT_UNSUPPORTED;
     // ---------------- K2: ops (lane + 64*t) ----------------
@@ -1753,11 +1688,8 @@ __device__ __forceinline__ Outcome merge_doc_small(const SmallParams &p, const S
     if constexpr (DIET) lane = fresh_lane();
     if (HM_ABLATE & 256) return OUT_UNSUPPORTED;
     if constexpr (LISTS) {
-        if (doc_lists) {
-            if (HM_PRIO_K3) __builtin_amdgcn_s_setprio(HM_PRIO_K3);
+        if (doc_lists)
             rga_order<OPL>(L, R, O, oreg, oobj, opar, oact, oelem, oarr, oh, p.res_epos ? p.res_epos + doc.reg_off : nullptr);
-            if (HM_PRIO_K3) __builtin_amdgcn_s_setprio(0);
-        }
     }
     // counters: an inc adds to every surviving counter set that is its ancestor.
     // JS numbers: an integer counter is exact only while |base| + sum|inc| <= 2^53; with at
@@ -1842,23 +1774,9 @@ __device__ __forceinline__ SurvRows<OPL> surv_rows(const SmallParams &p, const S
     return o;
 }
 
-// one 16-byte output row (non-temporal under HM_NT_OUT: written once, never read by this kernel)
-__device__ __forceinline__ void st16(void *dst, uint4 v) {
-#if HM_NT_OUT
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    const v4u x = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(x, reinterpret_cast<v4u *>(dst));
-#else
-    *reinterpret_cast<uint4 *>(dst) = v;
-#endif
-}
-__device__ __forceinline__ void st4(void *dst, uint32_t v) {
-#if HM_NT_OUT
-    __builtin_nontemporal_store(v, reinterpret_cast<uint32_t *>(dst));
-#else
-    *reinterpret_cast<uint32_t *>(dst) = v;
-#endif
-}
+// one 16-byte output row / one output word (plain stores: non-temporal ones measured no gain)
+__device__ __forceinline__ void st16(void *dst, uint4 v) { *reinterpret_cast<uint4 *>(dst) = v; }
+__device__ __forceinline__ void st4(void *dst, uint32_t v) { *reinterpret_cast<uint32_t *>(dst) = v; }
 // The result row of a document that was not merged here (the rare outcomes).  Its words are made
 // opaque inside the branch: as plain constants the compiler built the rows
 // once, ahead of the document loop, and held them in VGPR tuples across every merge.
@@ -1913,11 +1831,9 @@ __device__ __forceinline__ void write_outputs(const SmallParams &p, const SmallL
     // Every table's address is a wave-uniform row base (the table plus the document's offset, on
     // the scalar unit) plus the lane's 32-bit part: the stores take the scalar-base form, with
     // no 64-bit address arithmetic per lane.
-#if HM_KARG_RELOAD
-    if constexpr (DIET && HM_KARG_BATCH)
+    if constexpr (DIET)
         asm volatile("" :: "s"(p.res_docs), "s"(p.res_clock), "s"(p.res_back_clock), "s"(p.res_heads), "s"(p.res_hist),
                      "s"(p.res_all_deps), "s"(p.res_regs), "s"(p.res_surv));     // (see the document loop)
-#endif
     hm_reg_result *regs = p.res_regs + doc.reg_off;
     for_rows<C::NR, LISTS>(lane, R, [&](uint32_t r) {
         if constexpr (LISTS) {
@@ -1972,7 +1888,6 @@ __device__ __forceinline__ void write_outputs(const SmallParams &p, const SmallL
     }
 }
 
-#if HM_ASYNC_NEXT
 // A lower bound on the store instructions write_outputs issues for a document merged OK (each
 // term names the stores above it counts): the register rows (one dwordx4 per 64 registers),
 // the allDeps rows (two dwordx4 at S = 8, one at S = 4, at least one otherwise, when there are
@@ -2001,7 +1916,6 @@ __device__ __forceinline__ void pad_stores(const SmallParams &p, const hm_doc_ro
     for (uint32_t c = ok ? out_stores_min<OPL>(p, doc, st) : 0u; c < HM_ASYNC_STORES; c++)      // (wave-uniform)
         asm volatile("global_store_dword %0, %1, off" :: "v"(pad), "v"(zero) : "memory");
 }
-#endif
 
 template <int OPL, bool LISTS, int CLS>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(OPL >= 3 ? (LISTS ? (OPL == 3 ? HM_WAVES_PER_EU_LIST3 : HM_WAVES_PER_EU_OPL4 - 1) : HM_WAVES_PER_EU_OPL4)
@@ -2013,13 +1927,11 @@ void merge_small_kernel(SmallParams p) {
     SmallLds L;
     small_carve((LDS uint8_t *)lds_raw, WAVE * OPL, C::NR, C::NO, C::ND, LISTS, true, &L);
     p.cap_regs = C::NR; p.cap_objs = C::NO; p.cap_deps = C::ND;     // (the loop reads the C:: constants)
-#if HM_KARG_RELOAD
     // the loop reads the launch parameters through an opaque pointer to the kernarg segment:
     // each document re-loads the fields it uses (scalar loads) instead of holding ~50 SGPRs of
     // them across the loop, where they were spilled to VGPR lanes (readlane / writelane VALU)
     typedef __attribute__((address_space(4))) const SmallParams KParams;
     KParams *kp = (KParams *)__builtin_amdgcn_kernarg_segment_ptr();
-#endif
     // workgroups are dealt round-robin over the 8 XCDs (speed only, MI355X_MICROARCH.md): give
     // the workgroups of one XCD consecutive documents, so the 128 B lines a document boundary
     // splits in every table are read and written through one L2 instead of two
@@ -2039,18 +1951,18 @@ void merge_small_kernel(SmallParams p) {
     }
     wave_sync();
     for (;;) {
-#if HM_KARG_RELOAD
         asm volatile("" : "+s"(kp));
         const SmallParams &p = *(const SmallParams *)kp;
         // The fields a phase reads are requested together where the phase begins (here, ahead of
         // the next document's row loads, and ahead of the output stores): left to their uses they
         // were one scalar load per uniform branch, each waited for at once, i.e. a scalar-cache
         // round trip per field on the wave's path.
-        if constexpr (DIET && HM_KARG_BATCH)
+        if constexpr (DIET)
             asm volatile("" :: "s"(p.n_docs), "s"(p.a_stride), "s"(p.general_only), "s"(p.docs), "s"(p.min_clock), "s"(p.doc_slot));
-#endif
-        // software pipeline over this wave's documents: the next document's rows are
-        // loaded before this document's stores and staged to LDS after them
+        // software pipeline over this wave's documents: the next document's rows are loaded
+        // after this document's merge and before its stores, and staged to LDS after them
+        // (staged before the stores, the stores waited in write_outputs on reused registers:
+        // C4 2.38 -> 2.44 ms)
         const uint32_t dn = d + gridDim.x;
         const bool more = dn < p.n_docs;
         bool dokn = true;
@@ -2069,15 +1981,8 @@ void merge_small_kernel(SmallParams p) {
             __builtin_memcpy(&docn, w, sizeof docn);
         };
         Rows next;
-#if HM_ASYNC_NEXT
         AsyncRows anext;
-        constexpr bool ASY = OPL <= HM_ASYNC_MAX_OPL && !HM_PREFETCH_EARLY && !HM_STAGE_FIRST;
-#else
-        constexpr bool ASY = false;
-#endif
-#if HM_PREFETCH_EARLY
-        if (more) { take_docn(); dokn = check_doc(p, docn); next = load_rows<OPL>(p, docn); }
-#endif
+        constexpr bool ASY = OPL <= HM_ASYNC_MAX_OPL;
         const bool in_env = doc.n_changes <= 64 && doc.n_actors <= NA_MAX && doc.n_ops <= WAVE * OPL && doc.n_ops < 256 &&
                             doc.n_regs <= C::NR && doc.n_objs <= C::NO && doc.n_objs >= 1 &&
                             doc.n_deps <= C::ND && !p.general_only;
@@ -2103,72 +2008,42 @@ void merge_small_kernel(SmallParams p) {
         // a load may still write.
         const uint32_t lane_io = lane_id<DIET>();
         uint32_t mcmp = oc == OUT_OK ? min_cmp_of(p, L, doc, mc, lane_io) : 0u;
-#if HM_FENCE_MCMP
         // computed here, not sunk to its use in write_outputs: there its wait for the minimumClock
         // row (s_waitcnt vmcnt(0)) would also wait for the next document's row loads issued below
         asm volatile("" : "+s"(mcmp) :: "memory");
-#endif
-#if HM_ASYNC_NEXT
         // The next document's row words are waited for here on every path, not only under `more`
         // below: the compiler tracks outstanding loads per register without regard to the branch
         // conditions, and a load it believes may still be in flight makes it wait for everything
         // (vmcnt(0): the row loads issued below included) wherever the register is next written,
         // which the output phase does.
         asm volatile("" : "+v"(docw));
-#endif
-#if !HM_PREFETCH_EARLY
         if (more) {
-#if HM_KARG_RELOAD
-            if constexpr (DIET && HM_KARG_BATCH)
+            if constexpr (DIET)
                 asm volatile("" :: "s"(p.changes), "s"(p.deps), "s"(p.ops), "s"(p.a_stride), "s"(p.lim_changes), "s"(p.lim_deps),
                              "s"(p.lim_ops), "s"(p.lim_regs));
-#endif
             take_docn();
             dokn = check_doc(p, docn);
-#if HM_ASYNC_NEXT
             if constexpr (ASY) anext = load_rows_async<OPL, LISTS>(p, docn, lane_io);
-            else
-#endif
-            next = load_rows<OPL>(p, docn);
+            else next = load_rows<OPL>(p, docn);
         }
-#endif
         STAMP(L, 12);
         if (HM_PRIO_IO) __builtin_amdgcn_s_setprio(HM_PRIO_IO);
         const SurvRows<OPL> sv = surv_rows<OPL, LISTS>(p, L, st, lane_io);
-#if HM_STAGE_FIRST
-        // the next document's rows go to LDS before this document's stores are issued: a wait
-        // for a load also waits for every older store (vmcnt counts both in issue order), so
-        // staging after the stores waited for all of them; now nothing waits for the stores
-        // until the next document's merge has run
-        wave_sync();
-        if (more) stage_rows<OPL, LISTS, DIET, C>(p, L, docn, next);
-        STAMP(L, 11);
         write_outputs<OPL, LISTS, DIET, C>(p, L, d, ds, doc, oc, st, mcmp, sv, lane_io);
-        if (HM_PRIO_IO) __builtin_amdgcn_s_setprio(0);
-        wave_sync();
-        STAMP(L, 10);
-        if (!more) break;
-#else
-        write_outputs<OPL, LISTS, DIET, C>(p, L, d, ds, doc, oc, st, mcmp, sv, lane_io);
-#if HM_ASYNC_NEXT
         if constexpr (ASY) { if (more) pad_stores<OPL>(p, doc, st, ds, oc == OUT_OK); }
-#endif
         wave_sync();
         STAMP(L, 10);
         if (!more) break;
-#if HM_ASYNC_NEXT
         if constexpr (ASY) {
             next = take_rows_async<OPL, DIET>(anext, docn);
 #if HM_ASYNC_CHECK
             async_check<OPL>(p, docn, next);
 #endif
         }
-#endif
         stage_rows<OPL, LISTS, DIET, C>(p, L, docn, next);
         if (HM_PRIO_IO) __builtin_amdgcn_s_setprio(0);
         wave_sync();
         STAMP(L, 11);
-#endif
         w0 = make_uint2(next.c01.x, next.c01.y); w1 = make_uint2(next.c01.z, next.c01.w); w2 = next.c2;
         d = dn;
         doc = docn;
@@ -2211,7 +2086,7 @@ __global__ void clock_intersection_kernel(const uint32_t *a, const uint32_t *b, 
 // (check builds) documents whose rows were loaded asynchronously and checked, and those whose
 // asynchronous rows differed from the counted loads' (both since the last reset)
 extern "C" int hm_debug_async_check(unsigned long long *out2, int reset) {
-#if HM_ASYNC_CHECK && HM_ASYNC_NEXT
+#if HM_ASYNC_CHECK
     if (!out2 || hipDeviceSynchronize() != hipSuccess) return -1;
     if (hipMemcpyFromSymbol(&out2[0], HIP_SYMBOL(hm::hm_async_checked), 8) != hipSuccess ||
         hipMemcpyFromSymbol(&out2[1], HIP_SYMBOL(hm::hm_async_bad), 8) != hipSuccess) return -1;
@@ -2256,6 +2131,23 @@ size_t hm_small_lds_bytes(uint32_t opl, uint32_t cls, bool lists, bool counters)
     return cls == 0 ? carve_of<0>(opl, lists, counters) : cls == 2 ? carve_of<2>(opl, lists, counters) : carve_of<1>(opl, lists, counters);
 }
 
+// The instantiation a launch of (opl, cls, lists) runs: op rows per lane outside 1-3 take the
+// 4-row one, a class that is neither 0 nor 2 the class-1 carve.
+typedef void (*SmallKernel)(SmallParams);
+template <bool LISTS, int CLS> static SmallKernel small_kernel_opl(uint32_t opl) {
+    switch (opl) {
+    case 1: return hm::merge_small_kernel<1, LISTS, CLS>;
+    case 2: return hm::merge_small_kernel<2, LISTS, CLS>;
+    case 3: return hm::merge_small_kernel<3, LISTS, CLS>;
+    default: return hm::merge_small_kernel<4, LISTS, CLS>;
+    }
+}
+static SmallKernel hm_small_kernel(uint32_t opl, uint32_t cls, bool lists) {
+    if (cls == 0) return lists ? small_kernel_opl<true, 0>(opl) : small_kernel_opl<false, 0>(opl);
+    if (cls == 2) return lists ? small_kernel_opl<true, 2>(opl) : small_kernel_opl<false, 2>(opl);
+    return lists ? small_kernel_opl<true, 1>(opl) : small_kernel_opl<false, 1>(opl);
+}
+
 // resident 1-wave workgroups per CU for the instantiation a launch will use (VGPRs and LDS)
 uint32_t hm_small_occupancy(uint32_t opl, uint32_t cls, bool lists, bool counters) {
     const size_t lds = hm_small_lds_bytes(opl, cls, lists, counters);
@@ -2264,26 +2156,14 @@ uint32_t hm_small_occupancy(uint32_t opl, uint32_t cls, bool lists, bool counter
     // runs its documents serially at the end): also bound by the LDS with the allocation rounded
     // to 512 bytes (a 13,376-byte carve reported 12 workgroups per CU and ran as if 11 fit)
     const int by_lds = (int)(160u * 1024u / ((lds + 511) & ~(size_t)511));
-#define HM_OCC(O_, L_, C_) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, hm::merge_small_kernel<O_, L_, C_>, WAVE, lds)
-#define HM_OCC_OPL(L_, C_) switch (opl) { case 1: HM_OCC(1, L_, C_); break; case 2: HM_OCC(2, L_, C_); break; case 3: HM_OCC(3, L_, C_); break; default: HM_OCC(4, L_, C_); }
-    if (cls == 0)      { if (lists) { HM_OCC_OPL(true, 0) } else { HM_OCC_OPL(false, 0) } }
-    else if (cls == 2) { if (lists) { HM_OCC_OPL(true, 2) } else { HM_OCC_OPL(false, 2) } }
-    else               { if (lists) { HM_OCC_OPL(true, 1) } else { HM_OCC_OPL(false, 1) } }
-#undef HM_OCC_OPL
-#undef HM_OCC
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, hm_small_kernel(opl, cls, lists), WAVE, lds);
     if (n > by_lds) n = by_lds;
     return n > 0 ? (uint32_t)n : 1u;
 }
 
 hipError_t hm_launch_small(const SmallParams &p, uint32_t opl, uint32_t cls, bool lists, uint32_t grid, hipStream_t s) {
     const size_t lds = hm_small_lds_bytes(opl, cls, lists, p.counters != 0);
-#define HM_LAUNCH(O_, L_, C_) hipLaunchKernelGGL((hm::merge_small_kernel<O_, L_, C_>), dim3(grid), dim3(WAVE), lds, s, p)
-#define HM_OPL(L_, C_) switch (opl) { case 1: HM_LAUNCH(1, L_, C_); break; case 2: HM_LAUNCH(2, L_, C_); break; case 3: HM_LAUNCH(3, L_, C_); break; default: HM_LAUNCH(4, L_, C_); }
-    if (cls == 0)      { if (lists) { HM_OPL(true, 0) } else { HM_OPL(false, 0) } }
-    else if (cls == 2) { if (lists) { HM_OPL(true, 2) } else { HM_OPL(false, 2) } }
-    else               { if (lists) { HM_OPL(true, 1) } else { HM_OPL(false, 1) } }
-#undef HM_OPL
-#undef HM_LAUNCH
+    hipLaunchKernelGGL(hm_small_kernel(opl, cls, lists), dim3(grid), dim3(WAVE), lds, s, p);
     return hipGetLastError();
 }
 

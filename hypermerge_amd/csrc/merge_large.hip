@@ -19,18 +19,10 @@
 #include <stdint.h>
 #include "../../include/hypermerge_amd.h"
 #include "merge_kernels.h"
+#include "wave.h"
 
-#ifndef HML_KARG_RELOAD
-#define HML_KARG_RELOAD 1   // merge_large_kernel: launch parameters re-read per document (see the kernel)
-#endif
-#ifndef HML_WGS_PER_CU
-#define HML_WGS_PER_CU 1   // workgroups per CU: 16 waves per CU split into this many documents
-#endif
-#ifndef HML_LWG
-#define HML_LWG (1024 / HML_WGS_PER_CU)   // threads per workgroup
-#endif
-#define LWG HML_LWG
-#define HML_WPE (LWG * HML_WGS_PER_CU / 256)   // waves per SIMD (register budget 512 / HML_WPE)
+#define LWG 1024     // threads per workgroup: one workgroup (one document at a time) per CU, 16 waves
+#define HML_WPE 4    // waves per SIMD (register budget 512 / HML_WPE)
 #define LA_MAX 64    // objects whose tables live in LDS (Shared) rather than the pool
 #define LA_ACT 256   // actors per document (HM_MAX_STRIDE): the per-actor tables in Shared
 // LDS arena per workgroup (u32 words).  One 1024-thread workgroup per CU owns 150 KB: a
@@ -39,20 +31,7 @@
 // (~300 KB for a C3 text document) cannot stay in an XCD's 4 MB L2 across its workgroups and
 // were re-fetched from HBM (7.4x the algorithmic bytes).  Documents whose L2 closure rows
 // (2·n·A + T words) or L4 Euler tour (E words, 16-bit links) fit run those phases out of LDS.
-#if HML_WGS_PER_CU == 1
 #define LARENA 38400
-#else
-#define LARENA (36864 / HML_WGS_PER_CU)
-#endif
-#ifndef HML_RES
-#define HML_RES 1       // 0: every document takes the pool L3/L4 (dev A/B builds)
-#endif
-#ifndef HML_STAGE
-#define HML_STAGE 1     // 0: L1/L2 read change / dep rows from HBM and keep the L1 table in the pool (dev A/B)
-#endif
-#ifndef HML_DOC_ATTR
-#define HML_DOC_ATTR __noinline__   // the general path: its own register allocation, off merge_doc_res's
-#endif
 // Explicit address spaces: LDS pointers -> ds_*, pool pointers -> global_* (a generic pointer
 // would compile to flat_* ops, which count against lgkmcnt too, so every LDS wait would also
 // wait for the outstanding pool loads, stores and atomics).
@@ -65,10 +44,6 @@
 #endif
 typedef unsigned long long u64;
 
-#ifndef HM_PAR_HIST
-#define HM_PAR_HIST 1   // 0: queued documents always take the serial queue emulation (dev A/B builds)
-#endif
-#define PH_ATTR __noinline__
 #ifndef HM_STAMPS
 #define HM_STAMPS 0     // diagnostic builds only: per-phase s_memtime shares (tools/lstamps.py); never timed
 #endif
@@ -135,12 +110,8 @@ __device__ __forceinline__ uint32_t fresh_tid() {
     asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"((uint32_t)threadIdx.x));
     return t;
 }
-// DPP lane moves (gfx9 encodings; lanes without a source read 0): inclusive sum / max over the
-// wave with row shifts and the row broadcasts — VALU only, no address, no LDS crossbar
-#define DPP_ROW_SHR(n) (0x110 + (n))
-#define DPP_WAVE_SHR1 0x138
-#define DPP_ROW_BCAST15 0x142
-#define DPP_ROW_BCAST31 0x143
+// DPP lane moves (wave.h): inclusive sum / max over the wave with row shifts and the row
+// broadcasts — VALU only, no address, no LDS crossbar
 __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x) {
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, DPP_ROW_SHR(1), 0xF, 0xF, false);
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, DPP_ROW_SHR(2), 0xF, 0xF, false);
@@ -286,7 +257,7 @@ __device__ __forceinline__ uint32_t block_excl_max(Shared &sh, uint32_t v) {
 // (block-uniform) when the serial emulation must run instead.
 // (not inlined: it runs for queued documents only; every argument by value, so the caller's
 // parameter block and scratch table stay in registers instead of a stack copy)
-__device__ PH_ATTR bool parallel_history(const hm_change_row *CH, const hm_dep_row *deps, Shared &sh,
+__device__ __noinline__ bool parallel_history(const hm_change_row *CH, const hm_dep_row *deps, Shared &sh,
                                          GLB uint32_t *C, GLB uint32_t *hx, GLB uint32_t *tab, GLB uint32_t *h2a,
                                          GLB int32_t *hist, uint32_t n, uint32_t A, uint32_t T) {
     const uint32_t tid = threadIdx.x;
@@ -800,9 +771,6 @@ __device__ __forceinline__ int l34_res(const SmallParams &p, Shared &sh, LDS uin
     // ---- outputs ----
     for (uint32_t q = tid; q < total; q += LWG) {
         const uint32_t k = s_op[q];
-#ifdef HML_DEBUG
-        if (k >= m) { printf("RES bad s_op doc %u q %u total %u k %u m %u nsurv %u n %u H %u\n", doc.reserved[0], q, total, k, m, nsurv, n, H); continue; }
-#endif
         const hm_op_row o = OP[k];
         hm_surv_result sr; sr.op = k; sr.vtag = o.vtag; sr.value = o.value;
         p.res_surv[doc.op_off + q] = sr;
@@ -1051,7 +1019,8 @@ __device__ __forceinline__ int merge_doc_res(const SmallParams &p, Shared &sh, L
     return l34_res(p, sh, ar, doc, sCH, lh, lh2a, H, T, stage_base, AS);
 }
 
-__device__ HML_DOC_ATTR Outcome merge_doc_large(const SmallParams &p, Shared &sh, LDS uint32_t *ar, const hm_doc_row &doc, uint32_t d,
+// (not inlined: the general path gets its own register allocation, off merge_doc_res's)
+__device__ __noinline__ Outcome merge_doc_large(const SmallParams &p, Shared &sh, LDS uint32_t *ar, const hm_doc_row &doc, uint32_t d,
                                    uint8_t *pool, u64 pool_bytes, u64 *pool_used, int32_t &H_out) {
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t n = doc.n_changes, A = doc.n_actors, m = doc.n_ops, R = doc.n_regs, O = doc.n_objs;
@@ -1070,7 +1039,7 @@ __device__ HML_DOC_ATTR Outcome merge_doc_large(const SmallParams &p, Shared &sh
     // they take at most a quarter of it: L1 and L2 read them several times each.  The L1 table
     // joins them in LDS when it and L2's closure rows fit below (ltab); otherwise the pool.
     const uint32_t nd = doc.n_deps;
-    const bool staged = HML_STAGE && 8 * (size_t)n + 2 * (size_t)nd <= LARENA / 4;
+    const bool staged = 8 * (size_t)n + 2 * (size_t)nd <= LARENA / 4;
     const uint32_t stage_base = staged ? (LARENA - (8 * n + 2 * nd)) & ~1u : LARENA;
     LDS hm_change_row *sCH = (LDS hm_change_row *)(ar + stage_base);
     LDS hm_dep_row *sDP = (LDS hm_dep_row *)(ar + stage_base + 6 * n);
@@ -1186,7 +1155,7 @@ __device__ HML_DOC_ATTR Outcome merge_doc_large(const SmallParams &p, Shared &sh
         for (uint32_t i = tid; i < T; i += LWG) X.tab[i] = lt[i];
         bsync();
     }
-    if (HM_PAR_HIST && parallel_history(CH, p.deps, sh, X.vc, X.hx, X.tab, X.h2a, X.hist, n, A, T)) {
+    if (parallel_history(CH, p.deps, sh, X.vc, X.hx, X.tab, X.h2a, X.hist, n, A, T)) {
         // history from (t, pass, arrival) without the serial queue emulation
     } else if (wave == 0) {
         // ---- exact emulation of addChange / applyQueuedOps; wave 0, wave-uniform control ----
@@ -2076,18 +2045,14 @@ __global__ __launch_bounds__(LWG) __attribute__((amdgpu_waves_per_eu(HML_WPE))) 
 #if HM_STAMPS
     if (tid <= HML_NSTAMP) hml_st[tid] = 0;
 #endif
-#if HML_KARG_RELOAD
     // the loop reads the launch parameters through an opaque pointer to the kernarg segment: a
     // document re-loads the fields it uses (scalar loads) rather than holding them in SGPRs
     // across the loop, where they were spilled to VGPR lanes (readlane / writelane VALU)
     typedef __attribute__((address_space(4))) const SmallParams KParams;
     KParams *kp = (KParams *)__builtin_amdgcn_kernarg_segment_ptr();
-#endif
     for (;;) {
-#if HML_KARG_RELOAD
         asm volatile("" : "+s"(kp));
         const SmallParams &p = *(const SmallParams *)kp;
-#endif
         if (tid == 0) claim = atomicAdd(p.large_cursor, 1u);
         bsync();
         const uint32_t ci = claim;
@@ -2101,7 +2066,7 @@ __global__ __launch_bounds__(LWG) __attribute__((amdgpu_waves_per_eu(HML_WPE))) 
 #endif
         int rc = RES_FALLBACK;
         const uint32_t dn = doc.n_changes, dd = doc.n_deps;
-        if (HML_RES && dn >= 1 && doc.n_actors <= 8 && doc.n_objs >= 1 && doc.n_objs <= LA_MAX && doc.n_ops < 65536 &&
+        if (dn >= 1 && doc.n_actors <= 8 && doc.n_objs >= 1 && doc.n_objs <= LA_MAX && doc.n_ops < 65536 &&
             doc.n_regs + doc.n_objs < 32767 && 8 * (size_t)dn + 2 * (size_t)dd <= LARENA / 4)
             rc = merge_doc_res(p, sh, arena, doc, H);
         const bool via_res = rc != RES_FALLBACK;   // (every change ready on arrival: nothing queued)
@@ -2194,9 +2159,7 @@ size_t hm_large_stack_bytes() {
 
 hipError_t hm_launch_large(const SmallParams &p, void *pool, size_t pool_bytes, unsigned long long *pool_used,
                            uint32_t grid, hipStream_t s) {
-#ifndef HML_RESIDENT
-#define HML_RESIDENT HML_WGS_PER_CU    // workgroups launched per CU (dev A/B builds launch fewer)
-#endif
-    hipLaunchKernelGGL(hml::merge_large_kernel, dim3(grid / 4 * HML_RESIDENT), dim3(LWG), 0, s, p, (uint8_t *)pool, (u64)pool_bytes, pool_used);
+    // (the caller's grid counts four 256-thread workgroups per CU: one LWG-thread workgroup each)
+    hipLaunchKernelGGL(hml::merge_large_kernel, dim3(grid / 4), dim3(LWG), 0, s, p, (uint8_t *)pool, (u64)pool_bytes, pool_used);
     return hipGetLastError();
 }

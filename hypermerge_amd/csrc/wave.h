@@ -1,9 +1,16 @@
 // wave.h — what one 64-lane wavefront does the same way in every device query (changes / past
 // kernels): a sum, an inclusive scan, and the bitmap tile that turns "selected history positions"
-// into history order.  Device only.  Nothing here holds a barrier: the call sites keep theirs.
+// into history order; and the DPP control words of the two merge kernels' own VALU-only scans.
+// Device only.  Nothing here holds a barrier: the call sites keep theirs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+// DPP lane moves (gfx9 encodings) for __builtin_amdgcn_update_dpp: lanes without a source read 0
+#define DPP_ROW_SHR(n) (0x110 + (n))
+#define DPP_WAVE_SHR1 0x138
+#define DPP_ROW_BCAST15 0x142
+#define DPP_ROW_BCAST31 0x143
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     for (uint32_t d = 32; d; d >>= 1) v += __shfl_xor(v, d);

@@ -1,4 +1,4 @@
-"""merge_small_kernel's asynchronous next-row loads (HM_ASYNC_NEXT: inline-asm loads waited for
+"""merge_small_kernel's asynchronous next-row loads (inline-asm loads waited for
 with a fixed vmcnt that leaves the current document's stores in flight) checked in the check
 build (libhmgpu_check.so, HM_ASYNC_CHECK): every document's asynchronously loaded rows are
 re-read with counted loads and compared on the device.  Runs the strides and op-row classes that

@@ -12,10 +12,14 @@
 // stores (one hm_store per actor-stride class 8/16/32/64/128/256: a document moves to a wider class
 // when a new actor outgrows its rows, its log rows re-submitted from the old store), and the
 // patch base (the document as the last patch left it).  One call = one applyChanges round
-// for every document of the call: decode on host threads, submit per class, wait, commit or
-// roll back each document (a throwing applyChanges leaves DocBackend.back unchanged), read
-// back only the registers the round's ops hit (every register when changes were queued), and
-// render each document's patch, opSet clock / deps and DocBackend.clock as JSON text.
+// for every document of the call, the phases of `struct Call` in apply()'s order: validate,
+// decode (on host threads), place (stride classes), merge_class (per class: handles, one batch
+// built, submitted, waited for), settle (a document whose merge failed rolls back — a throwing
+// applyChanges leaves DocBackend.back unchanged — and the others' reads are listed), read_regs
+// (net diffs: the registers the round's ops hit, every register when changes were queued),
+// read_history (op diffs: the applied changes in order), commit, release, render (each document's
+// patch, opSet clock / deps and DocBackend.clock, binary or JSON), verify, assemble; fail() from
+// any phase before commit applies the call to no store and rolls every document back.
 //
 // Content identity (Automerge's `Inconsistent reuse of sequence number` check, Immutable
 // `equals` of two changes with one (actor, seq)) is a 128-bit hash of each change's
@@ -1230,93 +1234,158 @@ struct Busy {
     ~Busy() { if (ok) ds->busy.store(false); }
 };
 
-int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t *doc_block, const uint32_t *docs, uint32_t n,
-          hm_text *out) {
-    const uint32_t nd = ds->n_docs.load();
-    {
-        std::vector<uint8_t> seen(nd, 0);
-        for (uint32_t i = 0; i < n; i++) {
-            if (docs[i] >= nd || seen[docs[i]]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "bad or repeated docset document");
-            seen[docs[i]] = 1;
-            if (doc_block[i] > doc_block[i + 1]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "doc_block not ascending");
-        }
-    }
-    const bool prof = getenv("HM_DOCSET_PROFILE") != nullptr;
-    auto t0 = std::chrono::steady_clock::now();
-    auto mark = [&](const char *what) {
-        if (!prof) return;
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "[hm_docset] %-14s %9.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t0).count());
-        t0 = t;
-    };
-    std::vector<Round> R(n);
-    for (uint32_t i = 0; i < n; i++) { R[i].doc = docs[i]; R[i].b0 = doc_block[i]; R[i].b1 = doc_block[i + 1]; }
-    const uint32_t T = std::min<uint32_t>(ds->threads, std::max<uint32_t>(1, n / 64));
-    try {
-        par_for(n, T, [&](uint32_t lo, uint32_t hi, uint32_t) {
-            Scratch X;
-            for (uint32_t i = lo; i < hi; i++) {
-                DocSt &d = ds->doc(R[i].doc);
-                decode_round(d, R[i], data, bo, X);
-                if (R[i].status != HM_OK) { rollback(d, R[i]); R[i].started = false; }
-            }
-        });
-    } catch (...) {
-        // a decode ran out of memory: every document whose decode started goes back
-        for (uint32_t i = 0; i < n; i++) if (R[i].started) rollback(ds->doc(R[i].doc), R[i]);
-        throw;
-    }
-    mark("decode");
-    // placement: a document lives in the narrowest class that holds its actors
-    std::vector<std::vector<uint32_t>> by_cls(N_CLASS);
-    for (uint32_t i = 0; i < n; i++) {
-        Round &x = R[i];
-        if (x.status != HM_OK) continue;
-        DocSt &d = ds->doc(x.doc);
-        uint8_t c = class_for(x.n_actors);
-        if (d.cls != NO_CLASS && d.cls > c) c = d.cls;
-        x.cls = c;
-        x.placed = d.cls == NO_CLASS;
-        x.moved = !x.placed && c != d.cls;
-        x.handle = d.handle;
-        by_cls[c].push_back(i);
-    }
-    struct ClsOut {
-        std::vector<hm_doc_result> res;
-        std::vector<uint32_t> clock, back, heads;
-        uint64_t id = 0;
-        bool sub = false, done = false;                      // submitted / waited (applied on the device)
-    };
-    std::vector<ClsOut> co(N_CLASS);
-    uint64_t call_routing[3] = {0, 0, 0};                      // this call's routing (ds->routing once it commits)
-    int rc = HM_OK;
+// what one class's batch of a call left behind
+struct ClsOut {
+    std::vector<hm_doc_result> res;
+    std::vector<uint32_t> clock, back, heads;
+    uint64_t id = 0;
+    bool sub = false, done = false;                          // submitted / waited (applied on the device)
+};
+
+// this call's changes alone (updateClock(changes))
+void round_clock(const Round &x, uint32_t *rc) {
+    for (uint32_t a = 0; a < HM_MAX_STRIDE; a++) rc[a] = 0;
+    for (const hm_change_row &c : x.ch) if (c.actor < HM_MAX_STRIDE && c.seq > rc[c.actor]) rc[c.actor] = c.seq;
+}
+
+// One hm_docset_apply call: what the call holds, and one member function per phase.  apply()
+// below runs the phases in order.  All-or-nothing: until commit() a document's host state has
+// changed only in what rollback() (past the round's snapshot, Round::s_*) and fail() take back,
+// and every applied batch can be undone; from commit() on nothing fails the call.
+struct Call {
+    hm_docset *ds;
+    const uint8_t *data;
+    const uint64_t *bo;
+    const uint32_t *doc_block, *docs;
+    const uint32_t n;
+    std::vector<Round> R;
+    uint32_t T = 1;                                          // host threads of the decode and the commit
+    std::vector<uint32_t> by_cls[N_CLASS];                   // per class: its rounds of the call (indices into R)
+    ClsOut co[N_CLASS];
+    uint64_t call_routing[3] = {0, 0, 0};                    // this call's routing (ds->routing once it commits)
+    // released handles (a moved document's old one, a fresh one its document does not keep) go
+    // back to their store as empty documents (hm_doc_reset) and are reused by later calls; their
+    // rows are reclaimed when the store compacts
+    std::vector<uint32_t> rel[N_CLASS];
+    // net diffs: the register requests per class (document handle, register), their rows and survivors
+    std::vector<uint32_t> qdocs[N_CLASS], qregs[N_CLASS];
+    uint32_t cap[N_CLASS] = {};
+    std::vector<hm_reg_result> rrows[N_CLASS];
+    std::vector<hm_surv_result> rsurv[N_CLASS];
+    // op diffs: the rounds that read their history slice, per class, and the slices (applied
+    // changes in application order, their allDeps rows)
+    std::vector<uint32_t> hreq[N_CLASS], hlog[N_CLASS], had[N_CLASS];
+    bool exotic = false;                                     // a binary call that falls back to JSON
     // fault injection for the tests (HM_DOCSET_INJECT_FAIL=wait:<k> fails the call after the k-th
     // class's batch is applied, =read after every class's; the call must then be undone everywhere)
     const char *inj = getenv("HM_DOCSET_INJECT_FAIL");
     const int inj_wait = inj && !strncmp(inj, "wait:", 5) ? atoi(inj + 5) : -1;
     const bool inj_read = inj && !strcmp(inj, "read");
     int n_waited = 0;
-    for (uint32_t c = 0; c < N_CLASS && rc == HM_OK; c++) {
+    const bool prof = getenv("HM_DOCSET_PROFILE") != nullptr;    // a line per mark()
+    std::chrono::steady_clock::time_point t0;
+    void mark(const char *what) {
+        if (!prof) return;
+        const auto t = std::chrono::steady_clock::now();
+        fprintf(stderr, "[hm_docset] %-14s %9.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t0).count());
+        t0 = t;
+    }
+    int validate() {
+        const uint32_t nd = ds->n_docs.load();
+        std::vector<uint8_t> seen(nd, 0);
+        for (uint32_t i = 0; i < n; i++) {
+            if (docs[i] >= nd || seen[docs[i]]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "bad or repeated docset document");
+            seen[docs[i]] = 1;
+            if (doc_block[i] > doc_block[i + 1]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "doc_block not ascending");
+        }
+        t0 = std::chrono::steady_clock::now();               // (the profile clock starts at the decode)
+        return HM_OK;
+    }
+    // every document's blocks -> rows, on host threads; a document whose blocks do not decode goes
+    // back at once (its round keeps the status)
+    void decode() {
+        R.resize(n);
+        for (uint32_t i = 0; i < n; i++) { R[i].doc = docs[i]; R[i].b0 = doc_block[i]; R[i].b1 = doc_block[i + 1]; }
+        T = std::min<uint32_t>(ds->threads, std::max<uint32_t>(1, n / 64));
+        try {
+            par_for(n, T, [&](uint32_t lo, uint32_t hi, uint32_t) {
+                Scratch X;
+                for (uint32_t i = lo; i < hi; i++) {
+                    DocSt &d = ds->doc(R[i].doc);
+                    decode_round(d, R[i], data, bo, X);
+                    if (R[i].status != HM_OK) { rollback(d, R[i]); R[i].started = false; }
+                }
+            });
+        } catch (...) {
+            // a decode ran out of memory: every document whose decode started goes back
+            for (uint32_t i = 0; i < n; i++) if (R[i].started) rollback(ds->doc(R[i].doc), R[i]);
+            throw;
+        }
+    }
+    // placement: a document lives in the narrowest class that holds its actors
+    void place() {
+        for (uint32_t i = 0; i < n; i++) {
+            Round &x = R[i];
+            if (x.status != HM_OK) continue;
+            DocSt &d = ds->doc(x.doc);
+            uint8_t c = class_for(x.n_actors);
+            if (d.cls != NO_CLASS && d.cls > c) c = d.cls;
+            x.cls = c;
+            x.placed = d.cls == NO_CLASS;
+            x.moved = !x.placed && c != d.cls;
+            x.handle = d.handle;
+            by_cls[c].push_back(i);
+        }
+    }
+    // `fresh` handles of class c for its placed and moved documents: released ones first, then new ones
+    int take_handles(uint32_t c, hm_store *st, uint32_t fresh, std::vector<uint32_t> &fh) {
+        std::vector<uint32_t> &fl = ds->free_h[c];
+        const size_t k = std::min<size_t>(fresh, fl.size());
+        fh.assign(fl.end() - k, fl.end());
+        fl.resize(fl.size() - k);
+        uint32_t h0 = 0;
+        int rc;
+        if (fresh > k && (rc = hm_doc_open_n(st, fresh - (uint32_t)k, &h0))) { fl.insert(fl.end(), fh.begin(), fh.end()); return rc; }
+        ds->opened[c] += fresh - (uint32_t)k;
+        for (uint32_t j = 0; j < fresh - k; j++) fh.push_back(h0 + j);
+        return HM_OK;
+    }
+    // a moved document's whole log: its rows from the old store, ranks re-mapped to this round's,
+    // appended to the new class's batch
+    int moved_log(const Round &x, const DocSt &d, std::vector<hm_change_row> &ch, std::vector<hm_dep_row> &dp,
+                  std::vector<hm_op_row> &op) {
+        const uint32_t d0 = (uint32_t)dp.size(), o0 = (uint32_t)op.size();
+        ds->stat[2]++;
+        hm_doc_info_t inf;
+        hm_store *old = ds->stores[d.cls];
+        int rc = hm_doc_info(old, d.handle, &inf);
+        if (rc) return rc;
+        std::vector<hm_change_row> lc(inf.n_changes);
+        std::vector<hm_dep_row> ld(inf.n_deps);
+        std::vector<hm_op_row> lo(inf.n_ops);
+        if ((rc = hm_doc_log(old, d.handle, lc.data(), ld.data(), lo.data()))) return rc;
+        for (auto &cr : lc) {
+            if (!x.remap.empty() && cr.actor < x.remap.size()) cr.actor = x.remap[cr.actor];
+            cr.dep_off += d0; cr.op_first += o0;
+            ch.push_back(cr);
+        }
+        for (auto &dr : ld) { if (!x.remap.empty() && dr.actor < x.remap.size()) dr.actor = x.remap[dr.actor]; dp.push_back(dr); }
+        op.insert(op.end(), lo.begin(), lo.end());
+        return HM_OK;
+    }
+    // class c's documents of the call as one batch: handles, build, submit, wait.  A status other
+    // than HM_OK fails the call (fail()): co[c].sub / .done say how far the batch got.
+    int merge_class(uint32_t c) {
         auto &rows = by_cls[c];
-        if (rows.empty()) continue;
         hm_store *st;
-        if ((rc = store_of(ds, c, &st))) break;
+        int rc = store_of(ds, c, &st);
+        if (rc) return rc;
         const uint32_t S = STRIDES[c];
-        // fresh handles for placed and moved documents: released ones first, then new ones
         uint32_t fresh = 0;
         for (uint32_t i : rows) fresh += R[i].placed || R[i].moved;
         std::vector<uint32_t> fh;
         size_t next_fh = 0;
-        {
-            std::vector<uint32_t> &fl = ds->free_h[c];
-            const size_t k = std::min<size_t>(fresh, fl.size());
-            fh.assign(fl.end() - k, fl.end());
-            fl.resize(fl.size() - k);
-            uint32_t h0 = 0;
-            if (fresh > k && (rc = hm_doc_open_n(st, fresh - (uint32_t)k, &h0))) { fl.insert(fl.end(), fh.begin(), fh.end()); break; }
-            ds->opened[c] += fresh - (uint32_t)k;
-            for (uint32_t j = 0; j < fresh - k; j++) fh.push_back(h0 + j);
-        }
+        if ((rc = take_handles(c, st, fresh, fh))) return rc;
         std::vector<hm_doc_row> drows(rows.size());
         std::vector<hm_change_row> ch;
         std::vector<hm_dep_row> dp;
@@ -1343,22 +1412,7 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
             if (x.placed || x.moved) { x.handle = fh[next_fh++]; x.fresh = true; }
             hand[k] = x.handle;
             if (x.moved) {
-                // the whole log moves: its rows from the old store, ranks re-mapped to this round's
-                ds->stat[2]++;
-                hm_doc_info_t inf;
-                hm_store *old = ds->stores[d.cls];
-                if ((rc = hm_doc_info(old, d.handle, &inf))) break;
-                std::vector<hm_change_row> lc(inf.n_changes);
-                std::vector<hm_dep_row> ld(inf.n_deps);
-                std::vector<hm_op_row> lo(inf.n_ops);
-                if ((rc = hm_doc_log(old, d.handle, lc.data(), ld.data(), lo.data()))) break;
-                for (auto &cr : lc) {
-                    if (!x.remap.empty() && cr.actor < x.remap.size()) cr.actor = x.remap[cr.actor];
-                    cr.dep_off += d0; cr.op_first += o0;
-                    ch.push_back(cr);
-                }
-                for (auto &dr : ld) { if (!x.remap.empty() && dr.actor < x.remap.size()) dr.actor = x.remap[dr.actor]; dp.push_back(dr); }
-                op.insert(op.end(), lo.begin(), lo.end());
+                if ((rc = moved_log(x, d, ch, dp, op))) break;
             } else if (!x.placed && !x.remap.empty()) {
                 for (size_t a = 0; a < x.remap.size(); a++) remap[(size_t)k * S + a] = x.remap[a];
             }
@@ -1372,47 +1426,42 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
         }
         // handles taken but not handed to a document (a failed log read) are still empty
         ds->free_h[c].insert(ds->free_h[c].end(), fh.begin() + next_fh, fh.end());
-        if (rc) break;
+        if (rc) return rc;
         hm_batch b = {};
         b.n_docs = (uint32_t)rows.size(); b.n_changes = (uint32_t)ch.size(); b.n_deps = (uint32_t)dp.size(); b.n_ops = (uint32_t)op.size();
         b.a_stride = S;
         b.docs = drows.data(); b.changes = ch.data(); b.deps = dp.data(); b.ops = op.data();
-        if ((rc = hm_batch_submit(st, &b, hand.data(), any_remap ? remap.data() : nullptr, &co[c].id))) break;
-        co[c].sub = true;
         ClsOut &O = co[c];
+        if ((rc = hm_batch_submit(st, &b, hand.data(), any_remap ? remap.data() : nullptr, &O.id))) return rc;
+        O.sub = true;
         O.res.resize(rows.size()); O.clock.resize(rows.size() * (size_t)S); O.back.resize(rows.size() * (size_t)S);
         O.heads.resize(rows.size() * (size_t)S);
-        if ((rc = hm_batch_wait(st, O.id, O.res.data(), O.clock.data(), O.back.data(), O.heads.data()))) break;
+        if ((rc = hm_batch_wait(st, O.id, O.res.data(), O.clock.data(), O.back.data(), O.heads.data()))) return rc;
         O.sub = false;
         O.done = true;
-        {
-            uint32_t r3[3] = {0, 0, 0};
-            if (hm_store_last_routing(st, r3) == HM_OK)
-                for (int k = 0; k < 3; k++) call_routing[k] += r3[k];     // (counted once the call commits)
-        }
-        if (n_waited++ == inj_wait) { rc = hm_engine_fail(ds->e, HM_ERR_DEVICE, "injected failure (HM_DOCSET_INJECT_FAIL)"); break; }
+        uint32_t r3[3] = {0, 0, 0};
+        if (hm_store_last_routing(st, r3) == HM_OK)
+            for (int k = 0; k < 3; k++) call_routing[k] += r3[k];         // (counted once the call commits)
+        if (n_waited++ == inj_wait) return hm_engine_fail(ds->e, HM_ERR_DEVICE, "injected failure (HM_DOCSET_INJECT_FAIL)");
         for (uint32_t k = 0; k < rows.size(); k++) {
             Round &x = R[rows[k]];
             x.res = O.res[k];
             x.clock = O.clock.data() + (size_t)k * S; x.back = O.back.data() + (size_t)k * S; x.heads = O.heads.data() + (size_t)k * S;
         }
+        return HM_OK;
     }
-    // released handles (a moved document's old one, a fresh one its document does not keep) go
-    // back to their store as empty documents (hm_doc_reset) and are reused by later calls; their
-    // rows are reclaimed when the store compacts
-    std::vector<std::vector<uint32_t>> rel(N_CLASS);
-    auto release = [&]() {
+    void release() {
         for (uint32_t c = 0; c < N_CLASS; c++) {
             if (rel[c].empty()) continue;
             if (hm_doc_reset(ds->stores[c], rel[c].data(), (uint32_t)rel[c].size()) == HM_OK)
                 ds->free_h[c].insert(ds->free_h[c].end(), rel[c].begin(), rel[c].end());
             rel[c].clear();
         }
-    };
+    }
     // a call-level failure: the call is applied to no store — a store whose batch is in flight is
     // waited for, the batches already applied are undone (hm_batch_undo) — and every document of
     // the call rolls back on the host
-    auto fail_call = [&](int why) {
+    int fail(int why) {
         for (auto &v : rel) v.clear();                       // (every fresh handle is listed below)
         // a store whose batch cannot be waited for or undone keeps rows the host no longer
         // describes: the docset refuses every later call rather than diverge silently
@@ -1443,127 +1492,134 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
         release();
         if (lost) ds->broken = true;
         return why;
-    };
-    if (rc) return fail_call(rc);
-    mark("merge");
+    }
     // failed documents roll back; the registers and history slices each patch reads are requested
     // before any document's host state advances (a failed read then fails the call on every store)
-    std::vector<std::vector<uint32_t>> qdocs(N_CLASS), qregs(N_CLASS), hreq(N_CLASS);
-    std::vector<uint32_t> cap(N_CLASS, 0);
-    for (uint32_t i = 0; i < n; i++) {
-        Round &x = R[i];
-        DocSt &d = ds->doc(x.doc);
-        if (x.status == HM_OK && x.res.status != HM_OK) x.status = x.res.status;
-        if (x.status != HM_OK) {
-            if (x.cls != NO_CLASS) rollback(d, x);
-            if (x.placed) { d.cls = x.cls; d.handle = x.handle; }          // an empty document in its store
-            else if (x.moved) rel[x.cls].push_back(x.handle);               // it stays where it was
-            continue;
-        }
-        x.prev_hist = d.hist_len;
-        if (!ds->patches) continue;
-        if (ds->op_diffs) { hreq[x.cls].push_back(i); continue; }
-        x.full = !(d.n_queued == 0 && x.res.n_queued == 0 && x.res.hist_len - d.hist_len == x.ch.size());
-        x.q0 = (uint32_t)qregs[x.cls].size();
-        if (x.full) {
-            for (uint32_t g = 0; g < x.n_regs; g++) { qdocs[x.cls].push_back(x.handle); qregs[x.cls].push_back(g); }
-            ds->stat[4]++;
-        } else {
-            // the registers the round's set/del/link/inc ops hit, first hit first
-            std::vector<uint32_t> &q = qregs[x.cls];
-            for (const hm_op_row &o : x.op) {
-                if (o.action < HM_SET || o.reg == HM_NONE) continue;
-                bool dup = false;
-                for (uint32_t j = x.q0; j < q.size() && !dup; j++) dup = q[j] == o.reg;
-                if (dup) continue;
-                q.push_back(o.reg);
-                qdocs[x.cls].push_back(x.handle);
+    void settle() {
+        for (uint32_t i = 0; i < n; i++) {
+            Round &x = R[i];
+            DocSt &d = ds->doc(x.doc);
+            if (x.status == HM_OK && x.res.status != HM_OK) x.status = x.res.status;
+            if (x.status != HM_OK) {
+                if (x.cls != NO_CLASS) rollback(d, x);
+                if (x.placed) { d.cls = x.cls; d.handle = x.handle; }          // an empty document in its store
+                else if (x.moved) rel[x.cls].push_back(x.handle);               // it stays where it was
+                continue;
             }
-            ds->stat[3]++;
+            x.prev_hist = d.hist_len;
+            if (!ds->patches) continue;
+            if (ds->op_diffs) { hreq[x.cls].push_back(i); continue; }
+            x.full = !(d.n_queued == 0 && x.res.n_queued == 0 && x.res.hist_len - d.hist_len == x.ch.size());
+            x.q0 = (uint32_t)qregs[x.cls].size();
+            if (x.full) {
+                for (uint32_t g = 0; g < x.n_regs; g++) { qdocs[x.cls].push_back(x.handle); qregs[x.cls].push_back(g); }
+                ds->stat[4]++;
+            } else {
+                // the registers the round's set/del/link/inc ops hit, first hit first
+                std::vector<uint32_t> &q = qregs[x.cls];
+                for (const hm_op_row &o : x.op) {
+                    if (o.action < HM_SET || o.reg == HM_NONE) continue;
+                    bool dup = false;
+                    for (uint32_t j = x.q0; j < q.size() && !dup; j++) dup = q[j] == o.reg;
+                    if (dup) continue;
+                    q.push_back(o.reg);
+                    qdocs[x.cls].push_back(x.handle);
+                }
+                ds->stat[3]++;
+            }
+            x.q1 = (uint32_t)qregs[x.cls].size();
+            cap[x.cls] += x.res.n_surv;
         }
-        x.q1 = (uint32_t)qregs[x.cls].size();
-        cap[x.cls] += x.res.n_surv;
     }
-    std::vector<std::vector<hm_reg_result>> rrows(N_CLASS);
-    std::vector<std::vector<hm_surv_result>> rsurv(N_CLASS);
-    if (inj_read) return fail_call(hm_engine_fail(ds->e, HM_ERR_DEVICE, "injected failure (HM_DOCSET_INJECT_FAIL)"));
-    for (uint32_t c = 0; c < N_CLASS; c++) {
-        if (qregs[c].empty()) continue;
-        rrows[c].resize(qregs[c].size());
-        rsurv[c].resize(std::max<uint32_t>(cap[c], 1));
-        uint32_t got = 0;
-        rc = hm_store_read_regs(ds->stores[c], (uint32_t)qregs[c].size(), qdocs[c].data(), qregs[c].data(), rrows[c].data(),
-                                rsurv[c].data(), (uint32_t)rsurv[c].size(), &got);
-        if (rc) return fail_call(rc);
+    int read_regs() {
+        for (uint32_t c = 0; c < N_CLASS; c++) {
+            if (qregs[c].empty()) continue;
+            rrows[c].resize(qregs[c].size());
+            rsurv[c].resize(std::max<uint32_t>(cap[c], 1));
+            uint32_t got = 0;
+            const int rc = hm_store_read_regs(ds->stores[c], (uint32_t)qregs[c].size(), qdocs[c].data(), qregs[c].data(),
+                                              rrows[c].data(), rsurv[c].data(), (uint32_t)rsurv[c].size(), &got);
+            if (rc) return rc;
+        }
+        return HM_OK;
     }
     // op diffs: each document's history slice of this round (the changes the GPU applied, in
     // application order) with their allDeps rows
-    std::vector<std::vector<uint32_t>> hlog(N_CLASS), had(N_CLASS);
-    for (uint32_t c = 0; c < N_CLASS; c++) {
-        if (hreq[c].empty()) continue;
-        const uint32_t m = (uint32_t)hreq[c].size();
-        std::vector<uint32_t> hh(m), from(m), to(m), off(m + 1, 0);
-        for (uint32_t k = 0; k < m; k++) {
-            Round &x = R[hreq[c][k]];
-            hh[k] = x.handle;
-            to[k] = x.res.hist_len;
-            from[k] = x.prev_hist;
-            off[k + 1] = off[k] + (to[k] - from[k]);
-            x.h0 = off[k]; x.h1 = off[k + 1];
+    int read_history() {
+        for (uint32_t c = 0; c < N_CLASS; c++) {
+            if (hreq[c].empty()) continue;
+            const uint32_t m = (uint32_t)hreq[c].size();
+            std::vector<uint32_t> hh(m), from(m), to(m), off(m + 1, 0);
+            for (uint32_t k = 0; k < m; k++) {
+                Round &x = R[hreq[c][k]];
+                hh[k] = x.handle;
+                to[k] = x.res.hist_len;
+                from[k] = x.prev_hist;
+                off[k + 1] = off[k] + (to[k] - from[k]);
+                x.h0 = off[k]; x.h1 = off[k + 1];
+            }
+            hlog[c].resize(std::max(1u, off[m]));                 // (rounds that applied nothing: no rows)
+            had[c].resize(std::max<size_t>(1, (size_t)off[m] * STRIDES[c]));
+            const int rc = hm_store_read_history(ds->stores[c], m, hh.data(), from.data(), to.data(), off.data(), hlog[c].data(),
+                                                 had[c].data());
+            if (rc) return rc;
         }
-        hlog[c].resize(std::max(1u, off[m]));                 // (rounds that applied nothing: no rows)
-        had[c].resize(std::max<size_t>(1, (size_t)off[m] * STRIDES[c]));
-        rc = hm_store_read_history(ds->stores[c], m, hh.data(), from.data(), to.data(), off.data(), hlog[c].data(), had[c].data());
-        if (rc) return fail_call(rc);
+        return HM_OK;
     }
-    mark("read history");
     // commit: every successful document's host state advances with the device's (a call lists a
     // document once, so the documents advance in parallel; the released handles of moved documents
     // go to the shared lists first)
-    for (uint32_t i = 0; i < n; i++)
-        if (R[i].status == HM_OK && R[i].moved) { const DocSt &d = ds->doc(R[i].doc); rel[d.cls].push_back(d.handle); }
-    par_for(n, T, [&](uint32_t lo, uint32_t hi, uint32_t) {
-    for (uint32_t i = lo; i < hi; i++) {
-        Round &x = R[i];
-        if (x.status != HM_OK) continue;
-        DocSt &d = ds->doc(x.doc);
-        const uint32_t old_n_ops = d.n_ops;
-        d.cls = x.cls; d.handle = x.handle;
-        d.flags |= x.flags;
-        d.n_changes += (uint32_t)x.ch.size();
-        d.n_ops += (uint32_t)x.op.size();
-        d.hist_len = x.res.hist_len; d.n_queued = x.res.n_queued;
-        d.obj_type.resize(x.n_objs, NO_TYPE);
-        d.obj_emitted.resize(x.n_objs, 0);
-        d.sig.resize(x.n_regs, 0);
-        for (const hm_op_row &o : x.op)
-            if (o.action <= HM_MAKE_TEXT && o.obj < d.obj_type.size() && d.obj_type[o.obj] == NO_TYPE) d.obj_type[o.obj] = o.action;
-        if (ds->patches && ds->op_diffs) {
-            // the replay's view of the log (op indices are the store's: appended in order)
-            for (const hm_change_row &c : x.ch) {
-                d.ch_op0.push_back(old_n_ops + c.op_first);
-                d.op_seq.insert(d.op_seq.end(), c.n_ops, c.seq);
+    void commit() {
+        for (uint32_t i = 0; i < n; i++)
+            if (R[i].status == HM_OK && R[i].moved) { const DocSt &d = ds->doc(R[i].doc); rel[d.cls].push_back(d.handle); }
+        par_for(n, T, [&](uint32_t lo, uint32_t hi, uint32_t) {
+            for (uint32_t i = lo; i < hi; i++) {
+                Round &x = R[i];
+                if (x.status != HM_OK) continue;
+                DocSt &d = ds->doc(x.doc);
+                const uint32_t old_n_ops = d.n_ops;
+                d.cls = x.cls; d.handle = x.handle;
+                d.flags |= x.flags;
+                d.n_changes += (uint32_t)x.ch.size();
+                d.n_ops += (uint32_t)x.op.size();
+                d.hist_len = x.res.hist_len; d.n_queued = x.res.n_queued;
+                d.obj_type.resize(x.n_objs, NO_TYPE);
+                d.obj_emitted.resize(x.n_objs, 0);
+                d.sig.resize(x.n_regs, 0);
+                for (const hm_op_row &o : x.op)
+                    if (o.action <= HM_MAKE_TEXT && o.obj < d.obj_type.size() && d.obj_type[o.obj] == NO_TYPE) d.obj_type[o.obj] = o.action;
+                if (!(ds->patches && ds->op_diffs)) continue;
+                // the replay's view of the log (op indices are the store's: appended in order)
+                for (const hm_change_row &c : x.ch) {
+                    d.ch_op0.push_back(old_n_ops + c.op_first);
+                    d.op_seq.insert(d.op_seq.end(), c.n_ops, c.seq);
+                }
+                d.oplog.insert(d.oplog.end(), x.op.begin(), x.op.end());
+                d.rs.resize(x.n_regs);
+                d.el_op.resize(x.n_regs, HM_NONE);
+                d.el_in.resize(x.n_regs, 0);
+                d.el_blk.resize(x.n_regs, HM_NONE);
             }
-            d.oplog.insert(d.oplog.end(), x.op.begin(), x.op.end());
-            d.rs.resize(x.n_regs);
-            d.el_op.resize(x.n_regs, HM_NONE);
-            d.el_in.resize(x.n_regs, 0);
-            d.el_blk.resize(x.n_regs, HM_NONE);
-        }
+        });
+        for (int k = 0; k < 3; k++) ds->routing[k] += call_routing[k];
     }
-    });
-    for (int k = 0; k < 3; k++) ds->routing[k] += call_routing[k];
-    mark("commit");
-    release();
-    mark("read regs");
-    // render every document's patch and DocBackend.clock
-    auto round_clock = [](const Round &x, uint32_t *rc) {      // this call's changes alone (updateClock(changes))
-        for (uint32_t a = 0; a < HM_MAX_STRIDE; a++) rc[a] = 0;
-        for (const hm_change_row &c : x.ch) if (c.actor < HM_MAX_STRIDE && c.seq > rc[c.actor]) rc[c.actor] = c.seq;
-    };
-    bool exotic = false;
-    if (ds->binary) {
-        par_for(n, std::min<uint32_t>(ds->threads, std::max<uint32_t>(1, n / 128)), [&](uint32_t lo, uint32_t hi, uint32_t) {
+    // a round's diffs into either writer: the replay of its history slice (op diffs), or the net
+    // diffs of the registers it requested
+    template <typename W> void diffs(W &w, Round &x, DocSt &d) {
+        if (!ds->patches) return;
+        if (ds->op_diffs) {
+            Replay rp{d, STRIDES[x.cls]};
+            rp.round(w, hlog[x.cls].data() + x.h0, had[x.cls].data() + (size_t)x.h0 * STRIDES[x.cls], x.h1 - x.h0, x.touched);
+        } else if (x.q1 > x.q0) {
+            render_diffs(w, d, qregs[x.cls].data() + x.q0, rrows[x.cls].data() + x.q0, rsurv[x.cls].data(), x.q1 - x.q0);
+        } else render_diffs(w, d, nullptr, nullptr, nullptr, 0);
+    }
+    // every successful document's patch and DocBackend.clock: the binary pass, then the JSON pass
+    // (a JSON docset, or a binary call that met a lone surrogate: the binary pass already advanced
+    // the patch base, so the JSON is rebuilt from the binary documents — same diffs, same order)
+    void render() {
+        const uint32_t Tr = std::min<uint32_t>(ds->threads, std::max<uint32_t>(1, n / 128));
+        if (ds->binary) par_for(n, Tr, [&](uint32_t lo, uint32_t hi, uint32_t) {
             StrMap m;
             for (uint32_t i = lo; i < hi; i++) {
                 Round &x = R[i];
@@ -1579,30 +1635,18 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
                 round_clock(x, rc);
                 w.clock(rc, x.n_actors);
                 w.begin();
-                if (ds->patches && ds->op_diffs) {
-                    Replay rp{d, STRIDES[x.cls]};
-                    rp.round(w, hlog[x.cls].data() + x.h0, had[x.cls].data() + (size_t)x.h0 * STRIDES[x.cls], x.h1 - x.h0, x.touched);
-                } else if (ds->patches) {
-                    if (x.q1 > x.q0) render_diffs(w, d, qregs[x.cls].data() + x.q0, rrows[x.cls].data() + x.q0, rsurv[x.cls].data(), x.q1 - x.q0);
-                    else render_diffs(w, d, nullptr, nullptr, nullptr, 0);
-                }
+                diffs(w, x, d);
                 w.end();
             }
         });
-        for (auto &x : R) exotic |= x.bin.exotic;
-    }
-    if (!ds->binary || exotic) {
-        par_for(n, std::min<uint32_t>(ds->threads, std::max<uint32_t>(1, n / 128)), [&](uint32_t lo, uint32_t hi, uint32_t) {
+        if (ds->binary) for (auto &x : R) exotic |= x.bin.exotic;
+        if (ds->binary && !exotic) return;
+        par_for(n, Tr, [&](uint32_t lo, uint32_t hi, uint32_t) {
             for (uint32_t i = lo; i < hi; i++) {
                 Round &x = R[i];
                 if (x.status != HM_OK) continue;
+                if (exotic) { bin_to_json(x.bin, x.patch, x.bclock, x.cclock); continue; }
                 DocSt &d = ds->doc(x.doc);
-                if (exotic) {                                  // the binary pass already advanced the patch base
-                    // re-render from the words is not possible in JSON form without the base: rebuild
-                    // the JSON from the binary document (same diffs, same order)
-                    bin_to_json(x.bin, x.patch, x.bclock, x.cclock);
-                    continue;
-                }
                 std::string &o = x.patch;
                 o.reserve(256);
                 JsonW w{o, d};
@@ -1611,13 +1655,7 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
                 o += ",\"deps\":";
                 jclock(o, d, x.heads, x.n_actors);
                 o += ",\"canUndo\":false,\"canRedo\":false,\"diffs\":[";
-                if (ds->patches && ds->op_diffs) {
-                    Replay rp{d, STRIDES[x.cls]};
-                    rp.round(w, hlog[x.cls].data() + x.h0, had[x.cls].data() + (size_t)x.h0 * STRIDES[x.cls], x.h1 - x.h0, x.touched);
-                } else if (ds->patches) {
-                    if (x.q1 > x.q0) render_diffs(w, d, qregs[x.cls].data() + x.q0, rrows[x.cls].data() + x.q0, rsurv[x.cls].data(), x.q1 - x.q0);
-                    else render_diffs(w, d, nullptr, nullptr, nullptr, 0);
-                }
+                diffs(w, x, d);
                 o += "]}";
                 jclock(x.bclock, d, x.back, x.n_actors);
                 uint32_t rc[HM_MAX_STRIDE];
@@ -1626,9 +1664,8 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
             }
         });
     }
-    mark("diffs");
-    if (ds->patches && ds->op_diffs) {
-        // the replay's registers against the device's merged registers
+    // op diffs: the replay's registers against the device's merged registers
+    void verify() {
         for (uint32_t c = 0; c < N_CLASS; c++) {
             std::vector<uint32_t> vd, vr, vx;
             uint32_t vcap = 0;
@@ -1665,24 +1702,21 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
             ds->stat[6] += bad.load();
         }
         for (uint32_t c = 0; c < N_CLASS; c++) ds->stat[5] += hreq[c].size();
-        mark("verify");
     }
-    std::string &s = out->s;
-    s.clear();
-    if (ds->binary && !exotic) {
-        // HMP1 layout: header u32[8] {magic, n_docs, n_strings, n_words, n_nums, blob_bytes, ascii, 0},
-        // doc_word_off / doc_str_base / doc_num_base u32[n_docs + 1] each, str_off u32[n_strings + 1]
-        // (byte offsets into the blob), words u32[n_words], (8-aligned) nums f64[n_nums], blob
+    // HMP1 layout: header u32[8] {magic, n_docs, n_strings, n_words, n_nums, blob_bytes, ascii, 0},
+    // doc_word_off / doc_str_base / doc_num_base u32[n_docs + 1] each, str_off u32[n_strings + 1]
+    // (byte offsets into the blob), words u32[n_words], (8-aligned) nums f64[n_nums], blob
+    void assemble_hmp1(std::string &s) {
         std::vector<uint32_t> wo(n + 1, 0), sb(n + 1, 0), nb(n + 1, 0);
-        std::vector<uint64_t> bo(n + 1, 0);                  // each document's first blob byte
+        std::vector<uint64_t> bb(n + 1, 0);                  // each document's first blob byte
         for (uint32_t i = 0; i < n; i++) {
             const BinDoc &x = R[i].bin;
             wo[i + 1] = wo[i] + (uint32_t)x.w.size(); sb[i + 1] = sb[i] + (uint32_t)x.strs.size(); nb[i + 1] = nb[i] + (uint32_t)x.nums.size();
             uint64_t b = 0;
             for (auto &t : x.strs) b += t.second;
-            bo[i + 1] = bo[i] + b;
+            bb[i + 1] = bb[i] + b;
         }
-        const uint64_t blob = bo[n];
+        const uint64_t blob = bb[n];
         const uint32_t ns = sb[n], nw = wo[n], nn = nb[n];
         size_t head = 4 * (8 + 3 * ((size_t)n + 1) + (size_t)ns + 1 + nw);
         const size_t pad = (8 - head % 8) % 8;
@@ -1707,7 +1741,7 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
                 const BinDoc &x = R[i].bin;
                 if (!x.w.empty()) memcpy(words + wo[i], x.w.data(), 4 * x.w.size());
                 if (!x.nums.empty()) memcpy(nums + nb[i], x.nums.data(), 8 * x.nums.size());
-                uint64_t at = bo[i];
+                uint64_t at = bb[i];
                 uint32_t k = sb[i];
                 for (auto &t : x.strs) {
                     memcpy(bl + at, t.first, t.second);
@@ -1720,8 +1754,9 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
             if (!asc) ascii = false;
         });
         h[6] = ascii ? 1 : 0;
-    } else {
-        // {"p": [patch | null per document], "b": [max over the whole log | null], "c": [max over this call's changes | null]}
+    }
+    // {"p": [patch | null per document], "b": [max over the whole log | null], "c": [max over this call's changes | null]}
+    void assemble_json(std::string &s) {
         size_t tot = 16;
         for (auto &x : R) tot += x.patch.size() + x.bclock.size() + x.cclock.size() + 18;
         s.reserve(tot);
@@ -1733,22 +1768,119 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
         for (uint32_t i = 0; i < n; i++) { if (i) s += ','; if (R[i].status == HM_OK) s += R[i].cclock; else s += "null"; }
         s += "]}";
     }
-    out->res.resize(n);
-    for (uint32_t i = 0; i < n; i++) {
-        Round &x = R[i];
-        hm_doc_result &r = out->res[i];
-        if (x.cls == NO_CLASS && x.status != HM_OK) {                    // the call's blocks did not decode
-            r = hm_doc_result{};
-            r.status = x.status; r.err_change = x.err_block; r.err_op = HM_NONE;
-            DocSt &d = ds->doc(x.doc);
-            r.hist_len = d.hist_len; r.n_queued = d.n_queued;
-        } else r = x.res;
+    // the call's result: the text (HMP1, or JSON), every document's result row, the call counters
+    void assemble(hm_text *out) {
+        out->s.clear();
+        if (ds->binary && !exotic) assemble_hmp1(out->s);
+        else assemble_json(out->s);
+        out->res.resize(n);
+        for (uint32_t i = 0; i < n; i++) {
+            Round &x = R[i];
+            hm_doc_result &r = out->res[i];
+            if (x.cls == NO_CLASS && x.status != HM_OK) {                    // the call's blocks did not decode
+                r = hm_doc_result{};
+                r.status = x.status; r.err_change = x.err_block; r.err_op = HM_NONE;
+                DocSt &d = ds->doc(x.doc);
+                r.hist_len = d.hist_len; r.n_queued = d.n_queued;
+            } else r = x.res;
+        }
+        ds->stat[0]++;
+        ds->stat[1] += n;
     }
-    ds->stat[0]++;
-    ds->stat[1] += n;
-    mark("render");
+};
+
+// One call = one applyChanges round for every document of the call.  A phase that returns a
+// status fails the call: fail() undoes it on every store and rolls every document back.
+int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t *doc_block, const uint32_t *docs, uint32_t n,
+          hm_text *out) {
+    Call c{ds, data, bo, doc_block, docs, n};
+    int rc = c.validate();
+    if (rc) return rc;
+    c.decode();
+    c.mark("decode");
+    c.place();
+    for (uint32_t k = 0; k < N_CLASS; k++)
+        if (!c.by_cls[k].empty() && (rc = c.merge_class(k))) return c.fail(rc);
+    c.mark("merge");
+    c.settle();
+    // (the injected read failure: after the requests are built, before any read)
+    if (c.inj_read) return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "injected failure (HM_DOCSET_INJECT_FAIL)"));
+    if ((rc = c.read_regs())) return c.fail(rc);
+    if ((rc = c.read_history())) return c.fail(rc);
+    c.mark("read history");
+    c.commit();
+    c.mark("commit");
+    c.release();
+    c.mark("read regs");
+    c.render();
+    c.mark("diffs");
+    if (ds->patches && ds->op_diffs) {
+        c.verify();
+        c.mark("verify");
+    }
+    c.assemble(out);
+    c.mark("render");
     return HM_OK;
 }
+
+// ---------------- what the host queries over many documents share ----------------
+// the request's documents exist (and, with entry_off, its entry ranges do not decrease)
+int check_request(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off = nullptr) {
+    const uint32_t nd = ds->n_docs.load();
+    for (uint32_t i = 0; i < n; i++) {
+        if (docs[i] >= nd) return hm_engine_fail(ds->e, HM_ERR_INVALID, "bad docset document");
+        if (entry_off && entry_off[i + 1] < entry_off[i]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "entry_off must not decrease");
+    }
+    return HM_OK;
+}
+
+// the request's documents that live in class c: their places in docs[0..n) and their store handles
+void class_docs(hm_docset *ds, uint32_t c, uint32_t n, const uint32_t *docs, std::vector<uint32_t> &idx, std::vector<uint32_t> &hs) {
+    for (uint32_t i = 0; i < n; i++) {
+        const DocSt &d = ds->doc(docs[i]);
+        if (d.cls == c) { idx.push_back(i); hs.push_back(d.handle); }
+    }
+}
+
+// a clock entry's seq (a JS number) as the stores' u32
+uint32_t seq_u32(double v) { return !(v > 0) ? 0u : v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v; }
+
+// the per-document texts as one JSON array
+hm_text *json_array(const std::vector<std::string> &js) {
+    std::unique_ptr<hm_text> t(new hm_text());
+    t->s = "[";
+    for (size_t i = 0; i < js.size(); i++) { if (i) t->s += ','; t->s += js[i]; }
+    t->s += ']';
+    return t.release();
+}
+
+// hm_docset_materialize: one class's result tables, sized by the store once its count pass has
+// run (hm_past_alloc)
+struct PastTables {
+    uint32_t k, S;
+    std::vector<hm_doc_row> rows_d;
+    std::vector<hm_op_row> ops;
+    std::vector<uint32_t> op_log, clock, heads;
+    std::vector<hm_doc_result> res;
+    std::vector<hm_reg_result> regs;
+    std::vector<hm_surv_result> surv;
+    hm_past_out po;
+    static const hm_past_out *alloc(void *ctx, const uint64_t *tot) {
+        PastTables &t = *(PastTables *)ctx;
+        if (tot[2] > 0xFFFFFFFFull || tot[3] > 0xFFFFFFFFull) return nullptr;
+        try {
+            t.rows_d.resize(t.k); t.res.resize(t.k);
+            t.clock.resize((size_t)t.k * t.S); t.heads.resize((size_t)t.k * t.S);
+            t.ops.resize(tot[2] + 1); t.op_log.resize(tot[2] + 1); t.surv.resize(tot[2] + 1); t.regs.resize(tot[3] + 1);
+        } catch (...) { return nullptr; }
+        t.po = hm_past_out{};
+        t.po.cap_ops = (uint32_t)tot[2]; t.po.cap_regs = (uint32_t)tot[3];
+        t.po.docs = t.rows_d.data(); t.po.ops = t.ops.data(); t.po.op_log = t.op_log.data();
+        t.po.res.docs = t.res.data(); t.po.res.clock = t.clock.data(); t.po.res.heads = t.heads.data();
+        t.po.res.regs = t.regs.data(); t.po.res.surv = t.surv.data();
+        return &t.po;
+    }
+};
 
 }  // namespace
 
@@ -1855,18 +1987,17 @@ int hm_docset_clock_update(hm_docset *ds, uint32_t n, const uint32_t *docs, uint
     Busy b(ds);
     if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
     try {
-        const uint32_t nd = ds->n_docs.load();
-        for (uint32_t i = 0; i < n; i++) if (docs[i] >= nd) return hm_engine_fail(ds->e, HM_ERR_INVALID, "bad docset document");
+        int rc = check_request(ds, n, docs);
+        if (rc) return rc;
         std::vector<std::string> js(n, "{}");
         for (uint32_t c = 0; c < N_CLASS; c++) {
             std::vector<uint32_t> idx, hs;
-            for (uint32_t i = 0; i < n; i++) if (ds->doc(docs[i]).cls == c) { idx.push_back(i); hs.push_back(ds->doc(docs[i]).handle); }
+            class_docs(ds, c, n, docs, idx, hs);
             if (idx.empty()) continue;
             const uint32_t S = STRIDES[c], k = (uint32_t)idx.size();
             std::vector<uint8_t> w(k), df(k);
             std::vector<uint32_t> stv((size_t)k * S);
-            const int rc = hm_store_clock_update(ds->stores[c], k, hs.data(), w.data(), df.data(), stv.data());
-            if (rc) return rc;
+            if ((rc = hm_store_clock_update(ds->stores[c], k, hs.data(), w.data(), df.data(), stv.data()))) return rc;
             for (uint32_t j = 0; j < k; j++) {
                 const uint32_t i = idx[j];
                 if (out_written) out_written[i] = w[j];
@@ -1880,13 +2011,7 @@ int hm_docset_clock_update(hm_docset *ds, uint32_t n, const uint32_t *docs, uint
             if (out_written) out_written[i] = 0;
             if (out_differs) out_differs[i] = 0;
         }
-        if (out_stored) {
-            std::unique_ptr<hm_text> t(new hm_text());
-            t->s = "[";
-            for (uint32_t i = 0; i < n; i++) { if (i) t->s += ','; t->s += js[i]; }
-            t->s += ']';
-            *out_stored = t.release();
-        }
+        if (out_stored) *out_stored = json_array(js);
         return HM_OK;
     } catch (...) {
         return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_clock_update");
@@ -1933,17 +2058,16 @@ int hm_docset_waiting(hm_docset *ds, uint32_t n, const uint32_t *docs, hm_text *
     Busy b(ds);
     if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
     try {
-        const uint32_t nd = ds->n_docs.load();
-        for (uint32_t i = 0; i < n; i++) if (docs[i] >= nd) return hm_engine_fail(ds->e, HM_ERR_INVALID, "bad docset document");
+        int rc = check_request(ds, n, docs);
+        if (rc) return rc;
         std::vector<std::string> js(n, "{\"queued\":[],\"missing\":{}}");      // (a document not placed yet)
         for (uint32_t c = 0; c < N_CLASS; c++) {
             std::vector<uint32_t> idx, hs;
-            for (uint32_t i = 0; i < n; i++) if (ds->doc(docs[i]).cls == c) { idx.push_back(i); hs.push_back(ds->doc(docs[i]).handle); }
+            class_docs(ds, c, n, docs, idx, hs);
             if (idx.empty()) continue;
             const uint32_t S = STRIDES[c], k = (uint32_t)idx.size();
             std::vector<uint32_t> miss((size_t)k * S), nq(k), off(k + 1, 0);
-            int rc = hm_store_waiting(ds->stores[c], k, hs.data(), miss.data(), nullptr, nq.data());
-            if (rc) return rc;
+            if ((rc = hm_store_waiting(ds->stores[c], k, hs.data(), miss.data(), nullptr, nq.data()))) return rc;
             for (uint32_t j = 0; j < k; j++) off[j + 1] = off[j] + nq[j];
             std::vector<uint32_t> q(off[k] + 1);
             if ((rc = hm_store_read_queue(ds->stores[c], k, hs.data(), off.data(), q.data()))) return rc;
@@ -1957,11 +2081,7 @@ int hm_docset_waiting(hm_docset *ds, uint32_t n, const uint32_t *docs, hm_text *
                 o += '}';
             }
         }
-        std::unique_ptr<hm_text> t(new hm_text());
-        t->s = "[";
-        for (uint32_t i = 0; i < n; i++) { if (i) t->s += ','; t->s += js[i]; }
-        t->s += ']';
-        *out = t.release();
+        *out = json_array(js);
         return HM_OK;
     } catch (...) {
         return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_waiting");
@@ -1976,11 +2096,8 @@ int hm_docset_missing_changes(hm_docset *ds, uint32_t n, const uint32_t *docs, c
     Busy b(ds);
     if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
     try {
-        const uint32_t nd = ds->n_docs.load();
-        for (uint32_t i = 0; i < n; i++) {
-            if (docs[i] >= nd) return hm_engine_fail(ds->e, HM_ERR_INVALID, "bad docset document");
-            if (entry_off[i + 1] < entry_off[i]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "entry_off must not decrease");
-        }
+        int rc = check_request(ds, n, docs, entry_off);
+        if (rc) return rc;
         if (n && entry_off[n] - entry_off[0] && (!actor_ids || !actor_off || !seqs)) return HM_ERR_INVALID;
         std::vector<std::string> js(n, "[]");                                    // (a document not placed yet)
         for (uint32_t c = 0; c < N_CLASS; c++) {
@@ -1994,9 +2111,8 @@ int hm_docset_missing_changes(hm_docset *ds, uint32_t n, const uint32_t *docs, c
                     if (actor_off[k + 1] < actor_off[k]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease");
                     const uint32_t a = d.actors.find(actor_ids + actor_off[k], actor_off[k + 1] - actor_off[k], 0);
                     if (a == HM_NONE || a >= d.rank_of.size()) continue;       // (an actor the document has never seen)
-                    const double v = seqs[k];
                     eact.push_back(d.rank_of[a]);
-                    eseq.push_back(!(v > 0) ? 0u : v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v);
+                    eseq.push_back(seq_u32(seqs[k]));
                 }
                 off.push_back((uint32_t)eact.size());
             }
@@ -2004,7 +2120,7 @@ int hm_docset_missing_changes(hm_docset *ds, uint32_t n, const uint32_t *docs, c
             const uint32_t k = (uint32_t)idx.size();
             std::vector<uint32_t> rng(2 * (size_t)k), log;
             uint32_t total = 0;
-            int rc = hm_store_missing_changes(ds->stores[c], k, hs.data(), off.data(), eact.data(), eseq.data(), flags, nullptr,
+            rc = hm_store_missing_changes(ds->stores[c], k, hs.data(), off.data(), eact.data(), eseq.data(), flags, nullptr,
                                               rng.data(), nullptr, 0, &total);
             if (rc == HM_ERR_NOMEM && total) {                   // (the counts are known: now with room)
                 log.resize(total);
@@ -2019,11 +2135,7 @@ int hm_docset_missing_changes(hm_docset *ds, uint32_t n, const uint32_t *docs, c
                 o += ']';
             }
         }
-        std::unique_ptr<hm_text> t(new hm_text());
-        t->s = "[";
-        for (uint32_t i = 0; i < n; i++) { if (i) t->s += ','; t->s += js[i]; }
-        t->s += ']';
-        *out = t.release();
+        *out = json_array(js);
         return HM_OK;
     } catch (...) {
         return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_missing_changes");
@@ -2039,11 +2151,8 @@ int hm_docset_materialize(hm_docset *ds, uint32_t n, const uint32_t *docs, const
     Busy b(ds);
     if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
     try {
-        const uint32_t nd = ds->n_docs.load();
-        for (uint32_t i = 0; i < n; i++) {
-            if (docs[i] >= nd) return hm_engine_fail(ds->e, HM_ERR_INVALID, "bad docset document");
-            if (entry_off && entry_off[i + 1] < entry_off[i]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "entry_off must not decrease");
-        }
+        int rc = check_request(ds, n, docs, entry_off);
+        if (rc) return rc;
         if (entry_off && n && entry_off[n] - entry_off[0] && (!actor_ids || !actor_off || !seqs)) return HM_ERR_INVALID;
         std::vector<std::string> js(n);
         for (uint32_t i = 0; i < n; i++) {                       // (a document not placed yet: Backend.init())
@@ -2068,81 +2177,43 @@ int hm_docset_materialize(hm_docset *ds, uint32_t n, const uint32_t *docs, const
                     if (actor_off[k + 1] < actor_off[k]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease");
                     const uint32_t a = d.actors.find(actor_ids + actor_off[k], actor_off[k + 1] - actor_off[k], 0);
                     if (a == HM_NONE || a >= d.rank_of.size() || d.rank_of[a] >= S) continue;   // (an actor the document has never seen)
-                    const double v = seqs[k];
-                    row[d.rank_of[a]] = !(v > 0) ? 0u : v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v;
+                    row[d.rank_of[a]] = seq_u32(seqs[k]);
                 }
             }
             if (idx.empty()) continue;
             const uint32_t k = (uint32_t)idx.size();
-            hm_store *st = ds->stores[c];
             const uint32_t *hl = hist_len ? sel.data() : nullptr, *rows = hist_len ? nullptr : sel.data();
-            // the tables are sized once the count pass has run (one count pass per class)
-            struct Tables {
-                uint32_t k, S;
-                std::vector<hm_doc_row> rows_d;
-                std::vector<hm_op_row> ops;
-                std::vector<uint32_t> op_log, clock, heads;
-                std::vector<hm_doc_result> res;
-                std::vector<hm_reg_result> regs;
-                std::vector<hm_surv_result> surv;
-                hm_past_out po;
-            } T;
+            PastTables T;                                        // (one count pass per class)
             T.k = k; T.S = S;
-            const hm_past_alloc alloc = [](void *ctx, const uint64_t *tot) -> const hm_past_out * {
-                Tables &t = *(Tables *)ctx;
-                if (tot[2] > 0xFFFFFFFFull || tot[3] > 0xFFFFFFFFull) return nullptr;
-                try {
-                    t.rows_d.resize(t.k); t.res.resize(t.k);
-                    t.clock.resize((size_t)t.k * t.S); t.heads.resize((size_t)t.k * t.S);
-                    t.ops.resize(tot[2] + 1); t.op_log.resize(tot[2] + 1); t.surv.resize(tot[2] + 1); t.regs.resize(tot[3] + 1);
-                } catch (...) { return nullptr; }
-                t.po = hm_past_out{};
-                t.po.cap_ops = (uint32_t)tot[2]; t.po.cap_regs = (uint32_t)tot[3];
-                t.po.docs = t.rows_d.data(); t.po.ops = t.ops.data(); t.po.op_log = t.op_log.data();
-                t.po.res.docs = t.res.data(); t.po.res.clock = t.clock.data(); t.po.res.heads = t.heads.data();
-                t.po.res.regs = t.regs.data(); t.po.res.surv = t.surv.data();
-                return &t.po;
-            };
-            int rc = hm_store_materialize_sized(st, k, hs.data(), hl, rows, alloc, &T, nullptr);
-            if (rc) return rc;
-            std::vector<hm_doc_row> &rows_d = T.rows_d;
-            std::vector<hm_op_row> &ops = T.ops;
-            std::vector<uint32_t> &op_log = T.op_log, &clock = T.clock, &heads = T.heads;
-            std::vector<hm_doc_result> &res = T.res;
-            std::vector<hm_reg_result> &regs = T.regs;
-            std::vector<hm_surv_result> &surv = T.surv;
+            if ((rc = hm_store_materialize_sized(ds->stores[c], k, hs.data(), hl, rows, PastTables::alloc, &T, nullptr))) return rc;
             std::vector<uint8_t> created;
             for (uint32_t j = 0; j < k; j++) {
                 DocSt &d = ds->doc(docs[idx[j]]);
                 if (!d.ready) d.setup();
-                const hm_doc_row &r = rows_d[j];
+                const hm_doc_row &r = T.rows_d[j];
                 std::string &o = js[idx[j]];
                 o = "{\"doc\":" + std::to_string(docs[idx[j]]) + ",\"clock\":";
-                jclock(o, d, clock.data() + (size_t)j * S, std::min<size_t>(d.actors.size(), S));
+                jclock(o, d, T.clock.data() + (size_t)j * S, std::min<size_t>(d.actors.size(), S));
                 o += ",\"deps\":";
-                jclock(o, d, heads.data() + (size_t)j * S, std::min<size_t>(d.actors.size(), S));
-                o += ",\"history\":" + std::to_string(res[j].hist_len) + ",\"view\":";
-                if (res[j].status != HM_OK) { o += "null}"; continue; }
+                jclock(o, d, T.heads.data() + (size_t)j * S, std::min<size_t>(d.actors.size(), S));
+                o += ",\"history\":" + std::to_string(T.res[j].hist_len) + ",\"view\":";
+                if (T.res[j].status != HM_OK) { o += "null}"; continue; }
                 // the objects the gathered ops create, and the survivors' ops as the document's own log indices
                 created.assign(std::max<size_t>(d.obj_type.size(), 1), 0);
                 created[0] = 1;
                 for (uint32_t x = r.op_off; x < r.op_off + r.n_ops; x++)
-                    if (ops[x].action <= HM_MAKE_TEXT && ops[x].obj < created.size()) created[ops[x].obj] = 1;
-                const uint32_t ns = std::min(res[j].n_surv, r.n_ops);
+                    if (T.ops[x].action <= HM_MAKE_TEXT && T.ops[x].obj < created.size()) created[T.ops[x].obj] = 1;
+                const uint32_t ns = std::min(T.res[j].n_surv, r.n_ops);
                 for (uint32_t x = 0; x < ns; x++) {
-                    hm_surv_result &sv = surv[r.op_off + x];
-                    sv.op = sv.op < r.n_ops ? op_log[r.op_off + sv.op] : HM_NONE;
+                    hm_surv_result &sv = T.surv[r.op_off + x];
+                    sv.op = sv.op < r.n_ops ? T.op_log[r.op_off + sv.op] : HM_NONE;
                 }
-                render_view(o, d, regs.data() + r.reg_off, surv.data() + r.op_off, std::min<uint32_t>(r.n_regs, (uint32_t)d.regs.size()),
-                            created.data());
+                render_view(o, d, T.regs.data() + r.reg_off, T.surv.data() + r.op_off,
+                            std::min<uint32_t>(r.n_regs, (uint32_t)d.regs.size()), created.data());
                 o += '}';
             }
         }
-        std::unique_ptr<hm_text> t(new hm_text());
-        t->s = "[";
-        for (uint32_t i = 0; i < n; i++) { if (i) t->s += ','; t->s += js[i]; }
-        t->s += ']';
-        *out = t.release();
+        *out = json_array(js);
         return HM_OK;
     } catch (...) {
         return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_materialize");

@@ -17,6 +17,7 @@ from .decode import pack_offsets
 from .engine import Engine, lib
 
 NO_PATCHES = 1          # HM_DOCSET_NO_PATCHES
+BINARY = 2              # HM_DOCSET_BINARY
 NET_DIFFS = 4           # HM_DOCSET_NET_DIFFS
 
 
@@ -43,10 +44,14 @@ def _text(L, t) -> Tuple[str, np.ndarray]:
 
 
 class DocSet:
-    def __init__(self, engine: Engine, threads: int = 0, patches: bool = True, net_diffs: bool = False):
+    def __init__(self, engine: Engine, threads: int = 0, patches: bool = True, net_diffs: bool = False,
+                 binary: bool = False):
+        """binary: results in the HMP1 form the Node host reads (HM_DOCSET_BINARY).  `apply` reads
+        JSON only: of a binary docset it reads the calls that fall back to JSON (a string with a
+        lone surrogate among the call's patches)."""
         self._L, self.engine = lib(), engine
         h = ctypes.c_void_p()
-        cfg = _Cfg(threads, (0 if patches else NO_PATCHES) | (NET_DIFFS if net_diffs else 0))
+        cfg = _Cfg(threads, (0 if patches else NO_PATCHES) | (NET_DIFFS if net_diffs else 0) | (BINARY if binary else 0))
         engine._check(self._L.hm_docset_create(engine._h, ctypes.byref(cfg), ctypes.byref(h)), "hm_docset_create")
         self._h = h
 

@@ -303,3 +303,54 @@ def test_docset_rounds_report_their_route():
     for i, d in enumerate(ids[::7]):
         s = _oracle(logs[ids.index(d)])
         assert render_objects(view_objects(ds.view(d))) == json.loads(json.dumps(s["state"]))
+
+
+def test_docset_binary_falls_back_to_json_on_a_lone_surrogate():
+    """A binary docset (HM_DOCSET_BINARY) whose call renders a string with a lone surrogate
+    returns the JSON form instead of HMP1 (BinDoc::exotic, bin_to_json: the blob cannot carry the
+    surrogate through Buffer.toString).  Two docsets on one engine, one JSON and one binary, fed
+    the same two rounds — a map with such strings, a list with inserts and a removal, two actors
+    writing one key — return equal patches, clocks and result rows."""
+    from hypermerge_amd.columnar import ROOT_ID as R
+    from hypermerge_amd.docset import DocSet
+    from hypermerge_amd.engine import Engine
+    A, B, L = "actorA", "actorB", "11111111-2222-3333-4444-555555555555"
+
+    def ch(actor, seq, deps, *ops):
+        return {"actor": actor, "seq": seq, "deps": deps, "ops": list(ops)}
+
+    def st(obj, key, value):
+        return {"action": "set", "obj": obj, "key": key, "value": value}
+
+    def ins(key, elem):
+        return {"action": "ins", "obj": L, "key": key, "elem": elem}
+    rounds = [
+        [[ch(A, 1, {}, st(R, "s", "a\ud800b"), st(R, "n", 1.5))],
+         [ch(A, 1, {}, {"action": "makeList", "obj": L}, {"action": "link", "obj": R, "key": "list", "value": L},
+             ins("_head", 1), st(L, f"{A}:1", "x\udc00"), ins(f"{A}:1", 2), st(L, f"{A}:2", 7))],
+         [ch(A, 1, {}, st(R, "k", "left\ud800")), ch(B, 1, {}, st(R, "k", 2))]],
+        [[ch(A, 2, {}, st(R, "t", "tail\ud800"), {"action": "del", "obj": R, "key": "n"})],
+         [ch(B, 1, {A: 1}, ins(f"{A}:1", 3), st(L, f"{B}:3", "mid"), {"action": "del", "obj": L, "key": f"{A}:2"})],
+         [ch(A, 2, {B: 1}, st(R, "k", 3)), ch(B, 2, {}, st(R, "k", "right\udc00"))]],
+    ]
+    for rnd in rounds:                                        # (every round's blocks carry the JSON escape)
+        assert any(b"\\ud800" in blk for c in rnd for blk in _blocks(c))
+    eng = Engine(0)
+    js_ds, bin_ds = DocSet(eng), DocSet(eng, binary=True)
+    ids = js_ds.open(3)
+    assert bin_ds.open(3) == ids
+    docs = [ids, ids + 1, ids + 2]
+    seen = []
+    for rnd in rounds:
+        blocks = [_blocks(c) for c in rnd]
+        rj, tj = js_ds.apply(docs, blocks)
+        rb, tb = bin_ds.apply(docs, blocks)                   # (json.loads inside: the text is JSON, not HMP1)
+        assert (rj["status"] == 0).all()
+        assert tb["p"] == tj["p"] and tb["b"] == tj["b"] and tb["c"] == tj["c"]
+        assert rb.dtype == rj.dtype and all((rb[f] == rj[f]).all() for f in rj.dtype.names)
+        seen += [d for p in tj["p"] for d in p["diffs"]]
+    assert any(d.get("value") == "a\ud800b" for d in seen)
+    assert any(d["action"] == "insert" and d["type"] == "list" for d in seen)
+    assert any(d["action"] == "remove" and d["type"] == "list" for d in seen)
+    assert any(d.get("conflicts") and d["key"] == "k" for d in seen)
+    assert bin_ds.stats()["replay_mismatch"] == 0 and js_ds.stats()["replay_mismatch"] == 0

@@ -985,6 +985,9 @@ void render_diffs(W &w, DocSt &d, const uint32_t *req, const hm_reg_result *rows
 // resident depends on the new op), inc's counter sums and the sortBy(actor).reverse(), and
 // RGA placement ((elem, actor) descending siblings, pre-order), to know each op's diff.  The
 // registers it ends on are compared with the device's merged registers afterwards.
+// (For map / table registers and counters the same rows come from the device without a replay:
+// hm_store_op_diffs, which hm_docset_materialize_patch renders; the rounds of hm_docset_apply and
+// every list / text element diff still go through this replay.)
 struct Replay {
     DocSt &d;
     uint32_t S;
@@ -1880,6 +1883,18 @@ struct PastTables {
         t.po.res.regs = t.regs.data(); t.po.res.surv = t.surv.data();
         return &t.po;
     }
+    // hm_docset_materialize_patch: the prefix's clock, deps and history length alone
+    static const hm_past_out *alloc_heads(void *ctx, const uint64_t *) {
+        PastTables &t = *(PastTables *)ctx;
+        try {
+            t.rows_d.resize(t.k); t.res.resize(t.k);
+            t.clock.resize((size_t)t.k * t.S); t.heads.resize((size_t)t.k * t.S);
+        } catch (...) { return nullptr; }
+        t.po = hm_past_out{};
+        t.po.docs = t.rows_d.data();
+        t.po.res.docs = t.res.data(); t.po.res.clock = t.clock.data(); t.po.res.heads = t.heads.data();
+        return &t.po;
+    }
 };
 
 }  // namespace
@@ -2217,6 +2232,78 @@ int hm_docset_materialize(hm_docset *ds, uint32_t n, const uint32_t *docs, const
         return HM_OK;
     } catch (...) {
         return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_materialize");
+    }
+}
+
+int hm_docset_materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, hm_text **out) {
+    if (!ds || !out || (n && (!docs || !hist_len))) return HM_ERR_INVALID;
+    *out = nullptr;
+    Busy b(ds);
+    if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
+    try {
+        int rc = check_request(ds, n, docs);
+        if (rc) return rc;
+        if (n && !(ds->patches && ds->op_diffs))
+            return hm_engine_fail(ds->e, HM_ERR_UNSUPPORTED, "hm_docset_materialize_patch renders per-op diffs: not with HM_DOCSET_NO_PATCHES / HM_DOCSET_NET_DIFFS");
+        static const char TAIL[] = ",\"canUndo\":false,\"canRedo\":false,\"diffs\":[";
+        std::vector<std::string> js(n);
+        for (uint32_t i = 0; i < n; i++)                         // (a document not placed yet: Backend.init())
+            if (ds->doc(docs[i]).cls == NO_CLASS)
+                js[i] = "{\"doc\":" + std::to_string(docs[i]) + ",\"history\":0,\"patch\":{\"clock\":{},\"deps\":{}" + TAIL + "]}}";
+        for (uint32_t c = 0; c < N_CLASS; c++) {
+            const uint32_t S = STRIDES[c];
+            std::vector<uint32_t> idx, hs, hl;
+            for (uint32_t i = 0; i < n; i++) {
+                const DocSt &d = ds->doc(docs[i]);
+                if (d.cls != c) continue;
+                idx.push_back(i); hs.push_back(d.handle); hl.push_back(hist_len[i]);
+            }
+            if (idx.empty()) continue;
+            const uint32_t k = (uint32_t)idx.size();
+            PastTables T;                                        // the prefix's clock and deps: its merge from Backend.init()
+            T.k = k; T.S = S;
+            if ((rc = hm_store_materialize_sized(ds->stores[c], k, hs.data(), hl.data(), nullptr, PastTables::alloc_heads, &T, nullptr))) return rc;
+            // the diffs: what each op of the prefix did, from the resident tables
+            const std::vector<uint32_t> from(k, 0u);
+            uint64_t tot[2] = {0, 0};
+            if ((rc = hm_store_op_diff_sizes(ds->stores[c], k, hs.data(), from.data(), hl.data(), nullptr, nullptr, tot))) return rc;
+            if (tot[0] > 0xFFFFFFFFull || tot[1] > 0xFFFFFFFFull) return hm_engine_fail(ds->e, HM_ERR_NOMEM, "a call's rows stay below 2^32");
+            std::vector<hm_op_diff> rows(tot[0] + 1);
+            std::vector<hm_surv_result> surv(tot[1] + 1);
+            std::vector<uint32_t> range(2 * (size_t)k), flags(k);
+            hm_op_diff_out po = {(uint32_t)tot[0], (uint32_t)tot[1], rows.data(), surv.data(), range.data(), flags.data()};
+            if ((rc = hm_store_op_diffs(ds->stores[c], k, hs.data(), from.data(), hl.data(), &po, nullptr))) return rc;
+            for (uint32_t j = 0; j < k; j++) {
+                DocSt &d = ds->doc(docs[idx[j]]);
+                if (!d.ready) d.setup();
+                std::string &o = js[idx[j]];
+                o = "{\"doc\":" + std::to_string(docs[idx[j]]) + ",\"history\":" + std::to_string(T.res[j].hist_len) + ",\"patch\":";
+                if (flags[j] & HM_OD_LISTS) { o += "null,\"host\":true}"; continue; }   // (list / text elements: the caller replays)
+                if (T.res[j].status != HM_OK) { o += "null}"; continue; }
+                o += "{\"clock\":";
+                jclock(o, d, T.clock.data() + (size_t)j * S, std::min<size_t>(d.actors.size(), S));
+                o += ",\"deps\":";
+                jclock(o, d, T.heads.data() + (size_t)j * S, std::min<size_t>(d.actors.size(), S));
+                o += TAIL;
+                JsonW w{o, d};
+                for (uint32_t x = range[2 * j]; x < range[2 * j] + range[2 * j + 1]; x++) {
+                    const hm_op_diff &r = rows[x];
+                    if (r.op >= d.oplog.size()) return hm_engine_fail(ds->e, HM_ERR_INVALID, "an op diff outside the document's log");
+                    const hm_op_row &op = d.oplog[r.op];
+                    if (op.obj >= d.obj_type.size()) return hm_engine_fail(ds->e, HM_ERR_INVALID, "an op diff on an unknown object");
+                    if (r.kind == HM_OD_CREATE) { w.create(op.obj, op.action); continue; }
+                    if (op.reg >= d.regs.size()) return hm_engine_fail(ds->e, HM_ERR_INVALID, "an op diff on an unknown register");
+                    const uint8_t t = d.obj_type[op.obj] != NO_TYPE ? d.obj_type[op.obj] : (uint8_t)HM_MAKE_MAP;
+                    if (r.kind == HM_OD_SET) w.map_set(t, op.obj, op.reg, surv.data() + r.surv_off, r.n_surv);
+                    else w.map_remove(t, op.obj, op.reg);
+                }
+                o += "]}}";
+            }
+        }
+        *out = json_array(js);
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_materialize_patch");
     }
 }
 

@@ -18,6 +18,7 @@
 #include "waiting_kernels.h"
 #include "changes_kernels.h"
 #include "past_kernels.h"
+#include "op_diff_kernels.h"
 
 struct hm_engine {
     int device = 0;
@@ -552,6 +553,132 @@ int hm_materialize_device(hm_engine *e, const hm_batch *b, const hm_results *r, 
         return hr == hipSuccess ? HM_OK : hip_fail(e, hr, "past kernels launch");
     } catch (...) {
         return fail(e, HM_ERR_DEVICE, "exception in hm_materialize_device");
+    }
+}
+
+// the words of a wave's slice for any document of b: its launch hints, or the batch totals without them
+static unsigned long long od_batch_slice(const hm_batch *b) {
+    const bool hints = b->max_ops || b->max_regs || b->max_objs;
+    const unsigned long long w = hints ? hm_od_slice_words(b->max_ops, b->max_regs, b->max_objs ? b->max_objs : 1u)
+                                       : hm_od_slice_words(b->n_ops, b->n_regs, (unsigned long long)b->n_ops + b->n_docs);
+    return w ? w : 1ull;
+}
+// [counts 4n][offsets 4n][zero and flags 2n] u32, the scan's per-chunk words, then the waves' slices
+static size_t od_fixed_bytes(uint32_t n) {
+    return ((((size_t)n * 40) + 255) & ~(size_t)255) + ((((size_t)hm_past_scan_chunks(n) * HM_PAST_PART * 8) + 255) & ~(size_t)255);
+}
+
+size_t hm_op_diffs_work_bytes(const hm_batch *b, uint32_t n) {
+    if (!b || !n) return 0;
+    const unsigned long long sw = od_batch_slice(b);
+    return od_fixed_bytes(n) + (size_t)hm_od_waves(n, sw) * (size_t)sw * 4;
+}
+
+int hm_op_diffs_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                       const uint32_t *from, const uint32_t *to, const hm_op_diff_out *out,
+                       hm_op_diff_summary *out_summary, void *work, void *stream) {
+    try {
+        if (!e || !r || !out || !out_summary) return HM_ERR_INVALID;
+        int st = check_batch(e, b);
+        if (st) return st;
+        if (n && (!work || !from || !to || !out->range || !out->flags))
+            return fail(e, HM_ERR_INVALID, "hm_op_diffs: work, a range array or a per-request output missing");
+        if (((uintptr_t)work | (uintptr_t)b->ops) & 15u)       // (the counts and the op rows are read as 16-byte words)
+            return fail(e, HM_ERR_INVALID, "hm_op_diffs: work and b->ops must be 16-byte aligned");
+        if ((out->cap_rows && !out->rows) || (out->cap_surv && !out->surv))
+            return fail(e, HM_ERR_INVALID, "hm_op_diffs: an output table with a capacity is missing");
+        if (!r->docs || (b->n_changes && (!r->hist || !r->all_deps)))
+            return fail(e, HM_ERR_INVALID, "hm_op_diffs needs the results' docs, hist and all_deps tables");
+        HIPCHK(e, hipSetDevice(e->device));
+        hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+        OpDiffArgs A = {};
+        A.n = n; A.src = batch_source(b, r); A.src.handles = doc_index;
+        A.from = from; A.to = to;
+        A.cnt = (uint32_t *)work; A.off = A.cnt + 4 * (size_t)n; A.aux = A.off + 4 * (size_t)n;
+        A.part = (unsigned long long *)((char *)work + ((((size_t)n * 40) + 255) & ~(size_t)255));
+        A.sum = out_summary;
+        A.slice_words = od_batch_slice(b); A.waves = hm_od_waves(n, A.slice_words);
+        A.work = (uint32_t *)((char *)work + od_fixed_bytes(n));
+        A.cap_rows = out->cap_rows; A.cap_surv = out->cap_surv;
+        A.out_rows = out->rows; A.out_surv = out->surv; A.out_range = out->range; A.out_flags = out->flags;
+        hipError_t hr = hm_launch_op_diff_count(A, s);
+        if (hr == hipSuccess) hr = hm_launch_op_diff_fill(A, s);
+        return hr == hipSuccess ? HM_OK : hip_fail(e, hr, "op-diff kernels launch");
+    } catch (...) {
+        return fail(e, HM_ERR_DEVICE, "exception in hm_op_diffs_device");
+    }
+}
+
+int hm_op_diffs_host(hm_engine *e, const hm_batch *hb, const hm_results *hr, uint32_t n, const uint32_t *doc_index,
+                     const uint32_t *from, const uint32_t *to, const hm_op_diff_out *out, uint64_t *out_totals) {
+    try {
+        if (!e || !hr || !out) return HM_ERR_INVALID;
+        int st = check_batch(e, hb);
+        if (st) return st;
+        if (out_totals) out_totals[0] = out_totals[1] = 0;
+        if (!n) return HM_OK;
+        if (!from || !to || !out->range || !out->flags || (out->cap_rows && !out->rows) || (out->cap_surv && !out->surv))
+            return fail(e, HM_ERR_INVALID, "hm_op_diffs: a range array or an output missing");
+        if (!hr->docs || (hb->n_changes && (!hr->hist || !hr->all_deps)))
+            return fail(e, HM_ERR_INVALID, "hm_op_diffs needs the results' docs, hist and all_deps tables");
+        if (doc_index)
+            for (uint32_t i = 0; i < n; i++)
+                if (doc_index[i] >= hb->n_docs) return fail(e, HM_ERR_INVALID, "hm_op_diffs: a document outside the batch");
+        if (!doc_index && n > hb->n_docs) return fail(e, HM_ERR_INVALID, "hm_op_diffs: a document outside the batch");
+        HIPCHK(e, hipSetDevice(e->device));
+        const size_t S = hb->a_stride, nd = hb->n_docs;
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        // inputs 0..8, then the summary, the work memory and the four outputs
+        const size_t sz[15] = {nd * sizeof(hm_doc_row), hb->n_changes * sizeof(hm_change_row), hb->n_ops * sizeof(hm_op_row),
+                               nd * sizeof(hm_doc_result), (size_t)hb->n_changes * 4, (size_t)hb->n_changes * S * 4,
+                               doc_index ? (size_t)n * 4 : 0, (size_t)n * 4, (size_t)n * 4,
+                               sizeof(hm_op_diff_summary), hm_op_diffs_work_bytes(hb, n),
+                               (size_t)out->cap_rows * sizeof(hm_op_diff), (size_t)out->cap_surv * sizeof(hm_surv_result),
+                               (size_t)n * 8, (size_t)n * 4};
+        const void *src[9] = {hb->docs, hb->changes, hb->ops, hr->docs, hr->hist, hr->all_deps, doc_index, from, to};
+        size_t off[15], total = 0;
+        for (int i = 0; i < 15; i++) { off[i] = total; total += al(sz[i] ? sz[i] : 1); }
+        char *base = nullptr;
+        if (hipMalloc((void **)&base, total) != hipSuccess) return fail(e, HM_ERR_NOMEM, "hipMalloc op-diff staging");
+        hipStream_t s = e->stream;
+        hm_batch b = *hb;
+        b.docs = (const hm_doc_row *)(base + off[0]); b.changes = (const hm_change_row *)(base + off[1]);
+        b.deps = nullptr; b.n_deps = 0; b.ops = (const hm_op_row *)(base + off[2]);
+        hm_results d = {};
+        d.docs = (hm_doc_result *)(base + off[3]); d.hist = (int32_t *)(base + off[4]); d.all_deps = (uint32_t *)(base + off[5]);
+        hm_op_diff_out o = *out;
+        o.rows = (hm_op_diff *)(base + off[11]); o.surv = (hm_surv_result *)(base + off[12]);
+        o.range = (uint32_t *)(base + off[13]); o.flags = (uint32_t *)(base + off[14]);
+        hm_op_diff_summary sum;
+        memset(&sum, 0, sizeof sum);
+        hipError_t rr = hipSuccess;
+        for (int i = 0; i < 9 && rr == hipSuccess; i++)
+            if (sz[i]) rr = hipMemcpyAsync(base + off[i], src[i], sz[i], hipMemcpyHostToDevice, s);
+        int rc = HM_OK;
+        if (rr == hipSuccess)
+            rc = hm_op_diffs_device(e, &b, &d, n, doc_index ? (const uint32_t *)(base + off[6]) : nullptr,
+                                    (const uint32_t *)(base + off[7]), (const uint32_t *)(base + off[8]), &o,
+                                    (hm_op_diff_summary *)(base + off[9]), base + off[10], s);
+        if (rc == HM_OK && rr == hipSuccess) rr = hipMemcpyAsync(&sum, base + off[9], sizeof sum, hipMemcpyDeviceToHost, s);
+        if (rc == HM_OK && rr == hipSuccess) rr = hipStreamSynchronize(s);
+        const bool fits = sum.totals[0] <= out->cap_rows && sum.totals[1] <= out->cap_surv;
+        if (rc == HM_OK && rr == hipSuccess && !sum.bad && fits) {
+            if (sum.totals[0]) rr = hipMemcpy(out->rows, o.rows, (size_t)sum.totals[0] * sizeof(hm_op_diff), hipMemcpyDeviceToHost);
+            if (rr == hipSuccess && sum.totals[1]) rr = hipMemcpy(out->surv, o.surv, (size_t)sum.totals[1] * sizeof(hm_surv_result), hipMemcpyDeviceToHost);
+            if (rr == hipSuccess) rr = hipMemcpy(out->range, o.range, sz[13], hipMemcpyDeviceToHost);
+            if (rr == hipSuccess) rr = hipMemcpy(out->flags, o.flags, sz[14], hipMemcpyDeviceToHost);
+        }
+        (void)hipFree(base);
+        if (rc != HM_OK) return rc;
+        if (rr != hipSuccess) return hip_fail(e, rr, "hm_op_diffs_host");
+        if (sum.bad & HM_OD_BAD_HANDLE) return fail(e, HM_ERR_INVALID, "hm_op_diffs: a document outside the batch");
+        if (sum.bad & HM_OD_BAD_ROWS) return fail(e, HM_ERR_INVALID, "a change row outside its document's segments");
+        if (sum.bad) return fail(e, HM_ERR_NOMEM, "a document outgrows the op-diff work memory");
+        if (out_totals) { out_totals[0] = sum.totals[0]; out_totals[1] = sum.totals[1]; }
+        if (!fits) return fail(e, HM_ERR_NOMEM, "a capacity below the rows of the op diffs");
+        return HM_OK;
+    } catch (...) {
+        return fail(e, HM_ERR_DEVICE, "exception in hm_op_diffs_host");
     }
 }
 

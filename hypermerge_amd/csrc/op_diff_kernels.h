@@ -1,0 +1,71 @@
+// op_diff_kernels.h — launch interface of op_diff_kernels.hip (store.cpp, engine.cpp)
+#pragma once
+#include <hip/hip_runtime.h>
+#include "../../include/hypermerge_amd.h"
+#include "doc_source.h"
+#include "past_kernels.h"
+
+// history positions per bitmap tile of the walk (a longer history takes several tiles, each a pass
+// over the document's hist rows); a tile's ops are taken 64 at a time in application order
+#define HM_OD_TILE 512u
+
+// What each applied op of a history slice did to its document: request i = (handles[i], from[i],
+// to[i]) covers the applied changes at history positions from <= p < to, a handle may repeat.  In
+// application order (history position of the change, op index in the change) a make op emits a
+// `create` row, an assign on a map / table register the register as it stands after that op (the
+// survivors, winner first), `ins` nothing.  A range that holds an assign on a list / text object is
+// flagged HM_OD_LISTS and gets no rows.  Queued (hist -1) and duplicate (hist -2) changes contribute
+// nothing.
+//
+//   count  one wave per request: cnt[4i ..] = diff rows, survivor rows, 0, 0; aux[2i ..] = 0, flags
+//   scan   past_scan_kernel (hm_launch_past_scan): off[4i ..] = exclusive prefix sums of cnt in request
+//          order, sum = totals (rows, survivors), the maxima and the OR of the flags
+//   fill   one wave per request, nothing written when a total exceeds its cap: the rows, their
+//          survivors, out_range[2i ..] = (first row, rows), out_flags[i]
+//
+// Count and fill are one walk: the wave takes the document's applied ops in application order, tile
+// by tile, 64 ops a step, and threads every map register's assigns into a chain (previous / next
+// assign on the register, the op's change) in its slice of `work`; an op of the range then walks
+// its register's chain backwards, and from each set / link forwards again to itself, to know
+// whether a later assign covers it and which incs it collects.  A wave's slice holds
+// hm_od_slice_words(ops, registers, objects) words of the largest document it meets; a document
+// that needs more sets HM_OD_BAD_WORK and gets empty ranges.
+#define HM_OD_BAD_HANDLE 1u
+#define HM_OD_BAD_ROWS 2u
+#define HM_OD_BAD_WORK 4u
+
+__host__ __device__ inline unsigned long long hm_od_slice_words(unsigned long long n_ops, unsigned long long n_regs, unsigned long long n_objs) {
+    return 3ull * n_ops + n_regs + n_objs;
+}
+
+// workgroups (one wave each) of a call whose largest document needs slice_words: as many as the
+// requests, the waves a 256-CU device keeps resident (8,704 B of LDS each: 16 to a CU) and a
+// 256 MiB work budget allow, at least one
+inline uint32_t hm_od_waves(uint32_t n, unsigned long long slice_words) {
+    const unsigned long long budget = (256ull << 20) / 4ull, by_mem = budget / (slice_words ? slice_words : 1ull);
+    unsigned long long w = n < 4096u ? n : 4096u;
+    if (by_mem < w) w = by_mem;
+    return (uint32_t)(w ? w : 1ull);
+}
+
+struct OpDiffArgs {
+    uint32_t n;
+    DocSource src;
+    const uint32_t *from, *to;                 // [n]
+    uint32_t *cnt, *aux, *off;                 // [4n], [2n], [4n]
+    unsigned long long *part;                  // [hm_past_scan_chunks(n) * HM_PAST_PART]
+    hm_op_diff_summary *sum;
+    uint32_t *work;                            // [waves * slice_words]
+    unsigned long long slice_words;
+    uint32_t waves;                            // workgroups of the count and fill launches
+    // fill pass
+    uint32_t cap_rows, cap_surv;
+    hm_op_diff *out_rows;
+    hm_surv_result *out_surv;
+    uint32_t *out_range, *out_flags;           // [2n], [n]
+};
+// the largest slice a request of the call needs, left in *out_words (device, zeroed by the caller)
+hipError_t hm_launch_op_diff_need(const OpDiffArgs &a, unsigned long long *out_words, hipStream_t s);
+// count + scan (sum need not be zeroed; n == 0: sum is zeroed and nothing else is read or written)
+hipError_t hm_launch_op_diff_count(const OpDiffArgs &a, hipStream_t s);
+hipError_t hm_launch_op_diff_fill(const OpDiffArgs &a, hipStream_t s);

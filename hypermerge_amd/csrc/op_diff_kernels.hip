@@ -1,0 +1,309 @@
+// op_diff_kernels.hip — what each applied op of a history slice did to its document (Automerge
+// makePatch's per-op diffs; RepoBackend's MaterializeMsg reply and every applyChanges return them
+// with the merge): per make op a `create` row, per assign on a map / table register the register
+// as it stands after that op.  Everything is read from tables the merge left resident (hist,
+// all_deps, the change and op rows); no state is replayed.
+//
+// The rule (oracle/js/backend.js applyAssign; docset.cpp Replay::assign is the same in C++).  The
+// application key of an op is (history position of its change, op index in the change).  For an
+// assign k on register r, A(k) = the applied assigns on r with key <= key(k), over the whole history:
+//   survivors  x in A(k), set or link, such that no set / del / link y in A(k) after x has
+//              all_deps[change(y)][actor(x)] >= seq(x)  (a change's own column holds seq - 1: the ops
+//              of one change are concurrent)
+//   value      x's own; a counter set with a numeric value adds every inc y in A(k) after x with
+//              all_deps[change(y)][actor(x)] >= seq(x), in application order (INT + INT stays INT,
+//              anything else is an f64 sum tagged FLOAT)
+//   order      actor rank descending; two survivors of one actor are ops of one change, and of
+//              x before y, y comes first exactly when A(k) holds an odd number of ops with key >=
+//              key(y) (every assign reverses the list once after appending)
+//
+//  od_need_kernel    a lane per request: the largest work slice a request's document needs
+//  od_walk_kernel    <false> count, <true> fill; one wavefront per request, a 64-lane workgroup of its
+//                    own; per tile of HM_OD_TILE history positions below `to`:
+//    mark / rank / scatter / scan   as past_fill_kernel: the tile's applied changes in history order
+//             with their op rows' offsets (wave.h HistTile, wave_incl_scan)
+//    then 64 ops a step in application order, a lane per op:
+//      types  a make op leaves its object's type in the slice
+//      link   an assign on a map / table register joins the register's chain: matches inside the
+//             step are found in the wave (64 lane reads), last[reg] carries the chain across steps
+//      emit   the ops of the range: rows are numbered by ballot, survivors by a wave scan of the
+//             counts a first walk of the chain returns; the fill pass walks again to write them
+//  The scan between count and fill is past_scan_kernel (hm_launch_past_scan).
+//
+// Every loop over a chain is bounded by the document's op rows, so tables that are not a merge's
+// (overlapping op ranges) cannot hang a wave; no row past a lim_* of the source is read.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/hypermerge_amd.h"
+#include "op_diff_kernels.h"
+#include "wave.h"
+
+namespace hmo {
+
+#define OWG 64
+#define OTILE HM_OD_TILE
+static_assert(sizeof(hm_op_row) == 32 && sizeof(hm_change_row) == 24 && sizeof(hm_op_diff) == 16 && sizeof(hm_surv_result) == 16, "row sizes");
+static_assert(sizeof(hm_op_diff_summary) == sizeof(hm_past_summary), "the scan writes the summary as hm_past_summary");
+static_assert(offsetof(hm_op_diff_summary, flags) == offsetof(hm_past_summary, doc_flags) &&
+              offsetof(hm_op_diff_summary, bad) == offsetof(hm_past_summary, bad) &&
+              offsetof(hm_op_diff_summary, max_surv) == offsetof(hm_past_summary, max_deps), "summary layout");
+
+__global__ __launch_bounds__(256) void od_need_kernel(OpDiffArgs A, unsigned long long *out_words) {
+    const unsigned long long q = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (q >= A.n) return;
+    const DocRef s = doc_of(A.src, q);
+    if (s.bad) return;
+    atomicMax(out_words, hm_od_slice_words(s.n_o, s.n_r, s.n_objs));
+}
+
+struct Lds {
+    HistTile<OTILE> tile;
+    uint32_t src[OTILE];                       // per slot: the change's log row (document-local)
+    uint32_t hp[OTILE];                        // per slot: its history position
+    uint32_t op[OTILE];                        // per slot: op rows, then their offset within the tile
+    uint32_t of[OTILE];                        // per slot: the change's first source op row
+};
+
+// a wave's slice of the work memory, laid out for one document
+struct Slice {
+    uint32_t *prev, *next, *chg;               // per document-local op: the chain and the op's change (log row)
+    uint32_t *last;                            // per register: the last op of its chain so far
+    uint32_t *otype;                           // per object: 0, or 1 + the make action that created it
+};
+
+__device__ __forceinline__ bool numeric(uint32_t vt) { return vt == HM_V_INT || vt == HM_V_FLOAT; }
+__device__ __forceinline__ double num(uint32_t vt, uint64_t v) {
+    return vt == HM_V_INT ? (double)(int64_t)v : __longlong_as_double((long long)v);
+}
+
+// survivor order: does a come before b?  (key = vtag word while a row is being built: the tag in
+// bits 0-7, the actor rank in bits 8-23, bit 31 = the parity of the ops of A(k) at or after the op)
+__device__ __forceinline__ bool before(uint32_t a_op, uint32_t a_key, uint32_t b_op, uint32_t b_key) {
+    const uint32_t ra = (a_key >> 8) & 0xFFFFu, rb = (b_key >> 8) & 0xFFFFu;
+    if (ra != rb) return ra > rb;
+    const bool a_later = a_op > b_op;          // (one change: op order is application order)
+    const bool odd = ((a_later ? a_key : b_key) >> 31) != 0u;
+    return a_later == odd;
+}
+
+// The register of op k as it stands after k: returns its survivors; out != NULL: written to
+// out[0 .. n) in their order, at most room of them.
+__device__ uint32_t walk(const DocSource &D, const DocRef &s, const Slice &W, uint32_t k, hm_surv_result *out, uint32_t room) {
+    uint32_t n = 0, step = 0;
+    for (uint32_t x = k; x != HM_NONE && step < s.n_o; x = W.prev[x]) {
+        step++;                                // ops of A(k) with key >= key(x)
+        const hm_op_row xo = D.ops[s.o_off + x];
+        if (xo.action != HM_SET && xo.action != HM_LINK) continue;
+        const hm_change_row cx = D.changes[s.c_off + W.chg[x]];
+        const uint32_t ax = cx.actor, sx = cx.seq;
+        const bool counter = xo.datatype == HM_DT_COUNTER;
+        uint32_t vt = xo.vtag;
+        uint64_t val = xo.value;
+        bool alive = true;
+        if (x != k) {
+            uint32_t guard = 0;
+            for (uint32_t y = W.next[x]; y != HM_NONE && guard < s.n_o; y = W.next[y], guard++) {
+                const hm_op_row yo = D.ops[s.o_off + y];
+                const bool covers = ax < D.S && D.all_deps[(size_t)(s.c_off + W.chg[y]) * D.S + ax] >= sx;
+                if (yo.action == HM_INC) {
+                    if (covers && counter && numeric(vt)) {
+                        if (vt == HM_V_INT && yo.vtag == HM_V_INT) val = (uint64_t)((int64_t)val + (int64_t)yo.value);
+                        else {
+                            val = (uint64_t)__double_as_longlong(num(vt, val) + num(yo.vtag, yo.value));
+                            vt = HM_V_FLOAT;
+                        }
+                    }
+                } else if (covers) { alive = false; break; }
+                if (y == k) break;
+            }
+        }
+        if (!alive) continue;
+        if (out && n < room) {
+            const uint32_t key = (vt & 0xFFu) | (ax << 8) | ((step & 1u) << 31);
+            uint32_t j = n;                    // insertion by `before` (a register holds a handful of survivors)
+            for (; j > 0; j--) {
+                const hm_surv_result p = out[j - 1];
+                if (!before(x, key, p.op, p.vtag)) break;
+                out[j] = p;
+            }
+            hm_surv_result r;
+            r.op = x; r.vtag = key; r.value = val;
+            out[j] = r;
+        }
+        n++;
+    }
+    if (out) for (uint32_t j = 0; j < n && j < room; j++) out[j].vtag &= 0xFFu;
+    return n;
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
+    __shared__ Lds L;
+    const uint32_t lane = threadIdx.x;
+    const DocSource &D = A.src;
+    if (FILL) {
+        const hm_op_diff_summary *t = A.sum;                  // (one decision for the whole grid)
+        if (t->totals[0] > A.cap_rows || t->totals[1] > A.cap_surv) return;
+    }
+    uint32_t *const wbase = A.work + (size_t)blockIdx.x * A.slice_words;
+    for (unsigned long long q = blockIdx.x; q < A.n; q += gridDim.x) {
+        DocRef s = doc_of(D, q);
+        const uint32_t from = A.from[q], to = A.to[q];
+        uint4 cn = make_uint4(0, 0, 0, 0), of = make_uint4(0, 0, 0, 0);
+        uint32_t fl = 0;
+        if (FILL) {
+            cn = *(const uint4 *)(A.cnt + 4 * q); of = *(const uint4 *)(A.off + 4 * q);
+            fl = A.aux[2 * q + 1];
+            if (lane == 0) {
+                *(uint2 *)(A.out_range + 2 * q) = make_uint2(of.x, cn.x);
+                A.out_flags[q] = fl;
+            }
+            if (!cn.x) continue;
+        }
+        uint32_t bad = s.bad ? HM_OD_BAD_HANDLE : 0u;
+        if (hm_od_slice_words(s.n_o, s.n_r, s.n_objs) > A.slice_words) { bad |= HM_OD_BAD_WORK; s.n_c = 0; }
+        Slice W;
+        W.prev = wbase; W.next = W.prev + s.n_o; W.chg = W.next + s.n_o; W.last = W.chg + s.n_o; W.otype = W.last + s.n_r;
+        const uint32_t lim = to < s.n_c ? to : s.n_c;          // history positions of interest lie below it
+        uint32_t rows = 0, surv = 0;                           // emitted so far
+        bool lists = false, rows_ok = true;
+        if (from < lim) {
+            for (uint32_t i = lane; i < s.n_r; i += 64u) W.last[i] = HM_NONE;
+            for (uint32_t i = lane; i < s.n_objs; i += 64u) W.otype[i] = 0u;
+        }
+        const uint32_t n_tiles = from < lim ? (lim + OTILE - 1u) / OTILE : 0u;
+        for (uint32_t t = 0; t < n_tiles; t++) {
+            L.tile.clear(lane);
+            __syncthreads();
+            for (uint32_t i = lane; i < s.n_c; i += 64u) {     // mark
+                const int32_t hp = D.hist[s.c_off + i];
+                if (hp >= 0 && (uint32_t)hp < lim && (uint32_t)hp / OTILE == t) L.tile.mark((uint32_t)hp);
+            }
+            __syncthreads();
+            const uint32_t tile_n = L.tile.rank(lane);         // rank
+            __syncthreads();
+            if (!tile_n) continue;
+            for (uint32_t i = lane; i < s.n_c; i += 64u) {     // scatter
+                const int32_t hp = D.hist[s.c_off + i];
+                if (hp < 0 || (uint32_t)hp >= lim || (uint32_t)hp / OTILE != t) continue;
+                uint32_t k;
+                if (!L.tile.slot((uint32_t)hp, k)) continue;
+                const hm_change_row c = D.changes[s.c_off + i];
+                uint32_t no = c.n_ops;
+                if (no && (c.op_first < s.o_off || (unsigned long long)c.op_first + no > (unsigned long long)s.o_off + s.n_o)) { no = 0; rows_ok = false; }
+                L.src[k] = i; L.hp[k] = (uint32_t)hp; L.op[k] = no; L.of[k] = c.op_first;
+            }
+            __syncthreads();
+            uint32_t osum = 0;                                  // scan
+            for (uint32_t k0 = 0; k0 < tile_n; k0 += 64u) {
+                const uint32_t k = k0 + lane;
+                const uint32_t vo = k < tile_n ? L.op[k] : 0u;
+                const uint32_t io = wave_incl_scan(vo, lane);
+                if (k < tile_n) L.op[k] = osum + io - vo;
+                osum += __shfl(io, 63);
+            }
+            __syncthreads();
+            for (uint32_t k0 = 0; k0 < osum; k0 += 64u) {      // the tile's ops, 64 a step in application order
+                const uint32_t k = k0 + lane;
+                const bool valid = k < osum;
+                uint32_t dop = HM_NONE, ci = 0, p = 0, obj = HM_NONE, reg = HM_NONE, action = HM_INS;
+                if (valid) {
+                    uint32_t lo = 0, hi = tile_n;              // the last slot whose op offset is <= k
+                    while (hi - lo > 1u) {
+                        const uint32_t mid = (lo + hi) >> 1;
+                        if (L.op[mid] <= k) lo = mid; else hi = mid;
+                    }
+                    const uint32_t srow = L.of[lo] + (k - L.op[lo]);
+                    const uint4 w0 = *(const uint4 *)(D.ops + srow);          // obj, reg, parent, elem
+                    const uint32_t w1 = ((const uint32_t *)(D.ops + srow))[4]; // action, datatype, vtag, pad
+                    dop = srow - s.o_off; ci = L.src[lo]; p = L.hp[lo];
+                    obj = w0.x; reg = w0.y; action = w1 & 0xFFu;
+                }
+                const bool make = valid && action <= HM_MAKE_TEXT, assign = valid && action >= HM_SET && action <= HM_INC;
+                if (make && obj < s.n_objs) W.otype[obj] = 1u + action;          // types
+                __syncthreads();
+                const uint32_t ot = assign && obj < s.n_objs ? W.otype[obj] : 0u;
+                const bool list = ot == 1u + HM_MAKE_LIST || ot == 1u + HM_MAKE_TEXT;
+                const bool in_range = valid && p >= from;
+                lists |= in_range && list;
+                const bool chain = assign && !list && reg != HM_NONE && reg < s.n_r;
+                const unsigned long long cm = __ballot(chain);
+                if (cm) {                                       // link (uniform branch)
+                    uint32_t pl = HM_NONE, nl = HM_NONE;       // nearest lanes below / above with the same register
+                    for (uint32_t j = 0; j < 64u; j++) {
+                        if (!((cm >> j) & 1ull)) continue;
+                        const uint32_t rj = __shfl(reg, j);
+                        if (chain && rj == reg) {
+                            if (j < lane) pl = j;
+                            else if (j > lane && nl == HM_NONE) nl = j;
+                        }
+                    }
+                    const uint32_t dpl = __shfl(dop, pl == HM_NONE ? lane : pl), dnl = __shfl(dop, nl == HM_NONE ? lane : nl);
+                    if (chain) {
+                        const uint32_t pv = pl != HM_NONE ? dpl : W.last[reg];
+                        W.prev[dop] = pv; W.next[dop] = nl != HM_NONE ? dnl : HM_NONE; W.chg[dop] = ci;
+                        if (pl == HM_NONE && pv != HM_NONE && pv < s.n_o) W.next[pv] = dop;
+                    }
+                    __syncthreads();                            // (last[reg] read by the first lanes before the last lanes write it)
+                    if (chain && nl == HM_NONE) W.last[reg] = dop;
+                    __syncthreads();
+                }
+                const bool emit = in_range && (make || chain);  // emit
+                const unsigned long long em = __ballot(emit);
+                if (!em) continue;
+                const uint32_t row = rows + (uint32_t)__popcll(em & ((1ull << lane) - 1ull));
+                uint32_t ns = 0;
+                if (emit && chain && !(FILL && fl)) ns = walk(D, s, W, dop, nullptr, 0u);
+                const uint32_t is = wave_incl_scan(ns, lane);
+                if (FILL && emit && !fl) {
+                    const uint32_t so = surv + is - ns;
+                    if (row < cn.x && (unsigned long long)so + ns <= cn.y) {
+                        if (ns) walk(D, s, W, dop, A.out_surv + of.y + so, ns);
+                        hm_op_diff r;
+                        r.op = dop; r.kind = make ? HM_OD_CREATE : (ns ? HM_OD_SET : HM_OD_REMOVE); r.n_surv = ns; r.surv_off = of.y + so;
+                        A.out_rows[of.x + row] = r;
+                    }
+                }
+                rows += (uint32_t)__popcll(em); surv += __shfl(is, 63);
+            }
+            __syncthreads();
+        }
+        if (!FILL) {
+            const bool any_lists = __ballot(lists) != 0ull, any_rows_bad = __ballot(!rows_ok) != 0ull;
+            if (any_rows_bad) bad |= HM_OD_BAD_ROWS;
+            if (lane == 0) {
+                *(uint4 *)(A.cnt + 4 * q) = any_lists ? make_uint4(0, 0, 0, 0) : make_uint4(rows, surv, 0, 0);
+                *(uint2 *)(A.aux + 2 * q) = make_uint2(0u, any_lists ? HM_OD_LISTS : 0u);
+                if (bad) atomicOr(&A.sum->bad, bad);
+            }
+        }
+    }
+}
+
+}  // namespace hmo
+
+static PastArgs scan_args(const OpDiffArgs &a) {
+    PastArgs P = {};
+    P.n = a.n; P.cnt = a.cnt; P.aux = a.aux; P.off = a.off; P.part = a.part; P.sum = (hm_past_summary *)a.sum;
+    return P;
+}
+
+hipError_t hm_launch_op_diff_need(const OpDiffArgs &a, unsigned long long *out_words, hipStream_t s) {
+    if (!a.n) return hipSuccess;
+    hipLaunchKernelGGL(hmo::od_need_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a, out_words);
+    return hipGetLastError();
+}
+
+hipError_t hm_launch_op_diff_count(const OpDiffArgs &a, hipStream_t s) {
+    hipError_t r = hipMemsetAsync(a.sum, 0, sizeof(hm_op_diff_summary), s);
+    if (r != hipSuccess || !a.n) return r;                     // (no request: the zero summary is the answer)
+    hipLaunchKernelGGL(hmo::od_walk_kernel<false>, dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+    if ((r = hipGetLastError()) != hipSuccess) return r;
+    return hm_launch_past_scan(scan_args(a), s);
+}
+
+hipError_t hm_launch_op_diff_fill(const OpDiffArgs &a, hipStream_t s) {
+    if (!a.n) return hipSuccess;
+    hipLaunchKernelGGL(hmo::od_walk_kernel<true>, dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+    return hipGetLastError();
+}

@@ -56,3 +56,6 @@ struct PastArgs {
 // count + scan (sum need not be zeroed; n == 0: sum is zeroed and nothing else is read or written)
 hipError_t hm_launch_past_count(const PastArgs &a, hipStream_t s);
 hipError_t hm_launch_past_fill(const PastArgs &a, hipStream_t s);
+// the scan alone over cnt / aux already written (n, cnt, aux, off, part and sum are read): the op-diff
+// kernels reserve their requests' row and survivor blocks with it (op_diff_kernels.hip)
+hipError_t hm_launch_past_scan(const PastArgs &a, hipStream_t s);

@@ -287,9 +287,15 @@ hipError_t hm_launch_past_count(const PastArgs &a, hipStream_t s) {
         hipLaunchKernelGGL(hmp::past_count_kernel, dim3((uint32_t)(wgs < 65535ull ? wgs : 65535ull)), dim3(PCWG), 0, s, a);
         if ((r = hipGetLastError()) != hipSuccess) return r;
     }
+    return hm_launch_past_scan(a, s);
+}
+
+hipError_t hm_launch_past_scan(const PastArgs &a, hipStream_t s) {
+    if (!a.n) return hipSuccess;
     const dim3 chunks(hm_past_scan_chunks(a.n));
     hipLaunchKernelGGL(hmp::past_scan_kernel<false>, chunks, dim3(PSWG), 0, s, a);
-    if ((r = hipGetLastError()) != hipSuccess) return r;
+    const hipError_t r = hipGetLastError();
+    if (r != hipSuccess) return r;
     hipLaunchKernelGGL(hmp::past_scan_kernel<true>, chunks, dim3(PSWG), 0, s, a);
     return hipGetLastError();
 }

@@ -42,6 +42,7 @@
 #include "waiting_kernels.h"
 #include "changes_kernels.h"
 #include "past_kernels.h"
+#include "op_diff_kernels.h"
 
 namespace {
 
@@ -1288,7 +1289,118 @@ int hm_store_materialize_sized(hm_store *s, uint32_t n, const uint32_t *doc_hand
     }
 }
 
+// The count pass of n staged op-diff requests: handles and ranges go to the stage buffer, the counts,
+// offsets and summary stay there (A.cnt / A.off / A.aux / A.sum), the chains' work memory is the
+// head of s->past; *sum = the summary, read back.
+static int op_diff_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                         OpDiffArgs &A, hm_op_diff_summary *sum) {
+    hipStream_t st = hm_engine_stream(s->e);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_sum = 0, o_need = 128, o_h = 256, o_from = o_h + al(4 * (size_t)n), o_to = o_from + al(4 * (size_t)n),
+                 o_cnt = o_to + al(4 * (size_t)n), o_off = o_cnt + al(16 * (size_t)n), o_aux = o_off + al(16 * (size_t)n),
+                 o_part = o_aux + al(8 * (size_t)n), total = o_part + al((size_t)hm_past_scan_chunks(n) * HM_PAST_PART * 8);
+    int rc = ensure_stage(s, total);
+    if (rc) return rc;
+    uint8_t *sp = s->stage.p;
+    SCHK(s, hipMemcpyAsync(sp + o_h, doc_handles, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    SCHK(s, hipMemcpyAsync(sp + o_from, from, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    SCHK(s, hipMemcpyAsync(sp + o_to, to, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    SCHK(s, hipMemsetAsync(sp + o_need, 0, 8, st));
+    A = OpDiffArgs{};
+    A.n = n; A.src = store_source(s); A.src.handles = (const uint32_t *)(sp + o_h);
+    A.from = (const uint32_t *)(sp + o_from); A.to = (const uint32_t *)(sp + o_to);
+    A.cnt = (uint32_t *)(sp + o_cnt); A.off = (uint32_t *)(sp + o_off); A.aux = (uint32_t *)(sp + o_aux);
+    A.part = (unsigned long long *)(sp + o_part);
+    A.sum = (hm_op_diff_summary *)(sp + o_sum);
+    // the largest document of the call sizes a wave's slice of the work memory
+    SCHK(s, hm_launch_op_diff_need(A, (unsigned long long *)(sp + o_need), st));
+    SCHK(s, hipMemcpyAsync(&s->h_cnt[10], sp + o_need, 8, hipMemcpyDeviceToHost, st));
+    SCHK(s, hipStreamSynchronize(st));
+    unsigned long long need;
+    memcpy(&need, &s->h_cnt[10], 8);
+    A.slice_words = need ? need : 1;
+    A.waves = hm_od_waves(n, A.slice_words);
+    if ((rc = ensure_buf(s, s->past, al((size_t)A.waves * A.slice_words * 4)))) return rc;
+    A.work = (uint32_t *)s->past.p;
+    SCHK(s, hm_launch_op_diff_count(A, st));
+    SCHK(s, hipMemcpyAsync(s->h_st, A.sum, sizeof(hm_op_diff_summary), hipMemcpyDeviceToHost, st));
+    SCHK(s, hipStreamSynchronize(st));
+    memcpy(sum, s->h_st, sizeof *sum);
+    if (sum->bad & HM_OD_BAD_HANDLE) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad handle");
+    if (sum->bad & HM_OD_BAD_ROWS) return hm_engine_fail(s->e, HM_ERR_INVALID, "a change row outside its document's segments");
+    if (sum->bad) return hm_engine_fail(s->e, HM_ERR_NOMEM, "a document outgrows the op-diff work memory");
+    return HM_OK;
+}
+
 extern "C" {
+
+int hm_store_op_diff_sizes(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                           uint32_t *out_counts, uint32_t *out_flags, uint64_t *out_totals) {
+    if (!s || (n && (!doc_handles || !from || !to))) return HM_ERR_INVALID;
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        if (out_totals) out_totals[0] = out_totals[1] = 0;
+        if (!n) return HM_OK;
+        OpDiffArgs A;
+        hm_op_diff_summary sum;
+        int rc = op_diff_count(s, n, doc_handles, from, to, A, &sum);
+        if (rc) return rc;
+        if (out_totals) { out_totals[0] = sum.totals[0]; out_totals[1] = sum.totals[1]; }
+        if (out_counts || out_flags) {
+            hipStream_t st = hm_engine_stream(s->e);
+            std::vector<uint32_t> cnt(4 * (size_t)n), aux(2 * (size_t)n);
+            SCHK(s, hipMemcpyAsync(cnt.data(), A.cnt, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
+            SCHK(s, hipMemcpyAsync(aux.data(), A.aux, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+            SCHK(s, hipStreamSynchronize(st));
+            for (size_t i = 0; i < n; i++) {
+                if (out_counts) { out_counts[2 * i] = cnt[4 * i]; out_counts[2 * i + 1] = cnt[4 * i + 1]; }
+                if (out_flags) out_flags[i] = aux[2 * i + 1];
+            }
+        }
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_op_diff_sizes");
+    }
+}
+
+int hm_store_op_diffs(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                      const hm_op_diff_out *out, uint64_t *out_totals) {
+    if (!s || !out || (n && (!doc_handles || !from || !to || !out->range || !out->flags))) return HM_ERR_INVALID;
+    if ((out->cap_rows && !out->rows) || (out->cap_surv && !out->surv)) return HM_ERR_INVALID;
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        if (out_totals) out_totals[0] = out_totals[1] = 0;
+        if (!n) return HM_OK;
+        hipStream_t st = hm_engine_stream(s->e);
+        OpDiffArgs A;
+        hm_op_diff_summary sum;
+        int rc = op_diff_count(s, n, doc_handles, from, to, A, &sum);
+        if (rc) return rc;
+        const uint64_t tr = sum.totals[0], ts = sum.totals[1];
+        if (out_totals) { out_totals[0] = tr; out_totals[1] = ts; }
+        if (tr > out->cap_rows || ts > out->cap_surv)
+            return hm_engine_fail(s->e, HM_ERR_NOMEM, "a capacity below the rows of the op diffs");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        // [work][rows][survivors][ranges][flags]
+        const size_t sz[4] = {tr * sizeof(hm_op_diff), ts * sizeof(hm_surv_result), 8 * (size_t)n, 4 * (size_t)n};
+        size_t o[4], total = al((size_t)A.waves * A.slice_words * 4);
+        for (int i = 0; i < 4; i++) { o[i] = total; total += al(sz[i] + 1); }
+        if ((rc = ensure_buf(s, s->past, total))) return rc;
+        uint8_t *bp = s->past.p;
+        A.work = (uint32_t *)bp;
+        A.cap_rows = (uint32_t)tr; A.cap_surv = (uint32_t)ts;
+        A.out_rows = (hm_op_diff *)(bp + o[0]); A.out_surv = (hm_surv_result *)(bp + o[1]);
+        A.out_range = (uint32_t *)(bp + o[2]); A.out_flags = (uint32_t *)(bp + o[3]);
+        SCHK(s, hm_launch_op_diff_fill(A, st));
+        void *dst[4] = {out->rows, out->surv, out->range, out->flags};
+        for (int i = 0; i < 4; i++)
+            if (sz[i]) SCHK(s, hipMemcpyAsync(dst[i], bp + o[i], sz[i], hipMemcpyDeviceToHost, st));
+        SCHK(s, hipStreamSynchronize(st));
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_op_diffs");
+    }
+}
 
 // (the selection of one prefix request of the past kernels: out_change_log, nothing else gathered)
 int hm_doc_history_prefix(hm_store *s, uint32_t doc, uint32_t n, uint32_t *out) {

@@ -40,7 +40,8 @@ EXPORTS = ("hm_abi_version", "hm_status_message", "hm_engine_create", "hm_engine
            "hm_missing_deps_host", "hm_docset_blocked", "hm_docset_waiting", "hm_store_missing_changes",
            "hm_missing_changes_device", "hm_missing_changes_host", "hm_docset_missing_changes",
            "hm_store_past_sizes", "hm_store_materialize", "hm_materialize_work_bytes", "hm_materialize_device",
-           "hm_docset_materialize")
+           "hm_docset_materialize", "hm_store_op_diff_sizes", "hm_store_op_diffs", "hm_op_diffs_work_bytes",
+           "hm_op_diffs_device", "hm_op_diffs_host", "hm_docset_materialize_patch")
 
 _lib = None
 
@@ -130,6 +131,12 @@ def lib():
             "hm_materialize_work_bytes": [u32],
             "hm_docset_materialize": [vp, u32, vp, vp, vp, vp, vp, vp, vp],
             "hm_materialize_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, vp],
+            "hm_docset_materialize_patch": [vp, u32, vp, vp, vp],
+            "hm_store_op_diff_sizes": [vp, u32, vp, vp, vp, vp, vp, vp],
+            "hm_store_op_diffs": [vp, u32, vp, vp, vp, vp, vp],
+            "hm_op_diffs_work_bytes": [ctypes.POINTER(CBatch), u32],
+            "hm_op_diffs_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, vp],
+            "hm_op_diffs_host": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp],
         }
         for f, a in sig.items():
             getattr(L, f).argtypes = a
@@ -145,6 +152,7 @@ def lib():
         L.hm_decoded_free.restype = None
         L.hm_clock_records_scratch_bytes.restype = ctypes.c_size_t
         L.hm_materialize_work_bytes.restype = ctypes.c_size_t
+        L.hm_op_diffs_work_bytes.restype = ctypes.c_size_t
         L.hm_docset_destroy.restype = None
         L.hm_docset_engine.restype = ctypes.c_void_p
         L.hm_text_data.restype = ctypes.c_void_p
@@ -172,6 +180,26 @@ class CPastSummary(ctypes.Structure):
 
 
 assert ctypes.sizeof(CPastSummary) == 64
+
+
+OD_CREATE, OD_SET, OD_REMOVE = 0, 1, 2   # HM_OD_* row kinds
+OD_LISTS = 1                              # HM_OD_LISTS request flag
+OP_DIFF_DT = np.dtype([("op", "<u4"), ("kind", "<u4"), ("n_surv", "<u4"), ("surv_off", "<u4")])
+
+
+class COpDiffOut(ctypes.Structure):
+    """struct hm_op_diff_out"""
+    _fields_ = [("cap_rows", ctypes.c_uint32), ("cap_surv", ctypes.c_uint32), ("rows", ctypes.c_void_p),
+                ("surv", ctypes.c_void_p), ("range", ctypes.c_void_p), ("flags", ctypes.c_void_p)]
+
+
+class COpDiffSummary(ctypes.Structure):
+    """struct hm_op_diff_summary"""
+    _fields_ = [("totals", ctypes.c_uint64 * 4), ("max_rows", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3),
+                ("max_surv", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("bad", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(COpDiffSummary) == 64 and OP_DIFF_DT.itemsize == 16
 
 
 def pack_entries(have, n: int):
@@ -309,6 +337,47 @@ class Engine:
         self._check(self._L.hm_materialize_device(self._h, ctypes.byref(cbatch), ctypes.byref(cresults), n, p(doc_index),
                                                   p(hist_len), p(clock_rows), ctypes.byref(out), p(out_summary), p(work),
                                                   p(stream)), "hm_materialize_device")
+
+    def op_diffs_host(self, batch: Batch, results: Results, docs, frm, to, cap=None):
+        """hm_op_diffs_host: what each applied op of the history slices [frm[i], to[i]) of documents
+        docs[i] of a merged batch did (None: every document, one request each).  Returns (rows
+        OP_DIFF_DT, survivors SURV_RESULT_DT, ranges [n, 2] = first row and rows per request, flags [n]);
+        a request flagged OD_LISTS has no rows.  cap = (rows, survivors) the tables hold (None: every
+        op of the batch per request, which no slice exceeds in rows; survivors are sized by a first
+        call's totals when that is too small)."""
+        from .columnar import SURV_RESULT_DT
+        idx = None if docs is None else np.ascontiguousarray(docs, np.uint32)
+        n = batch.n_docs if idx is None else len(idx)
+        f, t = np.ascontiguousarray(frm, np.uint32), np.ascontiguousarray(to, np.uint32)
+        assert len(f) == n and len(t) == n
+        cb, cr = batch.c_struct(), results.c_struct()
+        tot = (ctypes.c_uint64 * 2)()
+        caps = cap if cap is not None else (0, 0)
+        for _ in range(2):
+            rows, surv = np.zeros(max(caps[0], 1), OP_DIFF_DT), np.zeros(max(caps[1], 1), SURV_RESULT_DT)
+            rng, fl = np.zeros((max(n, 1), 2), np.uint32), np.zeros(max(n, 1), np.uint32)
+            out = COpDiffOut(caps[0], caps[1], rows.ctypes.data, surv.ctypes.data, rng.ctypes.data, fl.ctypes.data)
+            st = self._L.hm_op_diffs_host(self._h, ctypes.byref(cb), ctypes.byref(cr), n,
+                                          idx.ctypes.data if idx is not None and n else None,
+                                          f.ctypes.data if n else None, t.ctypes.data if n else None, ctypes.byref(out), tot)
+            if st == 34 and cap is None and (tot[0] > caps[0] or tot[1] > caps[1]):   # HM_ERR_NOMEM: sized by the totals
+                caps = (int(tot[0]), int(tot[1]))
+                continue
+            break
+        self._check(st, "hm_op_diffs_host")
+        return rows[:int(tot[0])], surv[:int(tot[1])], rng[:n], fl[:n]
+
+    def op_diffs_work_bytes(self, cbatch: CBatch, n: int) -> int:
+        return int(self._L.hm_op_diffs_work_bytes(ctypes.byref(cbatch), n))
+
+    def op_diffs_device(self, cbatch: CBatch, cresults: CResults, n: int, doc_index: int, frm: int, to: int,
+                        out: "COpDiffOut", out_summary: int, work: int, stream: int = 0) -> None:
+        """hm_op_diffs_device: the same with every table in device memory (pointers; `out` a COpDiffOut of
+        device tables, `work` of op_diffs_work_bytes(cbatch, n) bytes; enqueued, not synchronised)."""
+        p = lambda x: ctypes.c_void_p(x) if x else None
+        self._check(self._L.hm_op_diffs_device(self._h, ctypes.byref(cbatch), ctypes.byref(cresults), n, p(doc_index),
+                                               p(frm), p(to), ctypes.byref(out), p(out_summary), p(work), p(stream)),
+                    "hm_op_diffs_device")
 
     def small_occupancy(self, batch: Batch) -> Sequence[int]:
         """(resident one-wave workgroups per CU, CUs, op rows per lane, size class, lists, counters) of

@@ -568,6 +568,26 @@ class GpuEngine {
     return out
   }
 
+  // the patches of documents as they were, many at once: reqs[i] = {state | id, history: n} -> per
+  // request {history, patch}: the patch Backend.applyChanges(Backend.init(), history.slice(0, n))
+  // returns ({clock, deps, canUndo: false, canRedo: false, diffs}), its per-op diffs read off the
+  // resident tables on the device.  A prefix that assigns list / text elements comes back with
+  // patch: null (an element's diff needs its index at that moment): the caller replays that one on
+  // the host.  Reflects the rounds already applied: in 'async' mode await idle() first.
+  materializePatch(reqs) {
+    const states = reqs.map((r) => r.state || this.stateOf(r.id))
+    const out = new Array(reqs.length)
+    this.docsets.forEach((ds, k) => {
+      const at = []
+      states.forEach((st, i) => { if (st.shard === k) at.push(i) })
+      if (!at.length) return
+      const hl = Uint32Array.from(at.map((i) => Math.min(Math.max(Math.floor(Number(reqs[i].history) || 0), 0), 0xffffffff)))
+      const got = JSON.parse(addon.docsetMaterializePatch(ds, Uint32Array.from(at.map((i) => states[i].id)), hl))
+      at.forEach((i, j) => { out[i] = { history: got[j].history, patch: got[j].patch } })
+    })
+    return out
+  }
+
   stateOf(docId) {
     const st = this.byDocId[this.shardOf(docId)].get(docId)
     if (st) return st
@@ -1025,9 +1045,14 @@ class DocBackend {
   // the document as it was when its history had n entries (Repo.materialize(url, n)): {clock, deps,
   // history, doc}, doc = the plain document that materializing Backend.applyChanges(Backend.init(),
   // history.slice(0, n)) gives, computed on the device from the resident log (undefined before init;
-  // of the rounds already applied: in 'async' mode await engine.idle() first).  The patch-shaped
-  // MaterializeMsg reply still replays history.slice(0, n) on the host.
+  // of the rounds already applied: in 'async' mode await engine.idle() first).
   materializeAt(n) { return this.back ? this.engine.materialize([{ state: this.back, history: n }])[0] : undefined }
+
+  // the patch-shaped MaterializeMsg reply: {history, patch} with the patch that
+  // Backend.applyChanges(Backend.init(), history.slice(0, n)) returns, its diffs computed on the
+  // device from the resident log.  patch is null when the prefix assigns list / text elements:
+  // that prefix is replayed on the host (INTEGRATION.md).  undefined before init.
+  materializePatchAt(n) { return this.back ? this.engine.materializePatch([{ state: this.back, history: n }])[0] : undefined }
 
   // changes: Change objects (the reference's), or raw hypercore blocks / JSON texts of them
   applyRemoteChanges(changes) { this.remoteChangesQ.push(changes) }

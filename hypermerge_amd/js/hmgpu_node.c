@@ -1040,6 +1040,31 @@ static napi_value DocsetMaterialize(napi_env env, napi_callback_info info) {
     return js;
 }
 
+/* docsetMaterializePatch(docset, ids Uint32Array, histLen Uint32Array) -> JSON text, per request
+ * {"doc", "history", "patch"}: the patch of the document as it was at that history length (clock, deps,
+ * per-op diffs from the device), or "patch": null with "host": true when the prefix assigns list /
+ * text elements (refused while a call on the docset is in flight) */
+static napi_value DocsetMaterializePatch(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return NULL;
+    Docset *d = get_docset(env, argv[0]);
+    if (!d) return NULL;
+    void *p[2]; size_t len[2];
+    for (int i = 0; i < 2; i++)
+        if (!get_bytes(env, argv[1 + i], &p[i], &len[i])) return NULL;
+    const uint32_t n = (uint32_t)(len[0] / 4);
+    if (len[1] / 4 != n || (n && (!p[0] || !p[1]))) { napi_throw_type_error(env, NULL, "docsetMaterializePatch: one history length per document"); return NULL; }
+    hm_text *t = NULL;
+    int st = hm_docset_materialize_patch(d->ds, n, (const uint32_t *)p[0], (const uint32_t *)p[1], &t);
+    if (st) return throw_status(env, d->engine, st, "hm_docset_materialize_patch");
+    size_t tl = 0;
+    const char *s = hm_text_data(t, &tl);
+    napi_value js;
+    napi_create_string_utf8(env, s, tl, &js);
+    hm_text_free(t);
+    return js;
+}
+
 /* docsetInfo(docset, doc) ->{aStride, nChanges, nOps, nActors, nObjs, nRegs, histLen, nQueued} */
 static napi_value DocsetInfo(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -1301,7 +1326,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"docsetCreate", DocsetCreate}, {"docsetOpen", DocsetOpen}, {"docsetApply", DocsetApply}, {"docsetApplyPacked", DocsetApplyPacked},
         {"docsetHistoryPrefix", DocsetHistoryPrefix}, {"docsetClockUpdate", DocsetClockUpdate},
         {"docsetView", DocsetView}, {"docsetBlocked", DocsetBlocked}, {"docsetWaiting", DocsetWaiting},
-        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetMaterialize", DocsetMaterialize}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
+        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetMaterialize", DocsetMaterialize}, {"docsetMaterializePatch", DocsetMaterializePatch}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
         {"cursorsCreate", CursorsCreate}, {"cursorsReserve", CursorsReserve}, {"cursorsUpdate", CursorsUpdate},
         {"cursorsGet", CursorsGet}, {"cursorsEntry", CursorsEntry}, {"cursorsDocsWithActors", CursorsDocsWithActors},
         {"syncRanges", SyncRanges}, {"decodeBlocks", DecodeBlocks}, {"commCreateLocalDocsets", CommCreateLocalDocsets},

@@ -552,6 +552,82 @@ int hm_materialize_device(hm_engine *e, const hm_batch *b, const hm_results *r, 
                           const uint32_t *hist_len, const uint32_t *clock_rows, const hm_past_out *out,
                           hm_past_summary *out_summary, void *work, void *stream);
 
+/* What each applied op of a history slice did to the document: the per-op diffs of Automerge's
+ * makePatch (the patch of src/RepoBackend.ts:570-579 MaterializeMsg and of every applyChanges), read
+ * off the resident tables without replaying anything.  Request i = document doc_handles[i] (a handle
+ * may repeat) with the applied changes at history positions from[i] <= p < min(to[i], history.size).
+ * In application order (history position of the change, op index in the change) the ops emit
+ *   make op                                   one HM_OD_CREATE row
+ *   ins                                       nothing
+ *   set / del / link / inc with a register    one row: the register as it stands after that op,
+ *   (reg < n_regs) on a map or table object   HM_OD_SET with its survivors (winner first, then the
+ *                                             conflicts), or HM_OD_REMOVE when none is left
+ * The survivors of an assign k on a register are taken over A(k), the applied assigns on it up to and
+ * including k in the whole history: a set / link x survives when no later set / del / link y of A(k)
+ * has all_deps[change(y)][actor(x)] >= seq(x); a numeric counter set adds the later incs of A(k) that
+ * cover it the same way, in application order (INT + INT stays INT, else an f64 sum tagged FLOAT);
+ * the order is actor rank descending, and of two survivors x before y of one change y comes first
+ * exactly when A(k) holds an odd number of ops at or after y (applyAssign's sortBy(actor).reverse()).
+ * Queued (hist -1) and duplicate (hist -2) changes contribute nothing.  A range that holds an assign
+ * on an object made by makeList / makeText is flagged HM_OD_LISTS and gets no rows (a list element's
+ * diff needs its index at that moment: the caller replays such a range on the host); a range that
+ * only creates or inserts into a list is answered. */
+#define HM_OD_CREATE 0u
+#define HM_OD_SET 1u
+#define HM_OD_REMOVE 2u
+#define HM_OD_LISTS 1u      /* request flag: no rows, replay the range on the host */
+typedef struct {          /* 16 B */
+    uint32_t op;          /* document-local op index, as hm_doc_log orders them */
+    uint32_t kind;        /* HM_OD_CREATE | HM_OD_SET | HM_OD_REMOVE */
+    uint32_t n_surv;
+    uint32_t surv_off;    /* into the call's table of hm_surv_result: winner first, then conflicts
+                             (a survivor's `op` is a document-local op index too) */
+} hm_op_diff;
+typedef struct {          /* 64 B */
+    uint64_t totals[4];   /* diff rows and survivor rows of all requests, 0, 0 */
+    uint32_t max_rows, reserved[3], max_surv;   /* the largest request */
+    uint32_t flags;       /* OR of the requests' flags */
+    uint32_t bad;         /* _device form: 1 a handle outside the source, 2 a change row outside its document,
+                             4 a document that outgrows the work memory */
+    uint32_t pad;
+} hm_op_diff_summary;
+typedef struct {
+    uint32_t cap_rows, cap_surv;   /* rows the two tables hold */
+    hm_op_diff     *rows;          /* [cap_rows] request order, application order within a request */
+    hm_surv_result *surv;          /* [cap_surv] */
+    uint32_t       *range;         /* [2n] (first row, rows) per request */
+    uint32_t       *flags;         /* [n] HM_OD_* per request */
+} hm_op_diff_out;
+/* The count pass alone: out_counts [2n] = diff rows, survivor rows per request, out_flags [n],
+ * out_totals [2] the sums (each may be NULL).  HM_ERR_INVALID: a handle outside the store.  No batch
+ * in flight. */
+int hm_store_op_diff_sizes(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                           uint32_t *out_counts, uint32_t *out_flags, uint64_t *out_totals);
+/* The rows as host tables (out->range and out->flags are required, the two tables when their
+ * capacity is not 0).  out_totals [2] (optional) = rows needed per table; HM_ERR_NOMEM with out_totals
+ * filled and no other output written when one exceeds its capacity; HM_ERR_INVALID (outputs
+ * untouched) for a handle outside the store; a call between submit and wait is refused.  n == 0
+ * launches nothing. */
+int hm_store_op_diffs(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                      const hm_op_diff_out *out, uint64_t *out_totals);
+/* The same over the tables of a merged cold batch (b's docs / changes / ops, r's docs / hist /
+ * all_deps), everything in device memory, enqueued on `stream` (NULL = the engine's) without
+ * synchronising.  Request i = document doc_index[i] of b (NULL: document i).  *out_summary (device)
+ * is valid after synchronising; when a total exceeds its capacity nothing is written to out.
+ * `work` = device memory of hm_op_diffs_work_bytes(b, n) bytes (b's counts and launch hints are
+ * read, not its tables; without max_ops / max_regs / max_objs hints the batch totals size it),
+ * 16-byte aligned as b->ops must be (HM_ERR_INVALID otherwise); afterwards its first 4n words are
+ * the per-request counts (rows, survivors, 0, 0) and the next 4n their offsets.  n == 0:
+ * *out_summary is zeroed and nothing else is touched.  A document whose status is not HM_OK offers
+ * nothing. */
+size_t hm_op_diffs_work_bytes(const hm_batch *b, uint32_t n);
+int hm_op_diffs_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                       const uint32_t *from, const uint32_t *to, const hm_op_diff_out *out,
+                       hm_op_diff_summary *out_summary, void *work, void *stream);
+/* _host: host tables in, host rows out (staged, synchronous), errors as hm_store_op_diffs. */
+int hm_op_diffs_host(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                     const uint32_t *from, const uint32_t *to, const hm_op_diff_out *out, uint64_t *out_totals);
+
 /* minimumClock row of a document (rank-indexed, 0 = absent); used for the
  * min_cmp of the next merges (Clock.cmp(DocBackend.clock, minimumClock)). */
 int hm_doc_set_min_clock(hm_store *s, uint32_t doc, const uint32_t *clock);
@@ -745,6 +821,16 @@ int hm_docset_missing_changes(hm_docset *ds, uint32_t n, const uint32_t *docs, c
 int hm_docset_materialize(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len,
                           const uint32_t *entry_off, const char *actor_ids, const uint32_t *actor_off,
                           const double *seqs, hm_text **out);
+/* the patch of a document as it was (the reply of src/RepoBackend.ts:570-579 MaterializeMsg:
+ * Backend.applyChanges(Backend.init(), history.slice(0, n))[1]): request i = document docs[i] (may
+ * repeat) at history length hist_len[i].  Result text = JSON array, per request {"doc": id, "history":
+ * history.size of the prefix, "patch": {"clock", "deps", "canUndo": false, "canRedo": false, "diffs"}}:
+ * clock and deps are the prefix's (hm_store_materialize), the diffs are Automerge's per-op sequence
+ * (create, map set, map remove) rendered from hm_store_op_diffs' rows, nothing replayed on the host.
+ * A prefix that assigns list / text elements gets "patch": null and "host": true: the caller replays
+ * it.  A document not placed yet: the empty patch.  HM_ERR_UNSUPPORTED on a docset created with
+ * HM_DOCSET_NO_PATCHES or HM_DOCSET_NET_DIFFS (it keeps no per-op view of the log). */
+int hm_docset_materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, hm_text **out);
 /* the merged document: {uuid: {"type", "keys": [[key, entry]], "elems": [[elemId, entry]]}} */
 int hm_docset_view(hm_docset *ds, uint32_t doc, hm_text **out);
 /* counters: calls, documents, class moves, net patches from the hit registers, net patches from every

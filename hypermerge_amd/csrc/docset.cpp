@@ -2236,7 +2236,11 @@ int hm_docset_materialize(hm_docset *ds, uint32_t n, const uint32_t *docs, const
 }
 
 int hm_docset_materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, hm_text **out) {
-    if (!ds || !out || (n && (!docs || !hist_len))) return HM_ERR_INVALID;
+    return hm_docset_materialize_patch_ex(ds, n, docs, hist_len, 0u, out);
+}
+
+int hm_docset_materialize_patch_ex(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, uint32_t opts, hm_text **out) {
+    if (!ds || !out || (n && (!docs || !hist_len)) || (opts & ~HM_ODF_LISTS)) return HM_ERR_INVALID;
     *out = nullptr;
     Busy b(ds);
     if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
@@ -2266,13 +2270,13 @@ int hm_docset_materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs,
             // the diffs: what each op of the prefix did, from the resident tables
             const std::vector<uint32_t> from(k, 0u);
             uint64_t tot[2] = {0, 0};
-            if ((rc = hm_store_op_diff_sizes(ds->stores[c], k, hs.data(), from.data(), hl.data(), nullptr, nullptr, tot))) return rc;
+            if ((rc = hm_store_op_diff_sizes_ex(ds->stores[c], k, hs.data(), from.data(), hl.data(), nullptr, nullptr, tot, opts))) return rc;
             if (tot[0] > 0xFFFFFFFFull || tot[1] > 0xFFFFFFFFull) return hm_engine_fail(ds->e, HM_ERR_NOMEM, "a call's rows stay below 2^32");
             std::vector<hm_op_diff> rows(tot[0] + 1);
             std::vector<hm_surv_result> surv(tot[1] + 1);
-            std::vector<uint32_t> range(2 * (size_t)k), flags(k);
+            std::vector<uint32_t> range(2 * (size_t)k), flags(k), index(tot[0] + 1);   // (index: element rows, HM_ODF_LISTS)
             hm_op_diff_out po = {(uint32_t)tot[0], (uint32_t)tot[1], rows.data(), surv.data(), range.data(), flags.data()};
-            if ((rc = hm_store_op_diffs(ds->stores[c], k, hs.data(), from.data(), hl.data(), &po, nullptr))) return rc;
+            if ((rc = hm_store_op_diffs_ex(ds->stores[c], k, hs.data(), from.data(), hl.data(), &po, index.data(), nullptr, opts))) return rc;
             for (uint32_t j = 0; j < k; j++) {
                 DocSt &d = ds->doc(docs[idx[j]]);
                 if (!d.ready) d.setup();
@@ -2295,7 +2299,11 @@ int hm_docset_materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs,
                     if (op.reg >= d.regs.size()) return hm_engine_fail(ds->e, HM_ERR_INVALID, "an op diff on an unknown register");
                     const uint8_t t = d.obj_type[op.obj] != NO_TYPE ? d.obj_type[op.obj] : (uint8_t)HM_MAKE_MAP;
                     if (r.kind == HM_OD_SET) w.map_set(t, op.obj, op.reg, surv.data() + r.surv_off, r.n_surv);
-                    else w.map_remove(t, op.obj, op.reg);
+                    else if (r.kind == HM_OD_REMOVE) w.map_remove(t, op.obj, op.reg);
+                    else if (r.kind == HM_OD_ELEM_INSERT) w.list_insert(t, op.obj, index[x], op.reg, surv.data() + r.surv_off, r.n_surv);
+                    else if (r.kind == HM_OD_ELEM_SET) w.list_set(t, op.obj, index[x], surv.data() + r.surv_off, r.n_surv);
+                    else if (r.kind == HM_OD_ELEM_REMOVE) w.list_remove(t, op.obj, index[x]);
+                    else return hm_engine_fail(ds->e, HM_ERR_INVALID, "an op diff of an unknown kind");
                 }
                 o += "]}}";
             }

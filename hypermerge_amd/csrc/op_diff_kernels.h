@@ -30,12 +30,33 @@
 // whether a later assign covers it and which incs it collects.  A wave's slice holds
 // hm_od_slice_words(ops, registers, objects) words of the largest document it meets; a document
 // that needs more sets HM_OD_BAD_WORK and gets empty ranges.
+//
+// opts & HM_ODF_LISTS: a document whose HM_DOC_HAS_LISTS hint is set has its element assigns answered
+// (HM_OD_ELEM_* rows, their index in out_index) instead of flagged; its slice is
+// hm_od_slice_words_lists.  The walk is a second pair of instantiations: with opts = 0 the kernels
+// are the ones they were.
 #define HM_OD_BAD_HANDLE 1u
 #define HM_OD_BAD_ROWS 2u
 #define HM_OD_BAD_WORK 4u
 
 __host__ __device__ inline unsigned long long hm_od_slice_words(unsigned long long n_ops, unsigned long long n_regs, unsigned long long n_objs) {
     return 3ull * n_ops + n_regs + n_objs;
+}
+
+// The slice of a document that carries HM_DOC_HAS_LISTS, in a call that answers element assigns
+// (HM_ODF_LISTS); term by term:
+//   3 ops + regs + objs   the chains, last[] and the object types, as above
+//   regs                  pos[]: an element register's place in the document's RGA order
+//   regs                  vis[]: is the element visible (does its register hold survivors) so far
+//   regs + 1              the Fenwick tree over pos (1-based): +1 per visible element; during the
+//                         order phase the same words map a register to its node
+//   regs                  a node's first child (order phase)
+//   objs                  per list / text object: the pos of its first element
+//   4 regs                the nodes being sorted: parent identity, ~elem, ~actor rank, register
+//   8 regs                the Euler tour's successor and weight per edge (2 per node), ping and pong
+// (a document has at most one applied ins per element register, so nodes <= regs)
+__host__ __device__ inline unsigned long long hm_od_slice_words_lists(unsigned long long n_ops, unsigned long long n_regs, unsigned long long n_objs) {
+    return 3ull * n_ops + 17ull * n_regs + 2ull * n_objs + 1ull;
 }
 
 // workgroups (one wave each) of a call whose largest document needs slice_words: as many as the
@@ -63,8 +84,16 @@ struct OpDiffArgs {
     hm_op_diff *out_rows;
     hm_surv_result *out_surv;
     uint32_t *out_range, *out_flags;           // [2n], [n]
+    // HM_ODF_* of the call; with HM_ODF_LISTS the fill writes out_index [cap_rows] beside out_rows
+    uint32_t opts;
+    uint32_t *out_index;
 };
-// the largest slice a request of the call needs, left in *out_words (device, zeroed by the caller)
+// the largest slice a request of the call needs, left in out_words[0]; out_words[1] = 1 when opts has
+// HM_ODF_LISTS and a requested document carries HM_DOC_HAS_LISTS (device, two words zeroed by the
+// caller).  A caller that finds it 0 may clear HM_ODF_LISTS in opts: no document would be answered
+// differently, the walk is then the instantiation without lists, and the fill launch sets out_index
+// (when given) to HM_NONE throughout, whatever the totals: only for a caller that launches the fill
+// once the totals fit, as the store does.
 hipError_t hm_launch_op_diff_need(const OpDiffArgs &a, unsigned long long *out_words, hipStream_t s);
 // count + scan (sum need not be zeroed; n == 0: sum is zeroed and nothing else is read or written)
 hipError_t hm_launch_op_diff_count(const OpDiffArgs &a, hipStream_t s);

@@ -18,8 +18,9 @@
 //              key(y) (every assign reverses the list once after appending)
 //
 //  od_need_kernel    a lane per request: the largest work slice a request's document needs
-//  od_walk_kernel    <false> count, <true> fill; one wavefront per request, a 64-lane workgroup of its
-//                    own; per tile of HM_OD_TILE history positions below `to`:
+//  od_walk_kernel    <FILL, LISTS>: FILL false = count, true = fill; LISTS = the call answers list / text
+//                    element assigns (HM_ODF_LISTS, further down); one wavefront per request, a 64-lane
+//                    workgroup of its own; per tile of HM_OD_TILE history positions below `to`:
 //    mark / rank / scatter / scan   as past_fill_kernel: the tile's applied changes in history order
 //             with their op rows' offsets (wave.h HistTile, wave_incl_scan)
 //    then 64 ops a step in application order, a lane per op:
@@ -53,7 +54,9 @@ __global__ __launch_bounds__(256) void od_need_kernel(OpDiffArgs A, unsigned lon
     if (q >= A.n) return;
     const DocRef s = doc_of(A.src, q);
     if (s.bad) return;
-    atomicMax(out_words, hm_od_slice_words(s.n_o, s.n_r, s.n_objs));
+    const bool lm = (A.opts & HM_ODF_LISTS) && (s.flags & HM_DOC_HAS_LISTS);
+    atomicMax(out_words, lm ? hm_od_slice_words_lists(s.n_o, s.n_r, s.n_objs) : hm_od_slice_words(s.n_o, s.n_r, s.n_objs));
+    if (lm) atomicOr(out_words + 1, 1ull);                     // (a document of the call has lists)
 }
 
 struct Lds {
@@ -136,7 +139,143 @@ __device__ uint32_t walk(const DocSource &D, const DocRef &s, const Slice &W, ui
     return n;
 }
 
-template <bool FILL>
+// ---- list / text elements (HM_ODF_LISTS) -------------------------------------------------------------
+// An element assign's diff carries the element's index at that moment: the visible elements of its
+// list that precede it in RGA order.  The order of the whole prefix serves every moment inside it
+// (two elements never change places), so per request the order phase ranks every element once:
+//   collect  the applied ins ops below `to` as nodes (parent identity, ~elem, ~actor rank, register);
+//            every _head child of every list hangs under one virtual root, keyed by its object, so
+//            the lists lie end to end in object order
+//   sort     a bitonic network over the slice, ascending: a run of one parent is its sibling list in
+//            (elem, actor rank) descending order
+//   tour     down / up edge per node over first child / next sibling / parent; ranked by pointer
+//            jumping (weight 1 on down edges, ping-pong arrays, ceil(log2(2 nodes)) rounds)
+//   pos[reg] = nodes - (down edges from the node's own to the end of the tour); a node whose tour
+//            does not end at the root (its chain does not reach _head) keeps HM_NONE
+// The walk then keeps a Fenwick tree over pos with +1 per visible element.
+#define OD_END_GOOD 0xFFFFFFFFu
+#define OD_END_BAD 0xFFFFFFFEu
+
+struct ListSlice {
+    uint32_t *pos, *vis;                       // per register
+    uint32_t *fen;                             // [regs + 1] the Fenwick tree; order phase: register -> node
+    uint32_t *fc;                              // per node: its first child (order phase)
+    uint32_t *ofirst;                          // per object: the pos of the list's first element
+    uint32_t *key;                             // [4 nodes]
+    uint32_t *nxt, *sum;                       // [2][2 nodes] each
+    uint32_t n;                                // nodes of the request
+};
+
+__device__ __forceinline__ uint32_t fen_prefix(const uint32_t *fen, uint32_t p) {   // visible elements at pos < p
+    uint32_t v = 0;
+    for (uint32_t i = p; i > 0u; i -= i & (0u - i)) v += fen[i];
+    return v;
+}
+__device__ __forceinline__ void fen_add(uint32_t *fen, uint32_t n, uint32_t p, uint32_t delta) {
+    for (uint32_t i = p + 1u; i <= n; i += i & (0u - i)) atomicAdd(&fen[i], delta);
+}
+
+__device__ __forceinline__ bool key_less(const uint32_t *a, const uint32_t *b) {
+    for (uint32_t w = 0; w < 3u; w++)
+        if (a[w] != b[w]) return a[w] < b[w];
+    return a[3] < b[3];
+}
+// the parent a node hangs under: every _head child (top bit clear) under the one virtual root
+__device__ __forceinline__ uint32_t parent_id(uint32_t w0) { return (w0 & 0x80000000u) ? w0 : 0u; }
+
+// returns the nodes; ok = false: an ins row that cannot be a merge's (a register, object or parent
+// outside the document, more applied ins ops than registers)
+__device__ uint32_t list_order(const DocSource &D, const DocRef &s, uint32_t lim, const ListSlice &X, uint32_t lane,
+                               uint32_t *ctr, bool &ok) {
+    if (lane == 0) *ctr = 0u;
+    for (uint32_t i = lane; i < s.n_r; i += 64u) { X.pos[i] = HM_NONE; X.vis[i] = 0u; X.fen[i] = HM_NONE; X.fc[i] = HM_NONE; }
+    for (uint32_t i = lane; i < s.n_objs; i += 64u) X.ofirst[i] = HM_NONE;
+    __syncthreads();
+    for (uint32_t i = lane; i < s.n_c; i += 64u) {             // collect
+        const int32_t hp = D.hist[s.c_off + i];
+        if (hp < 0 || (uint32_t)hp >= lim) continue;
+        const hm_change_row c = D.changes[s.c_off + i];
+        if (!c.n_ops) continue;
+        if (c.op_first < s.o_off || (unsigned long long)c.op_first + c.n_ops > (unsigned long long)s.o_off + s.n_o) continue;   // (the walk reports it)
+        for (uint32_t j = 0; j < c.n_ops; j++) {
+            const uint32_t *row = (const uint32_t *)(D.ops + c.op_first + j);
+            if ((row[4] & 0xFFu) != HM_INS) continue;
+            const uint32_t obj = row[0], reg = row[1], parent = row[2], elem = row[3];
+            if (reg >= s.n_r || obj >= s.n_objs || (parent != HM_HEAD && parent >= s.n_r)) { ok = false; continue; }
+            const uint32_t k = atomicAdd(ctr, 1u);
+            if (k >= s.n_r) { ok = false; continue; }
+            uint32_t *e = X.key + 4u * k;
+            e[0] = parent == HM_HEAD ? obj : (0x80000000u | parent); e[1] = ~elem; e[2] = 0xFFFFu - c.actor; e[3] = reg;
+        }
+    }
+    __syncthreads();
+    const uint32_t n = *ctr < s.n_r ? *ctr : s.n_r;
+    __syncthreads();
+    if (!n) return 0u;
+    for (uint32_t k = 2; (k >> 1) < n; k <<= 1)                // sort: every comparator ascending, rows past n count as +inf
+        for (uint32_t j = k >> 1; j > 0u; j >>= 1) {
+            const uint32_t m = j == (k >> 1) ? k - 1u : j;
+            for (uint32_t i = lane; i < n; i += 64u) {
+                const uint32_t l = i ^ m;
+                if (l <= i || l >= n) continue;
+                uint32_t a[4], b[4];
+                for (uint32_t w = 0; w < 4u; w++) { a[w] = X.key[4u * i + w]; b[w] = X.key[4u * l + w]; }
+                if (key_less(b, a))
+                    for (uint32_t w = 0; w < 4u; w++) { X.key[4u * i + w] = b[w]; X.key[4u * l + w] = a[w]; }
+            }
+            __syncthreads();
+        }
+    for (uint32_t i = lane; i < n; i += 64u) X.fen[X.key[4u * i + 3u]] = i;          // register -> node
+    __syncthreads();
+    for (uint32_t i = lane; i < n; i += 64u) {                 // a run's head is its parent's first child
+        const uint32_t w0 = X.key[4u * i];
+        if (!(w0 & 0x80000000u) || (i && X.key[4u * (i - 1u)] == w0)) continue;
+        const uint32_t pn = X.fen[w0 & 0x7FFFFFFFu];
+        if (pn != HM_NONE) X.fc[pn] = i;
+    }
+    __syncthreads();
+    const uint32_t e2 = 2u * n;
+    for (uint32_t i = lane; i < n; i += 64u) {                 // the tour
+        const uint32_t w0 = X.key[4u * i], c = X.fc[i];
+        const bool sib = i + 1u < n && parent_id(X.key[4u * (i + 1u)]) == parent_id(w0);
+        uint32_t up;
+        if (sib) up = 2u * (i + 1u);
+        else if (!(w0 & 0x80000000u)) up = OD_END_GOOD;
+        else {
+            const uint32_t pn = X.fen[w0 & 0x7FFFFFFFu];
+            up = pn != HM_NONE ? 2u * pn + 1u : OD_END_BAD;
+        }
+        X.nxt[2u * i] = c != HM_NONE ? 2u * c : 2u * i + 1u; X.sum[2u * i] = 1u;
+        X.nxt[2u * i + 1u] = up; X.sum[2u * i + 1u] = 0u;
+    }
+    __syncthreads();
+    uint32_t cur = 0;
+    for (uint32_t span = 1; span < e2; span <<= 1) {           // pointer jumping
+        const uint32_t *sn = X.nxt + cur * e2, *ss = X.sum + cur * e2;
+        uint32_t *dn = X.nxt + (cur ^ 1u) * e2, *dsum = X.sum + (cur ^ 1u) * e2;
+        for (uint32_t e = lane; e < e2; e += 64u) {
+            uint32_t t = sn[e], v = ss[e];
+            if (t < e2) { v += ss[t]; t = sn[t]; }
+            dn[e] = t; dsum[e] = v;
+        }
+        cur ^= 1u;
+        __syncthreads();
+    }
+    const uint32_t *fn = X.nxt + cur * e2, *fs = X.sum + cur * e2;
+    for (uint32_t i = lane; i < n; i += 64u) {
+        const uint32_t v = fs[2u * i];
+        if (fn[2u * i] != OD_END_GOOD || v == 0u || v > n) continue;
+        const uint32_t w0 = X.key[4u * i];
+        X.pos[X.key[4u * i + 3u]] = n - v;
+        if (!(w0 & 0x80000000u) && (i == 0u || X.key[4u * (i - 1u)] != w0)) X.ofirst[w0] = n - v;
+    }
+    __syncthreads();
+    for (uint32_t i = lane; i <= n; i += 64u) X.fen[i] = 0u;
+    __syncthreads();
+    return n;
+}
+
+template <bool FILL, bool LISTS>
 __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
     __shared__ Lds L;
     const uint32_t lane = threadIdx.x;
@@ -161,15 +300,23 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
             if (!cn.x) continue;
         }
         uint32_t bad = s.bad ? HM_OD_BAD_HANDLE : 0u;
-        if (hm_od_slice_words(s.n_o, s.n_r, s.n_objs) > A.slice_words) { bad |= HM_OD_BAD_WORK; s.n_c = 0; }
+        // element assigns are answered for a document that says it has lists; without the hint they are flagged
+        const bool lm = LISTS && (s.flags & HM_DOC_HAS_LISTS);
+        if ((lm ? hm_od_slice_words_lists(s.n_o, s.n_r, s.n_objs) : hm_od_slice_words(s.n_o, s.n_r, s.n_objs)) > A.slice_words) { bad |= HM_OD_BAD_WORK; s.n_c = 0; }
         Slice W;
         W.prev = wbase; W.next = W.prev + s.n_o; W.chg = W.next + s.n_o; W.last = W.chg + s.n_o; W.otype = W.last + s.n_r;
+        ListSlice X = {};
+        if (LISTS) {
+            X.pos = W.otype + s.n_objs; X.vis = X.pos + s.n_r; X.fen = X.vis + s.n_r; X.fc = X.fen + s.n_r + 1u;
+            X.ofirst = X.fc + s.n_r; X.key = X.ofirst + s.n_objs; X.nxt = X.key + 4u * (size_t)s.n_r; X.sum = X.nxt + 4u * (size_t)s.n_r;
+        }
         const uint32_t lim = to < s.n_c ? to : s.n_c;          // history positions of interest lie below it
         uint32_t rows = 0, surv = 0;                           // emitted so far
         bool lists = false, rows_ok = true;
         if (from < lim) {
             for (uint32_t i = lane; i < s.n_r; i += 64u) W.last[i] = HM_NONE;
             for (uint32_t i = lane; i < s.n_objs; i += 64u) W.otype[i] = 0u;
+            if (LISTS && lm) X.n = list_order(D, s, lim, X, lane, &L.src[0], rows_ok);
         }
         const uint32_t n_tiles = from < lim ? (lim + OTILE - 1u) / OTILE : 0u;
         for (uint32_t t = 0; t < n_tiles; t++) {
@@ -225,11 +372,12 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
                 const uint32_t ot = assign && obj < s.n_objs ? W.otype[obj] : 0u;
                 const bool list = ot == 1u + HM_MAKE_LIST || ot == 1u + HM_MAKE_TEXT;
                 const bool in_range = valid && p >= from;
-                lists |= in_range && list;
-                const bool chain = assign && !list && reg != HM_NONE && reg < s.n_r;
+                lists |= in_range && list && !(LISTS && lm);
+                const bool chain = assign && (!list || (LISTS && lm)) && reg != HM_NONE && reg < s.n_r;
+                const bool el = LISTS && chain && list;         // an element assign that is answered
                 const unsigned long long cm = __ballot(chain);
+                uint32_t pl = HM_NONE, nl = HM_NONE;           // nearest lanes below / above with the same register
                 if (cm) {                                       // link (uniform branch)
-                    uint32_t pl = HM_NONE, nl = HM_NONE;       // nearest lanes below / above with the same register
                     for (uint32_t j = 0; j < 64u; j++) {
                         if (!((cm >> j) & 1ull)) continue;
                         const uint32_t rj = __shfl(reg, j);
@@ -248,12 +396,37 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
                     if (chain && nl == HM_NONE) W.last[reg] = dop;
                     __syncthreads();
                 }
-                const bool emit = in_range && (make || chain);  // emit
+                uint32_t ns = 0, idx = HM_NONE;
+                bool was = false, now = false;                   // the element's visibility before and after the op
+                if (LISTS) {                                    // index
+                    uint32_t pe = HM_NONE, lo = 0;
+                    if (el) { pe = X.pos[reg]; lo = X.ofirst[obj]; }
+                    const bool elv = el && pe != HM_NONE && lo != HM_NONE;
+                    if (el && !elv) rows_ok = false;            // (no applied ins made this element: not a merge's tables)
+                    if (__ballot(elv)) {                        // (uniform branch)
+                        if (elv) { ns = walk(D, s, W, dop, nullptr, 0u); now = ns != 0u; }
+                        const uint32_t now_pl = __shfl((uint32_t)now, pl == HM_NONE ? lane : pl);
+                        if (elv) was = pl != HM_NONE ? now_pl != 0u : X.vis[reg] != 0u;
+                        const uint32_t delta = (uint32_t)now - (uint32_t)was;
+                        if (elv) idx = fen_prefix(X.fen, pe) - fen_prefix(X.fen, lo);   // as of the step's start
+                        const unsigned long long tm = __ballot(elv && delta != 0u);
+                        for (uint32_t j = 0; j < 64u; j++) {    // the earlier lanes of the step
+                            if (!((tm >> j) & 1ull)) continue;
+                            const uint32_t pj = __shfl(pe, j), dj = __shfl(delta, j);
+                            if (elv && j < lane && pj >= lo && pj < pe) idx += dj;
+                        }
+                        __syncthreads();                        // (the tree is read before it is updated)
+                        if (elv && delta != 0u) fen_add(X.fen, X.n, pe, delta);
+                        if (elv && nl == HM_NONE) X.vis[reg] = (uint32_t)now;
+                        __syncthreads();
+                    }
+                }
+                const bool emit = in_range && (make || (chain && (!el || was || now)));  // emit
                 const unsigned long long em = __ballot(emit);
                 if (!em) continue;
                 const uint32_t row = rows + (uint32_t)__popcll(em & ((1ull << lane) - 1ull));
-                uint32_t ns = 0;
-                if (emit && chain && !(FILL && fl)) ns = walk(D, s, W, dop, nullptr, 0u);
+                if (emit && chain && !el && !(FILL && fl)) ns = walk(D, s, W, dop, nullptr, 0u);
+                if (LISTS && !emit) ns = 0u;                    // (an element assign outside the range was walked for its visibility)
                 const uint32_t is = wave_incl_scan(ns, lane);
                 if (FILL && emit && !fl) {
                     const uint32_t so = surv + is - ns;
@@ -261,7 +434,9 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
                         if (ns) walk(D, s, W, dop, A.out_surv + of.y + so, ns);
                         hm_op_diff r;
                         r.op = dop; r.kind = make ? HM_OD_CREATE : (ns ? HM_OD_SET : HM_OD_REMOVE); r.n_surv = ns; r.surv_off = of.y + so;
+                        if (LISTS && el) r.kind = was ? (now ? HM_OD_ELEM_SET : HM_OD_ELEM_REMOVE) : HM_OD_ELEM_INSERT;
                         A.out_rows[of.x + row] = r;
+                        if (LISTS) A.out_index[of.x + row] = idx;
                     }
                 }
                 rows += (uint32_t)__popcll(em); surv += __shfl(is, 63);
@@ -297,13 +472,19 @@ hipError_t hm_launch_op_diff_need(const OpDiffArgs &a, unsigned long long *out_w
 hipError_t hm_launch_op_diff_count(const OpDiffArgs &a, hipStream_t s) {
     hipError_t r = hipMemsetAsync(a.sum, 0, sizeof(hm_op_diff_summary), s);
     if (r != hipSuccess || !a.n) return r;                     // (no request: the zero summary is the answer)
-    hipLaunchKernelGGL(hmo::od_walk_kernel<false>, dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+    if (a.opts & HM_ODF_LISTS) hipLaunchKernelGGL((hmo::od_walk_kernel<false, true>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+    else hipLaunchKernelGGL((hmo::od_walk_kernel<false, false>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
     if ((r = hipGetLastError()) != hipSuccess) return r;
     return hm_launch_past_scan(scan_args(a), s);
 }
 
 hipError_t hm_launch_op_diff_fill(const OpDiffArgs &a, hipStream_t s) {
     if (!a.n) return hipSuccess;
-    hipLaunchKernelGGL(hmo::od_walk_kernel<true>, dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+    if (a.opts & HM_ODF_LISTS) hipLaunchKernelGGL((hmo::od_walk_kernel<true, true>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+    else if (a.out_index && a.cap_rows) {                      // (no document of the call has lists: no row has an index)
+        const hipError_t r = hipMemsetAsync(a.out_index, 0xFF, (size_t)a.cap_rows * 4, s);
+        if (r != hipSuccess) return r;
+        hipLaunchKernelGGL((hmo::od_walk_kernel<true, false>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+    } else hipLaunchKernelGGL((hmo::od_walk_kernel<true, false>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
     return hipGetLastError();
 }

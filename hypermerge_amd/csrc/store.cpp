@@ -1293,7 +1293,7 @@ int hm_store_materialize_sized(hm_store *s, uint32_t n, const uint32_t *doc_hand
 // offsets and summary stay there (A.cnt / A.off / A.aux / A.sum), the chains' work memory is the
 // head of s->past; *sum = the summary, read back.
 static int op_diff_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
-                         OpDiffArgs &A, hm_op_diff_summary *sum) {
+                         uint32_t opts, OpDiffArgs &A, hm_op_diff_summary *sum) {
     hipStream_t st = hm_engine_stream(s->e);
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_sum = 0, o_need = 128, o_h = 256, o_from = o_h + al(4 * (size_t)n), o_to = o_from + al(4 * (size_t)n),
@@ -1305,19 +1305,23 @@ static int op_diff_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, c
     SCHK(s, hipMemcpyAsync(sp + o_h, doc_handles, 4 * (size_t)n, hipMemcpyHostToDevice, st));
     SCHK(s, hipMemcpyAsync(sp + o_from, from, 4 * (size_t)n, hipMemcpyHostToDevice, st));
     SCHK(s, hipMemcpyAsync(sp + o_to, to, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-    SCHK(s, hipMemsetAsync(sp + o_need, 0, 8, st));
+    SCHK(s, hipMemsetAsync(sp + o_need, 0, 16, st));
     A = OpDiffArgs{};
     A.n = n; A.src = store_source(s); A.src.handles = (const uint32_t *)(sp + o_h);
+    A.opts = opts;
     A.from = (const uint32_t *)(sp + o_from); A.to = (const uint32_t *)(sp + o_to);
     A.cnt = (uint32_t *)(sp + o_cnt); A.off = (uint32_t *)(sp + o_off); A.aux = (uint32_t *)(sp + o_aux);
     A.part = (unsigned long long *)(sp + o_part);
     A.sum = (hm_op_diff_summary *)(sp + o_sum);
-    // the largest document of the call sizes a wave's slice of the work memory
+    // the largest document of the call sizes a wave's slice of the work memory (HM_ODF_LISTS: a
+    // document with lists by hm_od_slice_words_lists)
     SCHK(s, hm_launch_op_diff_need(A, (unsigned long long *)(sp + o_need), st));
-    SCHK(s, hipMemcpyAsync(&s->h_cnt[10], sp + o_need, 8, hipMemcpyDeviceToHost, st));
+    SCHK(s, hipMemcpyAsync(&s->h_cnt[10], sp + o_need, 16, hipMemcpyDeviceToHost, st));
     SCHK(s, hipStreamSynchronize(st));
-    unsigned long long need;
+    unsigned long long need, any_lists;
     memcpy(&need, &s->h_cnt[10], 8);
+    memcpy(&any_lists, &s->h_cnt[12], 8);
+    if (!any_lists) A.opts &= ~HM_ODF_LISTS;                   // (no requested document has lists: the walk without them)
     A.slice_words = need ? need : 1;
     A.waves = hm_od_waves(n, A.slice_words);
     if ((rc = ensure_buf(s, s->past, al((size_t)A.waves * A.slice_words * 4)))) return rc;
@@ -1336,14 +1340,19 @@ extern "C" {
 
 int hm_store_op_diff_sizes(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
                            uint32_t *out_counts, uint32_t *out_flags, uint64_t *out_totals) {
-    if (!s || (n && (!doc_handles || !from || !to))) return HM_ERR_INVALID;
+    return hm_store_op_diff_sizes_ex(s, n, doc_handles, from, to, out_counts, out_flags, out_totals, 0u);
+}
+
+int hm_store_op_diff_sizes_ex(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                              uint32_t *out_counts, uint32_t *out_flags, uint64_t *out_totals, uint32_t opts) {
+    if (!s || (n && (!doc_handles || !from || !to)) || (opts & ~HM_ODF_LISTS)) return HM_ERR_INVALID;
     if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
     try {
         if (out_totals) out_totals[0] = out_totals[1] = 0;
         if (!n) return HM_OK;
         OpDiffArgs A;
         hm_op_diff_summary sum;
-        int rc = op_diff_count(s, n, doc_handles, from, to, A, &sum);
+        int rc = op_diff_count(s, n, doc_handles, from, to, opts, A, &sum);
         if (rc) return rc;
         if (out_totals) { out_totals[0] = sum.totals[0]; out_totals[1] = sum.totals[1]; }
         if (out_counts || out_flags) {
@@ -1365,8 +1374,15 @@ int hm_store_op_diff_sizes(hm_store *s, uint32_t n, const uint32_t *doc_handles,
 
 int hm_store_op_diffs(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
                       const hm_op_diff_out *out, uint64_t *out_totals) {
-    if (!s || !out || (n && (!doc_handles || !from || !to || !out->range || !out->flags))) return HM_ERR_INVALID;
+    return hm_store_op_diffs_ex(s, n, doc_handles, from, to, out, nullptr, out_totals, 0u);
+}
+
+int hm_store_op_diffs_ex(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                         const hm_op_diff_out *out, uint32_t *out_index, uint64_t *out_totals, uint32_t opts) {
+    if (!s || !out || (n && (!doc_handles || !from || !to || !out->range || !out->flags)) || (opts & ~HM_ODF_LISTS)) return HM_ERR_INVALID;
     if ((out->cap_rows && !out->rows) || (out->cap_surv && !out->surv)) return HM_ERR_INVALID;
+    const bool want_index = (opts & HM_ODF_LISTS) != 0u;
+    if (want_index && out->cap_rows && !out_index) return HM_ERR_INVALID;
     if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
     try {
         if (out_totals) out_totals[0] = out_totals[1] = 0;
@@ -1374,26 +1390,26 @@ int hm_store_op_diffs(hm_store *s, uint32_t n, const uint32_t *doc_handles, cons
         hipStream_t st = hm_engine_stream(s->e);
         OpDiffArgs A;
         hm_op_diff_summary sum;
-        int rc = op_diff_count(s, n, doc_handles, from, to, A, &sum);
+        int rc = op_diff_count(s, n, doc_handles, from, to, opts, A, &sum);
         if (rc) return rc;
         const uint64_t tr = sum.totals[0], ts = sum.totals[1];
         if (out_totals) { out_totals[0] = tr; out_totals[1] = ts; }
         if (tr > out->cap_rows || ts > out->cap_surv)
             return hm_engine_fail(s->e, HM_ERR_NOMEM, "a capacity below the rows of the op diffs");
         auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        // [work][rows][survivors][ranges][flags]
-        const size_t sz[4] = {tr * sizeof(hm_op_diff), ts * sizeof(hm_surv_result), 8 * (size_t)n, 4 * (size_t)n};
-        size_t o[4], total = al((size_t)A.waves * A.slice_words * 4);
-        for (int i = 0; i < 4; i++) { o[i] = total; total += al(sz[i] + 1); }
+        // [work][rows][survivors][ranges][flags][index]
+        const size_t sz[5] = {tr * sizeof(hm_op_diff), ts * sizeof(hm_surv_result), 8 * (size_t)n, 4 * (size_t)n, want_index ? 4 * (size_t)tr : 0};
+        size_t o[5], total = al((size_t)A.waves * A.slice_words * 4);
+        for (int i = 0; i < 5; i++) { o[i] = total; total += al(sz[i] + 1); }
         if ((rc = ensure_buf(s, s->past, total))) return rc;
         uint8_t *bp = s->past.p;
         A.work = (uint32_t *)bp;
         A.cap_rows = (uint32_t)tr; A.cap_surv = (uint32_t)ts;
         A.out_rows = (hm_op_diff *)(bp + o[0]); A.out_surv = (hm_surv_result *)(bp + o[1]);
-        A.out_range = (uint32_t *)(bp + o[2]); A.out_flags = (uint32_t *)(bp + o[3]);
+        A.out_range = (uint32_t *)(bp + o[2]); A.out_flags = (uint32_t *)(bp + o[3]); A.out_index = want_index ? (uint32_t *)(bp + o[4]) : nullptr;
         SCHK(s, hm_launch_op_diff_fill(A, st));
-        void *dst[4] = {out->rows, out->surv, out->range, out->flags};
-        for (int i = 0; i < 4; i++)
+        void *dst[5] = {out->rows, out->surv, out->range, out->flags, out_index};
+        for (int i = 0; i < 5; i++)
             if (sz[i]) SCHK(s, hipMemcpyAsync(dst[i], bp + o[i], sz[i], hipMemcpyDeviceToHost, st));
         SCHK(s, hipStreamSynchronize(st));
         return HM_OK;

@@ -192,19 +192,21 @@ class DocSet:
         s, _ = _text(self._L, t)
         return json.loads(s)
 
-    def materialize_patch(self, docs: Sequence[int], history: Sequence[int]) -> List[Dict[str, Any]]:
+    def materialize_patch(self, docs: Sequence[int], history: Sequence[int], lists: bool = False) -> List[Dict[str, Any]]:
         """The patches of documents as they were (RepoBackend's MaterializeMsg reply, many per call):
         docs[i] at history length history[i].  Per request {"doc", "history", "patch"}: the patch is
         Backend.applyChanges(Backend.init(), history.slice(0, n))'s {clock, deps, canUndo, canRedo, diffs}
         with the per-op diffs read off the resident tables on the device; a prefix that assigns list
         / text elements has "patch": None and "host": True and is replayed by the caller
-        (hm_docset_materialize_patch)."""
+        (hm_docset_materialize_patch).  lists=True (hm_docset_materialize_patch_ex with HM_ODF_LISTS):
+        the element diffs (insert / set / remove at the index of that moment) come from the device too,
+        and no document fed through this package has "patch": None."""
         ids = np.ascontiguousarray(docs, np.uint32)
         hl = np.ascontiguousarray(np.minimum(np.asarray(history, np.int64), 0xFFFFFFFF), np.uint32)
         assert len(hl) == len(ids)
         t = ctypes.c_void_p()
-        self.engine._check(self._L.hm_docset_materialize_patch(self._h, len(ids), ids.ctypes.data if len(ids) else None,
-                                                               hl.ctypes.data if len(ids) else None, ctypes.byref(t)),
+        self.engine._check(self._L.hm_docset_materialize_patch_ex(self._h, len(ids), ids.ctypes.data if len(ids) else None,
+                                                                  hl.ctypes.data if len(ids) else None, 1 if lists else 0, ctypes.byref(t)),
                            "hm_docset_materialize_patch")
         s, _ = _text(self._L, t)
         return json.loads(s)

@@ -41,7 +41,9 @@ EXPORTS = ("hm_abi_version", "hm_status_message", "hm_engine_create", "hm_engine
            "hm_missing_changes_device", "hm_missing_changes_host", "hm_docset_missing_changes",
            "hm_store_past_sizes", "hm_store_materialize", "hm_materialize_work_bytes", "hm_materialize_device",
            "hm_docset_materialize", "hm_store_op_diff_sizes", "hm_store_op_diffs", "hm_op_diffs_work_bytes",
-           "hm_op_diffs_device", "hm_op_diffs_host", "hm_docset_materialize_patch")
+           "hm_op_diffs_device", "hm_op_diffs_host", "hm_docset_materialize_patch",
+           "hm_store_op_diff_sizes_ex", "hm_store_op_diffs_ex", "hm_op_diffs_work_bytes_ex", "hm_op_diffs_device_ex",
+           "hm_op_diffs_host_ex", "hm_docset_materialize_patch_ex")
 
 _lib = None
 
@@ -137,6 +139,12 @@ def lib():
             "hm_op_diffs_work_bytes": [ctypes.POINTER(CBatch), u32],
             "hm_op_diffs_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, vp],
             "hm_op_diffs_host": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp],
+            "hm_docset_materialize_patch_ex": [vp, u32, vp, vp, u32, vp],
+            "hm_store_op_diff_sizes_ex": [vp, u32, vp, vp, vp, vp, vp, vp, u32],
+            "hm_store_op_diffs_ex": [vp, u32, vp, vp, vp, vp, vp, vp, u32],
+            "hm_op_diffs_work_bytes_ex": [ctypes.POINTER(CBatch), u32, u32],
+            "hm_op_diffs_device_ex": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, vp, vp, u32],
+            "hm_op_diffs_host_ex": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, u32],
         }
         for f, a in sig.items():
             getattr(L, f).argtypes = a
@@ -153,6 +161,7 @@ def lib():
         L.hm_clock_records_scratch_bytes.restype = ctypes.c_size_t
         L.hm_materialize_work_bytes.restype = ctypes.c_size_t
         L.hm_op_diffs_work_bytes.restype = ctypes.c_size_t
+        L.hm_op_diffs_work_bytes_ex.restype = ctypes.c_size_t
         L.hm_docset_destroy.restype = None
         L.hm_docset_engine.restype = ctypes.c_void_p
         L.hm_text_data.restype = ctypes.c_void_p
@@ -184,6 +193,8 @@ assert ctypes.sizeof(CPastSummary) == 64
 
 OD_CREATE, OD_SET, OD_REMOVE = 0, 1, 2   # HM_OD_* row kinds
 OD_LISTS = 1                              # HM_OD_LISTS request flag
+OD_ELEM_INSERT, OD_ELEM_SET, OD_ELEM_REMOVE = 3, 4, 5   # HM_OD_ELEM_* row kinds (ODF_LISTS)
+ODF_LISTS = 1                             # HM_ODF_LISTS option: answer list / text element assigns
 OP_DIFF_DT = np.dtype([("op", "<u4"), ("kind", "<u4"), ("n_surv", "<u4"), ("surv_off", "<u4")])
 
 
@@ -338,14 +349,17 @@ class Engine:
                                                   p(hist_len), p(clock_rows), ctypes.byref(out), p(out_summary), p(work),
                                                   p(stream)), "hm_materialize_device")
 
-    def op_diffs_host(self, batch: Batch, results: Results, docs, frm, to, cap=None):
+    def op_diffs_host(self, batch: Batch, results: Results, docs, frm, to, cap=None, lists=False):
         """hm_op_diffs_host: what each applied op of the history slices [frm[i], to[i]) of documents
         docs[i] of a merged batch did (None: every document, one request each).  Returns (rows
         OP_DIFF_DT, survivors SURV_RESULT_DT, ranges [n, 2] = first row and rows per request, flags [n]);
         a request flagged OD_LISTS has no rows.  cap = (rows, survivors) the tables hold (None: every
         op of the batch per request, which no slice exceeds in rows; survivors are sized by a first
-        call's totals when that is too small)."""
+        call's totals when that is too small).  lists=True (hm_op_diffs_host_ex with ODF_LISTS): list /
+        text element assigns are answered as OD_ELEM_* rows and the rows' index table ([rows] u32, NONE
+        where a row has none) is returned as a fifth element."""
         from .columnar import SURV_RESULT_DT
+        opts = ODF_LISTS if lists else 0
         idx = None if docs is None else np.ascontiguousarray(docs, np.uint32)
         n = batch.n_docs if idx is None else len(idx)
         f, t = np.ascontiguousarray(frm, np.uint32), np.ascontiguousarray(to, np.uint32)
@@ -356,27 +370,33 @@ class Engine:
         for _ in range(2):
             rows, surv = np.zeros(max(caps[0], 1), OP_DIFF_DT), np.zeros(max(caps[1], 1), SURV_RESULT_DT)
             rng, fl = np.zeros((max(n, 1), 2), np.uint32), np.zeros(max(n, 1), np.uint32)
+            index = np.zeros(max(caps[0], 1), np.uint32)
             out = COpDiffOut(caps[0], caps[1], rows.ctypes.data, surv.ctypes.data, rng.ctypes.data, fl.ctypes.data)
-            st = self._L.hm_op_diffs_host(self._h, ctypes.byref(cb), ctypes.byref(cr), n,
-                                          idx.ctypes.data if idx is not None and n else None,
-                                          f.ctypes.data if n else None, t.ctypes.data if n else None, ctypes.byref(out), tot)
+            st = self._L.hm_op_diffs_host_ex(self._h, ctypes.byref(cb), ctypes.byref(cr), n,
+                                             idx.ctypes.data if idx is not None and n else None,
+                                             f.ctypes.data if n else None, t.ctypes.data if n else None, ctypes.byref(out),
+                                             index.ctypes.data if lists else None, tot, opts)
             if st == 34 and cap is None and (tot[0] > caps[0] or tot[1] > caps[1]):   # HM_ERR_NOMEM: sized by the totals
                 caps = (int(tot[0]), int(tot[1]))
                 continue
             break
         self._check(st, "hm_op_diffs_host")
-        return rows[:int(tot[0])], surv[:int(tot[1])], rng[:n], fl[:n]
+        base = (rows[:int(tot[0])], surv[:int(tot[1])], rng[:n], fl[:n])
+        return base + (index[:int(tot[0])],) if lists else base
 
-    def op_diffs_work_bytes(self, cbatch: CBatch, n: int) -> int:
-        return int(self._L.hm_op_diffs_work_bytes(ctypes.byref(cbatch), n))
+    def op_diffs_work_bytes(self, cbatch: CBatch, n: int, lists=False) -> int:
+        return int(self._L.hm_op_diffs_work_bytes_ex(ctypes.byref(cbatch), n, ODF_LISTS if lists else 0))
 
     def op_diffs_device(self, cbatch: CBatch, cresults: CResults, n: int, doc_index: int, frm: int, to: int,
-                        out: "COpDiffOut", out_summary: int, work: int, stream: int = 0) -> None:
+                        out: "COpDiffOut", out_summary: int, work: int, stream: int = 0, lists=False, out_index: int = 0) -> None:
         """hm_op_diffs_device: the same with every table in device memory (pointers; `out` a COpDiffOut of
-        device tables, `work` of op_diffs_work_bytes(cbatch, n) bytes; enqueued, not synchronised)."""
+        device tables, `work` of op_diffs_work_bytes(cbatch, n) bytes; enqueued, not synchronised).
+        lists=True (hm_op_diffs_device_ex with ODF_LISTS): out_index = the device table of out.cap_rows
+        u32 the rows' indexes go to, `work` of op_diffs_work_bytes(cbatch, n, lists=True) bytes."""
         p = lambda x: ctypes.c_void_p(x) if x else None
-        self._check(self._L.hm_op_diffs_device(self._h, ctypes.byref(cbatch), ctypes.byref(cresults), n, p(doc_index),
-                                               p(frm), p(to), ctypes.byref(out), p(out_summary), p(work), p(stream)),
+        self._check(self._L.hm_op_diffs_device_ex(self._h, ctypes.byref(cbatch), ctypes.byref(cresults), n, p(doc_index),
+                                                  p(frm), p(to), ctypes.byref(out), p(out_index), p(out_summary), p(work),
+                                                  p(stream), ODF_LISTS if lists else 0),
                     "hm_op_diffs_device")
 
     def small_occupancy(self, batch: Batch) -> Sequence[int]:

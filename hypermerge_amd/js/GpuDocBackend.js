@@ -573,8 +573,11 @@ class GpuEngine {
   // returns ({clock, deps, canUndo: false, canRedo: false, diffs}), its per-op diffs read off the
   // resident tables on the device.  A prefix that assigns list / text elements comes back with
   // patch: null (an element's diff needs its index at that moment): the caller replays that one on
-  // the host.  Reflects the rounds already applied: in 'async' mode await idle() first.
-  materializePatch(reqs) {
+  // the host.  With { lists: true } the element diffs (insert / set / remove at the index of that
+  // moment) come from the device as well and no document applied through this engine gets patch:
+  // null.  Reflects the rounds already applied: in 'async' mode await idle() first.
+  materializePatch(reqs, opts) {
+    const lists = !!(opts && opts.lists)
     const states = reqs.map((r) => r.state || this.stateOf(r.id))
     const out = new Array(reqs.length)
     this.docsets.forEach((ds, k) => {
@@ -582,7 +585,8 @@ class GpuEngine {
       states.forEach((st, i) => { if (st.shard === k) at.push(i) })
       if (!at.length) return
       const hl = Uint32Array.from(at.map((i) => Math.min(Math.max(Math.floor(Number(reqs[i].history) || 0), 0), 0xffffffff)))
-      const got = JSON.parse(addon.docsetMaterializePatch(ds, Uint32Array.from(at.map((i) => states[i].id)), hl))
+      const ids = Uint32Array.from(at.map((i) => states[i].id))
+      const got = JSON.parse(lists ? addon.docsetMaterializePatchEx(ds, ids, hl, 1) : addon.docsetMaterializePatch(ds, ids, hl))
       at.forEach((i, j) => { out[i] = { history: got[j].history, patch: got[j].patch } })
     })
     return out
@@ -1051,8 +1055,9 @@ class DocBackend {
   // the patch-shaped MaterializeMsg reply: {history, patch} with the patch that
   // Backend.applyChanges(Backend.init(), history.slice(0, n)) returns, its diffs computed on the
   // device from the resident log.  patch is null when the prefix assigns list / text elements:
-  // that prefix is replayed on the host (INTEGRATION.md).  undefined before init.
-  materializePatchAt(n) { return this.back ? this.engine.materializePatch([{ state: this.back, history: n }])[0] : undefined }
+  // that prefix is replayed on the host (INTEGRATION.md), unless { lists: true } asks the device
+  // for the element diffs too.  undefined before init.
+  materializePatchAt(n, opts) { return this.back ? this.engine.materializePatch([{ state: this.back, history: n }], opts)[0] : undefined }
 
   // changes: Change objects (the reference's), or raw hypercore blocks / JSON texts of them
   applyRemoteChanges(changes) { this.remoteChangesQ.push(changes) }

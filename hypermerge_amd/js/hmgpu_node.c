@@ -1044,9 +1044,10 @@ static napi_value DocsetMaterialize(napi_env env, napi_callback_info info) {
  * {"doc", "history", "patch"}: the patch of the document as it was at that history length (clock, deps,
  * per-op diffs from the device), or "patch": null with "host": true when the prefix assigns list /
  * text elements (refused while a call on the docset is in flight) */
-static napi_value DocsetMaterializePatch(napi_env env, napi_callback_info info) {
-    napi_value argv[3];
-    if (!get_args(env, info, 3, argv)) return NULL;
+static napi_value materialize_patch(napi_env env, napi_callback_info info, int ex) {
+    napi_value argv[4];
+    if (!get_args(env, info, ex ? 4 : 3, argv)) return NULL;
+    const uint32_t opts = ex ? get_u32(env, argv[3]) : 0u;
     Docset *d = get_docset(env, argv[0]);
     if (!d) return NULL;
     void *p[2]; size_t len[2];
@@ -1055,7 +1056,7 @@ static napi_value DocsetMaterializePatch(napi_env env, napi_callback_info info) 
     const uint32_t n = (uint32_t)(len[0] / 4);
     if (len[1] / 4 != n || (n && (!p[0] || !p[1]))) { napi_throw_type_error(env, NULL, "docsetMaterializePatch: one history length per document"); return NULL; }
     hm_text *t = NULL;
-    int st = hm_docset_materialize_patch(d->ds, n, (const uint32_t *)p[0], (const uint32_t *)p[1], &t);
+    int st = hm_docset_materialize_patch_ex(d->ds, n, (const uint32_t *)p[0], (const uint32_t *)p[1], opts, &t);
     if (st) return throw_status(env, d->engine, st, "hm_docset_materialize_patch");
     size_t tl = 0;
     const char *s = hm_text_data(t, &tl);
@@ -1064,6 +1065,11 @@ static napi_value DocsetMaterializePatch(napi_env env, napi_callback_info info) 
     hm_text_free(t);
     return js;
 }
+static napi_value DocsetMaterializePatch(napi_env env, napi_callback_info info) { return materialize_patch(env, info, 0); }
+/* docsetMaterializePatchEx(docset, ids, histLen, opts): the same with hm_docset_materialize_patch_ex's
+ * option word; 1 (HM_ODF_LISTS) = list / text element diffs come from the device too, so "patch": null
+ * is left to a document that assigns list elements without its lists hint */
+static napi_value DocsetMaterializePatchEx(napi_env env, napi_callback_info info) { return materialize_patch(env, info, 1); }
 
 /* docsetInfo(docset, doc) ->{aStride, nChanges, nOps, nActors, nObjs, nRegs, histLen, nQueued} */
 static napi_value DocsetInfo(napi_env env, napi_callback_info info) {
@@ -1326,7 +1332,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"docsetCreate", DocsetCreate}, {"docsetOpen", DocsetOpen}, {"docsetApply", DocsetApply}, {"docsetApplyPacked", DocsetApplyPacked},
         {"docsetHistoryPrefix", DocsetHistoryPrefix}, {"docsetClockUpdate", DocsetClockUpdate},
         {"docsetView", DocsetView}, {"docsetBlocked", DocsetBlocked}, {"docsetWaiting", DocsetWaiting},
-        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetMaterialize", DocsetMaterialize}, {"docsetMaterializePatch", DocsetMaterializePatch}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
+        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetMaterialize", DocsetMaterialize}, {"docsetMaterializePatch", DocsetMaterializePatch}, {"docsetMaterializePatchEx", DocsetMaterializePatchEx}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
         {"cursorsCreate", CursorsCreate}, {"cursorsReserve", CursorsReserve}, {"cursorsUpdate", CursorsUpdate},
         {"cursorsGet", CursorsGet}, {"cursorsEntry", CursorsEntry}, {"cursorsDocsWithActors", CursorsDocsWithActors},
         {"syncRanges", SyncRanges}, {"decodeBlocks", DecodeBlocks}, {"commCreateLocalDocsets", CommCreateLocalDocsets},

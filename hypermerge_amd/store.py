@@ -527,36 +527,43 @@ class DocStore:
                     "hm_store_materialize")
         return b, r, clog, olog
 
-    def op_diff_sizes(self, handles, frm, to) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """hm_store_op_diff_sizes: ([n, 2] diff rows / survivor rows per request, flags [n], their [2] totals)."""
+    def op_diff_sizes(self, handles, frm, to, lists=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """hm_store_op_diff_sizes: ([n, 2] diff rows / survivor rows per request, flags [n], their [2] totals).
+        lists=True: the sizes of op_diffs(..., lists=True)."""
         hs, f, t = (np.ascontiguousarray(x, np.uint32) for x in (handles, frm, to))
         n = len(hs)
         assert len(f) == n and len(t) == n
         cnt, fl, tot = np.zeros((max(n, 1), 2), np.uint32), np.zeros(max(n, 1), np.uint32), np.zeros(2, np.uint64)
-        self._check(self._L.hm_store_op_diff_sizes(self._h, n, _p(hs), _p(f), _p(t), _p(cnt), _p(fl), _p(tot)),
+        self._check(self._L.hm_store_op_diff_sizes_ex(self._h, n, _p(hs), _p(f), _p(t), _p(cnt), _p(fl), _p(tot), 1 if lists else 0),
                     "hm_store_op_diff_sizes")
         return cnt[:n], fl[:n], tot
 
-    def op_diffs(self, handles, frm, to, cap=None):
+    def op_diffs(self, handles, frm, to, cap=None, lists=False):
         """hm_store_op_diffs: what each applied op of the history slices [frm[i], to[i]) of the documents
         `handles` (a handle may repeat) did: per make op a create row, per assign on a map / table
         register the register as it stands after that op.  Returns (rows OP_DIFF_DT, survivors
         SURV_RESULT_DT, ranges [n, 2] = first row and rows per request, flags [n]); a request flagged
         OD_LISTS (its range assigns list / text elements) has no rows and is replayed on the host.
-        cap = (rows, survivors) the tables hold; None: the sizes are asked first."""
+        cap = (rows, survivors) the tables hold; None: the sizes are asked first.
+        lists=True (hm_store_op_diffs_ex with HM_ODF_LISTS): list / text element assigns are answered
+        as OD_ELEM_INSERT / OD_ELEM_SET / OD_ELEM_REMOVE rows, nothing is flagged, and the rows' index
+        table ([rows] u32: the element's index at the moment of the op, NONE for the other rows) is
+        returned as a fifth element."""
         from .engine import COpDiffOut, OP_DIFF_DT
         hs, f, t = (np.ascontiguousarray(x, np.uint32) for x in (handles, frm, to))
         n = len(hs)
         assert len(f) == n and len(t) == n
         if cap is None:
-            cap = tuple(int(x) for x in self.op_diff_sizes(hs, f, t)[2]) if n else (0, 0)
+            cap = tuple(int(x) for x in self.op_diff_sizes(hs, f, t, lists)[2]) if n else (0, 0)
         rows, surv = np.zeros(max(cap[0], 1), OP_DIFF_DT), np.zeros(max(cap[1], 1), SURV_RESULT_DT)
         rng, fl = np.zeros((max(n, 1), 2), np.uint32), np.zeros(max(n, 1), np.uint32)
-        tot = np.zeros(2, np.uint64)
+        tot, index = np.zeros(2, np.uint64), np.zeros(max(cap[0], 1), np.uint32)
         out = COpDiffOut(cap[0], cap[1], rows.ctypes.data, surv.ctypes.data, rng.ctypes.data, fl.ctypes.data)
-        self._check(self._L.hm_store_op_diffs(self._h, n, _p(hs), _p(f), _p(t), ctypes.byref(out), _p(tot)),
+        self._check(self._L.hm_store_op_diffs_ex(self._h, n, _p(hs), _p(f), _p(t), ctypes.byref(out),
+                                                 _p(index) if lists else None, _p(tot), 1 if lists else 0),
                     "hm_store_op_diffs")
-        return rows[:int(tot[0])], surv[:int(tot[1])], rng[:n], fl[:n]
+        base = (rows[:int(tot[0])], surv[:int(tot[1])], rng[:n], fl[:n])
+        return base + (index[:int(tot[0])],) if lists else base
 
     def set_min_clock(self, h: int, clock: Dict[str, int]) -> None:
         """minimumClock (actor id -> seq); its actors must already be in the document's actor table."""

@@ -578,7 +578,7 @@ int hm_materialize_device(hm_engine *e, const hm_batch *b, const hm_results *r, 
 #define HM_OD_LISTS 1u      /* request flag: no rows, replay the range on the host */
 typedef struct {          /* 16 B */
     uint32_t op;          /* document-local op index, as hm_doc_log orders them */
-    uint32_t kind;        /* HM_OD_CREATE | HM_OD_SET | HM_OD_REMOVE */
+    uint32_t kind;        /* HM_OD_CREATE | HM_OD_SET | HM_OD_REMOVE; with HM_ODF_LISTS also HM_OD_ELEM_* */
     uint32_t n_surv;
     uint32_t surv_off;    /* into the call's table of hm_surv_result: winner first, then conflicts
                              (a survivor's `op` is a document-local op index too) */
@@ -627,6 +627,47 @@ int hm_op_diffs_device(hm_engine *e, const hm_batch *b, const hm_results *r, uin
 /* _host: host tables in, host rows out (staged, synchronous), errors as hm_store_op_diffs. */
 int hm_op_diffs_host(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
                      const uint32_t *from, const uint32_t *to, const hm_op_diff_out *out, uint64_t *out_totals);
+
+/* The same calls with an option word; opts = 0 is the call above, bit for bit.
+ *
+ * HM_ODF_LISTS: list / text element assigns are answered too.  For an applied set / del / link / inc k
+ * on the register of element e of list L, with `after` = the register holds survivors after k and
+ * `before` = it did after the previous applied assign on e (false without one):
+ *   before  after   row
+ *   yes     yes     HM_OD_ELEM_SET     survivors as HM_OD_SET
+ *   yes     no      HM_OD_ELEM_REMOVE
+ *   no      yes     HM_OD_ELEM_INSERT  survivors as HM_OD_SET; the element id is regs[ops[op].reg]
+ *   no      no      no row (a del or an inc on an element that is not visible)
+ * The row's index = the elements of L before e in L's RGA order whose register held survivors just
+ * before k: it travels in out_index [out->cap_rows], parallel to out->rows (HM_NONE for create and
+ * map / table rows; required when cap_rows != 0; not read with opts = 0).  RGA order: the pre-order of
+ * the tree of the applied ins ops below `to` from _head, siblings by (elem, actor rank) descending.
+ * Nothing is replayed for it: the order comes from a sort and a ranked Euler tour of those ins rows,
+ * the visibility from the same survivor rule.
+ * Only a document whose HM_DOC_HAS_LISTS hint is set is answered this way.  Every encoder of this
+ * project sets the hint and a store ORs it over a document's batches, so its own paths always are; a
+ * foreign table that assigns list elements without the hint gets HM_OD_LISTS and no rows, as with
+ * opts = 0 (the safe answer: replay it on the host).  An element assign on a register that no applied
+ * ins of the prefix made (not a merge's tables) emits no row and fails the call like a change row
+ * outside its document (HM_ERR_INVALID; _device: bad & 2).
+ * The work memory of hm_op_diffs_device_ex is hm_op_diffs_work_bytes_ex(b, n, opts) bytes: with
+ * HM_ODF_LISTS and HM_DOC_HAS_LISTS in b->doc_flags (0 = unknown counts as set) a wave's slice is
+ * sized for the order phase as well. */
+#define HM_ODF_LISTS 1u
+#define HM_OD_ELEM_INSERT 3u
+#define HM_OD_ELEM_SET 4u
+#define HM_OD_ELEM_REMOVE 5u
+int hm_store_op_diff_sizes_ex(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                              uint32_t *out_counts, uint32_t *out_flags, uint64_t *out_totals, uint32_t opts);
+int hm_store_op_diffs_ex(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                         const hm_op_diff_out *out, uint32_t *out_index, uint64_t *out_totals, uint32_t opts);
+size_t hm_op_diffs_work_bytes_ex(const hm_batch *b, uint32_t n, uint32_t opts);
+int hm_op_diffs_device_ex(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                          const uint32_t *from, const uint32_t *to, const hm_op_diff_out *out, uint32_t *out_index,
+                          hm_op_diff_summary *out_summary, void *work, void *stream, uint32_t opts);
+int hm_op_diffs_host_ex(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                        const uint32_t *from, const uint32_t *to, const hm_op_diff_out *out, uint32_t *out_index,
+                        uint64_t *out_totals, uint32_t opts);
 
 /* minimumClock row of a document (rank-indexed, 0 = absent); used for the
  * min_cmp of the next merges (Clock.cmp(DocBackend.clock, minimumClock)). */
@@ -831,6 +872,13 @@ int hm_docset_materialize(hm_docset *ds, uint32_t n, const uint32_t *docs, const
  * it.  A document not placed yet: the empty patch.  HM_ERR_UNSUPPORTED on a docset created with
  * HM_DOCSET_NO_PATCHES or HM_DOCSET_NET_DIFFS (it keeps no per-op view of the log). */
 int hm_docset_materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, hm_text **out);
+/* The same with hm_store_op_diffs_ex's option word; opts = 0 is the call above.  HM_ODF_LISTS: the
+ * element rows are rendered too (insert with index and elemId, set and remove with index), so text and
+ * list documents get their patch from the device; "patch": null with "host": true is then left to a
+ * document that assigns list elements without the HM_DOC_HAS_LISTS hint, which no path of this
+ * project produces. */
+int hm_docset_materialize_patch_ex(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, uint32_t opts,
+                                   hm_text **out);
 /* the merged document: {uuid: {"type", "keys": [[key, entry]], "elems": [[elemId, entry]]}} */
 int hm_docset_view(hm_docset *ds, uint32_t doc, hm_text **out);
 /* counters: calls, documents, class moves, net patches from the hit registers, net patches from every

@@ -17,6 +17,15 @@ od_need_kernel, od_walk_kernel<false> = count, past_scan_kernel<false/true>, od_
 fill).  The parent's host replay (docset.cpp Replay on 16 threads) is not driven from here: it
 lives behind hm_docset_apply's rounds, whose patches this tree still renders that way.
 
+--ex times the same C4 legs through the *_ex calls with HM_ODF_LISTS (C4 documents carry no list hint:
+the order phase is skipped, the other instantiation of the walk runs).
+
+--lists times the element diffs instead (HM_ODF_LISTS, the index table copied back with the rows): a
+C5 store of --c5-docs documents and a C3 store of --c3-docs documents, fed the same way; `full` and
+`last`, sizes and rows, with the row counts by kind, and read_history_* of the same slices for the
+read-back the route without the option does before its host replay (which still has no entry point
+of its own to time).
+
 Prints one JSON line."""
 import argparse
 import ctypes
@@ -38,14 +47,32 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--tail", type=int, default=4)
+    ap.add_argument("--ex", action="store_true", help="the C4 legs through the *_ex calls with HM_ODF_LISTS")
+    ap.add_argument("--lists", action="store_true", help="C5 and C3 stores, element diffs answered")
+    ap.add_argument("--c5-docs", type=int, default=100_000)
+    ap.add_argument("--c3-docs", type=int, default=500)
     args = ap.parse_args()
     from hypermerge_amd import synth
-    from hypermerge_amd.columnar import SURV_RESULT_DT
-    from hypermerge_amd.engine import OP_DIFF_DT, COpDiffOut, Engine
-    from hypermerge_amd.store import RowStore, slice_changes
+    from hypermerge_amd.engine import Engine
     note = lambda m: print(f"[bench_op_diffs] {m}", file=sys.stderr, flush=True)      # noqa: E731
     eng = Engine(0)
-    b = synth.generate(synth.config("C4", n_docs=args.docs), threads=min(16, os.cpu_count() or 1))
+    if args.lists:
+        res = {"reps": args.reps, "warmup": args.warmup, "opts": "HM_ODF_LISTS"}
+        for name, docs in (("C5", args.c5_docs), ("C3", args.c3_docs)):
+            res[name] = run(args, eng, synth.generate(synth.config(name, n_docs=docs), threads=min(16, os.cpu_count() or 1)), 1, note)
+        print(json.dumps(res))
+        return
+    res = run(args, eng, synth.generate(synth.config("C4", n_docs=args.docs), threads=min(16, os.cpu_count() or 1)), 1 if args.ex else 0, note)
+    res["opts"] = "HM_ODF_LISTS" if args.ex else 0
+    print(json.dumps(res))
+    assert res["tail_equal"]
+
+
+def run(args, eng, b, opts, note):
+    """the legs over one resident store of b's documents; opts = the *_ex calls' option word (0: the calls without it)"""
+    from hypermerge_amd.columnar import SURV_RESULT_DT
+    from hypermerge_amd.engine import OP_DIFF_DT, COpDiffOut
+    from hypermerge_amd.store import RowStore, slice_changes
     n, S = b.n_docs, b.a_stride
     nch = b.docs["n_changes"].astype(np.int64)
     note(f"{n} documents, {len(b.changes)} changes, {len(b.ops)} ops generated")
@@ -77,23 +104,32 @@ def main():
     out, legs = {}, []
     keep = []
     for name, (frm, to) in sets.items():
-        cnt, fl, tot = st.op_diff_sizes(hs, frm, to)
+        cnt, fl, tot = st.op_diff_sizes(hs, frm, to, lists=bool(opts))
         tr, ts = int(tot[0]), int(tot[1])
         out[name] = {"requests": n, "history_positions": int((to.astype(np.int64) - frm).clip(0).sum()), "rows": tr,
                      "survivors": ts, "flagged": int((fl != 0).sum()), "copy_back_bytes": 16 * (tr + ts) + 12 * n}
         rows, surv = np.zeros(max(tr, 1), OP_DIFF_DT), np.zeros(max(ts, 1), SURV_RESULT_DT)
         rg, flg, t2 = np.zeros(2 * n, np.uint32), np.zeros(n, np.uint32), np.zeros(2, np.uint64)
+        index = np.zeros(max(tr, 1), np.uint32)
+        if opts:
+            out[name]["copy_back_bytes"] += 4 * tr
         o = COpDiffOut(tr, ts, p(rows), p(surv), p(rg), p(flg))
         off = np.zeros(n + 1, np.uint32)
         np.cumsum((to.astype(np.int64) - frm).clip(0), out=off[1:])
         hlog, had = np.zeros(max(int(off[-1]), 1), np.uint32), np.zeros(max(int(off[-1]), 1) * S, np.uint32)
-        keep.append((rows, surv, rg, flg, t2, o, off, hlog, had, frm, to))
+        keep.append((rows, surv, rg, flg, t2, o, off, hlog, had, frm, to, index))
 
         def sizes(frm=frm, to=to, t2=t2):
-            assert L.hm_store_op_diff_sizes(st._h, n, p(hs), p(frm), p(to), None, None, p(t2)) == 0
+            if opts:
+                assert L.hm_store_op_diff_sizes_ex(st._h, n, p(hs), p(frm), p(to), None, None, p(t2), opts) == 0
+            else:
+                assert L.hm_store_op_diff_sizes(st._h, n, p(hs), p(frm), p(to), None, None, p(t2)) == 0
 
-        def diffs(frm=frm, to=to, o=o, t2=t2):
-            assert L.hm_store_op_diffs(st._h, n, p(hs), p(frm), p(to), ctypes.byref(o), p(t2)) == 0
+        def diffs(frm=frm, to=to, o=o, t2=t2, index=index):
+            if opts:
+                assert L.hm_store_op_diffs_ex(st._h, n, p(hs), p(frm), p(to), ctypes.byref(o), p(index), p(t2), opts) == 0
+            else:
+                assert L.hm_store_op_diffs(st._h, n, p(hs), p(frm), p(to), ctypes.byref(o), p(t2)) == 0
 
         def read_history(frm=frm, to=to, off=off, hlog=hlog, had=had):
             assert L.hm_store_read_history(st._h, n, p(hs), p(frm), p(to), p(off), p(hlog), p(had)) == 0
@@ -115,12 +151,13 @@ def main():
         l0, ln = int(last[2][2 * d]), int(last[2][2 * d + 1])
         a, c = full[0][f0 + fn - ln:f0 + fn], last[0][l0:l0 + ln]
         ok &= bool((a["op"] == c["op"]).all() and (a["kind"] == c["kind"]).all() and (a["n_surv"] == c["n_surv"]).all())
+    for name, k in zip(sets, keep):                            # rows by kind (create, set, remove, element insert / set / remove)
+        out[name]["rows_by_kind"] = [int(x) for x in np.bincount(k[0]["kind"][:out[name]["rows"]], minlength=6)]
     res = {"docs": n, "a_stride": S, "rounds": rounds, "log_changes": int(nch.sum()), "log_ops": int(len(b.ops)),
            "reps": args.reps, "warmup": args.warmup, "tail_equal": ok, "sets": out}
     for name, v in ms.items():
         res[name] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v), "runs_ms": [round(x, 3) for x in v]}
-    print(json.dumps(res))
-    assert ok
+    return res
 
 
 if __name__ == "__main__":

@@ -17,7 +17,8 @@
 // built, submitted, waited for), settle (a document whose merge failed rolls back — a throwing
 // applyChanges leaves DocBackend.back unchanged — and the others' reads are listed), read_regs
 // (net diffs: the registers the round's ops hit, every register when changes were queued),
-// read_history (op diffs: the applied changes in order), commit, release, render (each document's
+// read_history (op diffs: the applied changes in order; HM_DOCSET_DEVICE_DIFFS: read_diffs instead, the
+// device's per-op rows of every round's slice), commit, release, render (each document's
 // patch, opSet clock / deps and DocBackend.clock, binary or JSON), verify, assemble; fail() from
 // any phase before commit applies the call to no store and rolls every document back.
 //
@@ -986,8 +987,9 @@ void render_diffs(W &w, DocSt &d, const uint32_t *req, const hm_reg_result *rows
 // RGA placement ((elem, actor) descending siblings, pre-order), to know each op's diff.  The
 // registers it ends on are compared with the device's merged registers afterwards.
 // (For map / table registers and counters the same rows come from the device without a replay:
-// hm_store_op_diffs, which hm_docset_materialize_patch renders; the rounds of hm_docset_apply and
-// every list / text element diff still go through this replay.)
+// hm_store_op_diffs, which hm_docset_materialize_patch renders, with HM_ODF_LISTS the list / text
+// element diffs too; the rounds of hm_docset_apply go through this replay unless the docset was
+// created with HM_DOCSET_DEVICE_DIFFS, which renders them from those rows: Call::read_diffs.)
 struct Replay {
     DocSt &d;
     uint32_t S;
@@ -1138,6 +1140,31 @@ bool same_register(const DocSt &d, uint32_t g, const hm_reg_result &r, const hm_
     return true;
 }
 
+// One request's op-diff rows (hm_store_op_diffs_ex: rows[first .. first + n), their index table and
+// the call's survivors) into a patch writer, in the rows' order: what hm_docset_materialize_patch and
+// the rounds of a HM_DOCSET_DEVICE_DIFFS docset render.  Reads the document's log rows, object types
+// and names; returns NULL, or what is wrong with a row (nothing is written for that row or after it).
+template <typename W>
+const char *render_op_rows(W &w, const DocSt &d, const hm_op_diff *rows, const uint32_t *index, const hm_surv_result *surv,
+                           uint32_t first, uint32_t n) {
+    for (uint32_t x = first; x < first + n; x++) {
+        const hm_op_diff &r = rows[x];
+        if (r.op >= d.oplog.size()) return "an op diff outside the document's log";
+        const hm_op_row &op = d.oplog[r.op];
+        if (op.obj >= d.obj_type.size()) return "an op diff on an unknown object";
+        if (r.kind == HM_OD_CREATE) { w.create(op.obj, op.action); continue; }
+        if (op.reg >= d.regs.size()) return "an op diff on an unknown register";
+        const uint8_t t = d.obj_type[op.obj] != NO_TYPE ? d.obj_type[op.obj] : (uint8_t)HM_MAKE_MAP;
+        if (r.kind == HM_OD_SET) w.map_set(t, op.obj, op.reg, surv + r.surv_off, r.n_surv);
+        else if (r.kind == HM_OD_REMOVE) w.map_remove(t, op.obj, op.reg);
+        else if (r.kind == HM_OD_ELEM_INSERT) w.list_insert(t, op.obj, index[x], op.reg, surv + r.surv_off, r.n_surv);
+        else if (r.kind == HM_OD_ELEM_SET) w.list_set(t, op.obj, index[x], surv + r.surv_off, r.n_surv);
+        else if (r.kind == HM_OD_ELEM_REMOVE) w.list_remove(t, op.obj, index[x]);
+        else return "an op diff of an unknown kind";
+    }
+    return nullptr;
+}
+
 // the document as the patch base holds it: {uuid: {type, keys: [[key, entry]], elems: [[elemId, entry]]}}
 // (created: per object, 1 = it exists in the rendered state; NULL = every object the document knows)
 void render_view(std::string &o, const DocSt &d, const hm_reg_result *rows, const hm_surv_result *surv, uint32_t n_regs,
@@ -1192,6 +1219,9 @@ struct hm_docset {
     bool patches = true;
     bool binary = false;                                     // HM_DOCSET_BINARY results
     bool op_diffs = true;                                    // Automerge's per-op diff sequence (else HM_DOCSET_NET_DIFFS)
+    bool device_diffs = false;                               // HM_DOCSET_DEVICE_DIFFS: the sequence from the device's op-diff rows
+    uint64_t dstat[4] = {0, 0, 0, 0};                        // device diffs: rounds rendered, store calls, calls repeated, 0
+    double surv_per_row = 2.0;                               // device diffs: survivors guessed per row (grows with what the calls report)
     hm_store *stores[N_CLASS] = {};
     std::vector<uint32_t> free_h[N_CLASS];                   // released handles (empty documents), reused first
     uint32_t opened[N_CLASS] = {};                           // handles opened per store
@@ -1278,6 +1308,12 @@ struct Call {
     // op diffs: the rounds that read their history slice, per class, and the slices (applied
     // changes in application order, their allDeps rows)
     std::vector<uint32_t> hreq[N_CLASS], hlog[N_CLASS], had[N_CLASS];
+    // device diffs (HM_DOCSET_DEVICE_DIFFS): per class the op-diff rows of its rounds' slices, their
+    // survivors, index table and (block, rows) per request; Round::h0 = the round's request
+    std::vector<hm_op_diff> drows[N_CLASS];
+    std::vector<hm_surv_result> dsurv[N_CLASS];
+    std::vector<uint32_t> dindex[N_CLASS], drange[N_CLASS];
+    uint64_t call_dstat[3] = {0, 0, 0};                      // (ds->dstat once the call commits)
     bool exotic = false;                                     // a binary call that falls back to JSON
     // fault injection for the tests (HM_DOCSET_INJECT_FAIL=wait:<k> fails the call after the k-th
     // class's batch is applied, =read after every class's; the call must then be undone everywhere)
@@ -1569,6 +1605,61 @@ struct Call {
         }
         return HM_OK;
     }
+    // device diffs: what each applied op of every round's history slice did, from the stores (one
+    // one-walk call per class).  The tables are guessed: rows = the ops the rounds handed in, plus the
+    // log's ops of a document that held queued changes (they may apply now), survivors = rows times the
+    // largest survivors-per-row ratio the docset's calls have reported so far; a call that reports
+    // larger totals is repeated once with them.
+    int read_diffs() {
+        for (uint32_t c = 0; c < N_CLASS; c++) {
+            call_dstat[0] += hreq[c].size();
+            std::vector<uint32_t> hh, from, to, who;
+            size_t ops = 0;
+            for (uint32_t i : hreq[c]) {
+                Round &x = R[i];
+                x.h0 = HM_NONE;
+                if (x.prev_hist >= x.res.hist_len) continue;     // (the round applied nothing: no diffs)
+                x.h0 = (uint32_t)hh.size();
+                hh.push_back(x.handle); from.push_back(x.prev_hist); to.push_back(x.res.hist_len); who.push_back(i);
+                ops += x.op.size();
+                const DocSt &d = ds->doc(x.doc);
+                if (d.n_queued) ops += d.n_ops;
+            }
+            if (hh.empty()) continue;
+            const uint32_t m = (uint32_t)hh.size();
+            std::vector<uint32_t> flags(m);
+            drange[c].resize(2 * (size_t)m);
+            uint64_t cap[2] = {ops + 64, (uint64_t)((double)ops * ds->surv_per_row) + 64}, tot[2] = {0, 0};
+            const std::string before = hm_engine_last_error(ds->e);
+            for (int attempt = 0;; attempt++) {
+                if (cap[0] > 0xFFFFFFFFull || cap[1] > 0xFFFFFFFFull) return hm_engine_fail(ds->e, HM_ERR_NOMEM, "a call's rows stay below 2^32");
+                drows[c].resize(cap[0] + 1); dsurv[c].resize(cap[1] + 1); dindex[c].resize(cap[0] + 1);
+                hm_op_diff_out po = {(uint32_t)cap[0], (uint32_t)cap[1], drows[c].data(), dsurv[c].data(), drange[c].data(), flags.data()};
+                call_dstat[1]++;
+                const int rc = hm_store_op_diffs_ex(ds->stores[c], m, hh.data(), from.data(), to.data(), &po, dindex[c].data(), tot,
+                                                    HM_ODF_LISTS | HM_ODF_ONCE);
+                if (rc == HM_OK) break;
+                if (rc != HM_ERR_NOMEM || attempt || (tot[0] <= cap[0] && tot[1] <= cap[1])) return rc;
+                hm_engine_fail(ds->e, HM_OK, before.c_str());     // (too small a guess is no failure: the sizes are known now)
+                call_dstat[2]++;
+                cap[0] = tot[0]; cap[1] = tot[1];
+            }
+            if (tot[0]) ds->surv_per_row = std::min(16.0, std::max(ds->surv_per_row, 1.25 * (double)tot[1] / (double)tot[0]));
+            for (uint32_t k = 0; k < m; k++) {
+                const Round &x = R[who[k]];
+                if (flags[k]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "a round's op diffs were flagged: list elements assigned without the document's hint");
+                const uint64_t r0 = drange[c][2 * (size_t)k], rn = drange[c][2 * (size_t)k + 1];
+                if (r0 + rn > cap[0]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "a round's op diffs outside the call's rows");
+                const uint64_t n_ops = (uint64_t)ds->doc(x.doc).n_ops + x.op.size();      // (the log once the round commits)
+                for (uint64_t r = r0; r < r0 + rn; r++) {
+                    const hm_op_diff &dr = drows[c][r];
+                    if (dr.op >= n_ops || (uint64_t)dr.surv_off + dr.n_surv > cap[1])
+                        return hm_engine_fail(ds->e, HM_ERR_INVALID, "an op diff outside the document's log");
+                }
+            }
+        }
+        return HM_OK;
+    }
     // commit: every successful document's host state advances with the device's (a call lists a
     // document once, so the documents advance in parallel; the released handles of moved documents
     // go to the shared lists first)
@@ -1592,6 +1683,10 @@ struct Call {
                 for (const hm_op_row &o : x.op)
                     if (o.action <= HM_MAKE_TEXT && o.obj < d.obj_type.size() && d.obj_type[o.obj] == NO_TYPE) d.obj_type[o.obj] = o.action;
                 if (!(ds->patches && ds->op_diffs)) continue;
+                if (ds->device_diffs) {                          // (the renderer reads the log's op rows; nothing is replayed)
+                    d.oplog.insert(d.oplog.end(), x.op.begin(), x.op.end());
+                    continue;
+                }
                 // the replay's view of the log (op indices are the store's: appended in order)
                 for (const hm_change_row &c : x.ch) {
                     d.ch_op0.push_back(old_n_ops + c.op_first);
@@ -1605,12 +1700,18 @@ struct Call {
             }
         });
         for (int k = 0; k < 3; k++) ds->routing[k] += call_routing[k];
+        for (int k = 0; k < 3; k++) ds->dstat[k] += call_dstat[k];
     }
     // a round's diffs into either writer: the replay of its history slice (op diffs), or the net
     // diffs of the registers it requested
     template <typename W> void diffs(W &w, Round &x, DocSt &d) {
         if (!ds->patches) return;
-        if (ds->op_diffs) {
+        if (ds->device_diffs) {
+            // (read_diffs checked every row against the log before the commit)
+            if (x.h0 != HM_NONE)
+                render_op_rows(w, d, drows[x.cls].data(), dindex[x.cls].data(), dsurv[x.cls].data(), drange[x.cls][2 * (size_t)x.h0],
+                               drange[x.cls][2 * (size_t)x.h0 + 1]);
+        } else if (ds->op_diffs) {
             Replay rp{d, STRIDES[x.cls]};
             rp.round(w, hlog[x.cls].data() + x.h0, had[x.cls].data() + (size_t)x.h0 * STRIDES[x.cls], x.h1 - x.h0, x.touched);
         } else if (x.q1 > x.q0) {
@@ -1809,15 +1910,20 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
     // (the injected read failure: after the requests are built, before any read)
     if (c.inj_read) return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "injected failure (HM_DOCSET_INJECT_FAIL)"));
     if ((rc = c.read_regs())) return c.fail(rc);
-    if ((rc = c.read_history())) return c.fail(rc);
-    c.mark("read history");
+    if (ds->device_diffs) {
+        if ((rc = c.read_diffs())) return c.fail(rc);
+        c.mark("read diffs");
+    } else {
+        if ((rc = c.read_history())) return c.fail(rc);
+        c.mark("read history");
+    }
     c.commit();
     c.mark("commit");
     c.release();
     c.mark("read regs");
     c.render();
     c.mark("diffs");
-    if (ds->patches && ds->op_diffs) {
+    if (ds->patches && ds->op_diffs && !ds->device_diffs) {
         c.verify();
         c.mark("verify");
     }
@@ -1912,6 +2018,11 @@ int hm_docset_create(hm_engine *e, const hm_docset_config *cfg, hm_docset **out)
     ds->patches = !(cfg && (cfg->flags & HM_DOCSET_NO_PATCHES));
     ds->binary = cfg && (cfg->flags & HM_DOCSET_BINARY);
     ds->op_diffs = !(cfg && (cfg->flags & HM_DOCSET_NET_DIFFS));
+    ds->device_diffs = cfg && (cfg->flags & HM_DOCSET_DEVICE_DIFFS);
+    if (ds->device_diffs && !(ds->patches && ds->op_diffs)) {
+        delete ds;
+        return hm_engine_fail(e, HM_ERR_INVALID, "HM_DOCSET_DEVICE_DIFFS renders per-op diffs: not with HM_DOCSET_NO_PATCHES / HM_DOCSET_NET_DIFFS");
+    }
     ds->chunks.reserve(1u << 16);
     *out = ds;
     return HM_OK;
@@ -2290,21 +2401,8 @@ int hm_docset_materialize_patch_ex(hm_docset *ds, uint32_t n, const uint32_t *do
                 jclock(o, d, T.heads.data() + (size_t)j * S, std::min<size_t>(d.actors.size(), S));
                 o += TAIL;
                 JsonW w{o, d};
-                for (uint32_t x = range[2 * j]; x < range[2 * j] + range[2 * j + 1]; x++) {
-                    const hm_op_diff &r = rows[x];
-                    if (r.op >= d.oplog.size()) return hm_engine_fail(ds->e, HM_ERR_INVALID, "an op diff outside the document's log");
-                    const hm_op_row &op = d.oplog[r.op];
-                    if (op.obj >= d.obj_type.size()) return hm_engine_fail(ds->e, HM_ERR_INVALID, "an op diff on an unknown object");
-                    if (r.kind == HM_OD_CREATE) { w.create(op.obj, op.action); continue; }
-                    if (op.reg >= d.regs.size()) return hm_engine_fail(ds->e, HM_ERR_INVALID, "an op diff on an unknown register");
-                    const uint8_t t = d.obj_type[op.obj] != NO_TYPE ? d.obj_type[op.obj] : (uint8_t)HM_MAKE_MAP;
-                    if (r.kind == HM_OD_SET) w.map_set(t, op.obj, op.reg, surv.data() + r.surv_off, r.n_surv);
-                    else if (r.kind == HM_OD_REMOVE) w.map_remove(t, op.obj, op.reg);
-                    else if (r.kind == HM_OD_ELEM_INSERT) w.list_insert(t, op.obj, index[x], op.reg, surv.data() + r.surv_off, r.n_surv);
-                    else if (r.kind == HM_OD_ELEM_SET) w.list_set(t, op.obj, index[x], surv.data() + r.surv_off, r.n_surv);
-                    else if (r.kind == HM_OD_ELEM_REMOVE) w.list_remove(t, op.obj, index[x]);
-                    else return hm_engine_fail(ds->e, HM_ERR_INVALID, "an op diff of an unknown kind");
-                }
+                if (const char *err = render_op_rows(w, d, rows.data(), index.data(), surv.data(), range[2 * j], range[2 * j + 1]))
+                    return hm_engine_fail(ds->e, HM_ERR_INVALID, err);
                 o += "]}}";
             }
         }
@@ -2353,6 +2451,12 @@ int hm_docset_handles(const hm_docset *ds, uint32_t a_stride, uint32_t *out_open
 int hm_docset_routing(const hm_docset *ds, uint64_t *out3) {
     if (!ds || !out3) return HM_ERR_INVALID;
     for (int k = 0; k < 3; k++) out3[k] = ds->routing[k];
+    return HM_OK;
+}
+
+int hm_docset_diff_stats(const hm_docset *ds, uint64_t *out4) {
+    if (!ds || !out4) return HM_ERR_INVALID;
+    for (int i = 0; i < 4; i++) out4[i] = ds->dstat[i];
     return HM_OK;
 }
 

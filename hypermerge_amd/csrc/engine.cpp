@@ -574,7 +574,7 @@ static size_t od_fixed_bytes(uint32_t n) {
 size_t hm_op_diffs_work_bytes(const hm_batch *b, uint32_t n) { return hm_op_diffs_work_bytes_ex(b, n, 0u); }
 
 size_t hm_op_diffs_work_bytes_ex(const hm_batch *b, uint32_t n, uint32_t opts) {
-    if (!b || !n) return 0;
+    if (!b || !n || (opts & ~HM_ODF_LISTS)) return 0;         // (HM_ODF_ONCE is the resident store's alone)
     const unsigned long long sw = od_batch_slice(b, opts);
     return od_fixed_bytes(n) + (size_t)hm_od_waves(n, sw) * (size_t)sw * 4;
 }

@@ -98,3 +98,12 @@ hipError_t hm_launch_op_diff_need(const OpDiffArgs &a, unsigned long long *out_w
 // count + scan (sum need not be zeroed; n == 0: sum is zeroed and nothing else is read or written)
 hipError_t hm_launch_op_diff_count(const OpDiffArgs &a, hipStream_t s);
 hipError_t hm_launch_op_diff_fill(const OpDiffArgs &a, hipStream_t s);
+// HM_ODF_ONCE: one launch instead of count + scan + fill.  A request reserves its row block (the ops
+// of its slice: an upper bound of its rows) and, per 64-op step, the step's survivor block, each with
+// one atomicAdd on sum->totals; a block that does not fit under cap_rows / cap_surv is not written and
+// the walk goes on, so sum->totals = (the row bounds, the survivors) of the whole call whatever the
+// caps.  out_range[2i ..] = (block, rows emitted): the blocks lie in the order the waves finished, a
+// block's unused tail is a gap; a flagged request gets (block, 0).  surv_off is absolute.  sum: totals,
+// flags and bad are written, the maxima stay 0; cnt / off / aux / part are not used.  out_index as in
+// the fill launch (HM_NONE throughout when opts has no HM_ODF_LISTS).
+hipError_t hm_launch_op_diff_once(const OpDiffArgs &a, hipStream_t s);

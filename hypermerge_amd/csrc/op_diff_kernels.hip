@@ -30,6 +30,10 @@
 //      emit   the ops of the range: rows are numbered by ballot, survivors by a wave scan of the
 //             counts a first walk of the chain returns; the fill pass walks again to write them
 //  The scan between count and fill is past_scan_kernel (hm_launch_past_scan).
+//  od_walk_kernel    <false, LISTS, true>: the one-walk form (HM_ODF_ONCE): no count pass and no scan; a
+//                    request takes a row block sized by the ops of its slice and, per step, a survivor
+//                    block sized by the step's first walks, each with one atomicAdd on the call's
+//                    totals (changes_kernel's pattern), and writes as it goes
 //
 // Every loop over a chain is bounded by the document's op rows, so tables that are not a merge's
 // (overlapping op ranges) cannot hang a wave; no row past a lim_* of the source is read.
@@ -275,8 +279,15 @@ __device__ uint32_t list_order(const DocSource &D, const DocRef &s, uint32_t lim
     return n;
 }
 
-template <bool FILL, bool LISTS>
+// a 64-bit sum over the wave, in every lane
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
+    for (uint32_t d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+template <bool FILL, bool LISTS, bool ONCE = false>
 __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
+    static_assert(!(FILL && ONCE), "the one-walk form has no fill pass");
     __shared__ Lds L;
     const uint32_t lane = threadIdx.x;
     const DocSource &D = A.src;
@@ -313,6 +324,26 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
         const uint32_t lim = to < s.n_c ? to : s.n_c;          // history positions of interest lie below it
         uint32_t rows = 0, surv = 0;                           // emitted so far
         bool lists = false, rows_ok = true;
+        // ONCE: the request's row block (the ops of its slice bound its rows: an ins emits none, every
+        // other op at most one), reserved on the call's row total; written only when it fits
+        unsigned long long blk = 0, bound = 0;
+        bool fits = false;
+        if (ONCE) {
+            if (from < lim)
+                for (uint32_t i = lane; i < s.n_c; i += 64u) {
+                    const int32_t hp = D.hist[s.c_off + i];
+                    if (hp < 0 || (uint32_t)hp < from || (uint32_t)hp >= lim) continue;
+                    const hm_change_row c = D.changes[s.c_off + i];
+                    if (c.n_ops && c.op_first >= s.o_off && (unsigned long long)c.op_first + c.n_ops <= (unsigned long long)s.o_off + s.n_o)
+                        bound += c.n_ops;
+                }
+            bound = wave_sum64(bound);
+            if (bound) {                                       // (uniform branch)
+                if (lane == 0) blk = atomicAdd((unsigned long long *)&A.sum->totals[0], bound);
+                blk = __shfl(blk, 0);
+                fits = blk + bound <= (unsigned long long)A.cap_rows;
+            }
+        }
         if (from < lim) {
             for (uint32_t i = lane; i < s.n_r; i += 64u) W.last[i] = HM_NONE;
             for (uint32_t i = lane; i < s.n_objs; i += 64u) W.otype[i] = 0u;
@@ -439,11 +470,40 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
                         if (LISTS) A.out_index[of.x + row] = idx;
                     }
                 }
+                if (ONCE) {
+                    // the step's survivor block, reserved on the call's survivor total by the sizes the
+                    // first walks returned; the second walk writes into it
+                    const uint32_t ssum = __shfl(is, 63);
+                    unsigned long long sblk = 0;
+                    if (ssum) {                                 // (uniform branch)
+                        if (lane == 0) sblk = atomicAdd((unsigned long long *)&A.sum->totals[1], (unsigned long long)ssum);
+                        sblk = __shfl(sblk, 0);
+                    }
+                    if (emit && fits && row < bound && sblk + ssum <= (unsigned long long)A.cap_surv) {
+                        const unsigned long long so = sblk + is - ns;
+                        if (ns) walk(D, s, W, dop, A.out_surv + so, ns);
+                        hm_op_diff r;
+                        r.op = dop; r.kind = make ? HM_OD_CREATE : (ns ? HM_OD_SET : HM_OD_REMOVE); r.n_surv = ns; r.surv_off = (uint32_t)so;
+                        if (LISTS && el) r.kind = was ? (now ? HM_OD_ELEM_SET : HM_OD_ELEM_REMOVE) : HM_OD_ELEM_INSERT;
+                        A.out_rows[blk + row] = r;
+                        if (LISTS) A.out_index[blk + row] = idx;
+                    }
+                }
                 rows += (uint32_t)__popcll(em); surv += __shfl(is, 63);
             }
             __syncthreads();
         }
-        if (!FILL) {
+        if (ONCE) {
+            // (a flagged request keeps its block and refers to none of it)
+            const bool any_lists = __ballot(lists) != 0ull, any_rows_bad = __ballot(!rows_ok) != 0ull;
+            if (any_rows_bad) bad |= HM_OD_BAD_ROWS;
+            if (lane == 0) {
+                *(uint2 *)(A.out_range + 2 * q) = make_uint2((uint32_t)blk, any_lists || !fits ? 0u : rows);
+                A.out_flags[q] = any_lists ? HM_OD_LISTS : 0u;
+                if (any_lists) atomicOr(&A.sum->flags, HM_OD_LISTS);
+                if (bad) atomicOr(&A.sum->bad, bad);
+            }
+        } else if (!FILL) {
             const bool any_lists = __ballot(lists) != 0ull, any_rows_bad = __ballot(!rows_ok) != 0ull;
             if (any_rows_bad) bad |= HM_OD_BAD_ROWS;
             if (lane == 0) {
@@ -476,6 +536,17 @@ hipError_t hm_launch_op_diff_count(const OpDiffArgs &a, hipStream_t s) {
     else hipLaunchKernelGGL((hmo::od_walk_kernel<false, false>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
     if ((r = hipGetLastError()) != hipSuccess) return r;
     return hm_launch_past_scan(scan_args(a), s);
+}
+
+hipError_t hm_launch_op_diff_once(const OpDiffArgs &a, hipStream_t s) {
+    hipError_t r = hipMemsetAsync(a.sum, 0, sizeof(hm_op_diff_summary), s);
+    if (r != hipSuccess || !a.n) return r;
+    if (a.opts & HM_ODF_LISTS) hipLaunchKernelGGL((hmo::od_walk_kernel<false, true, true>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+    else {                                                     // (no document of the call has lists: no row has an index)
+        if (a.out_index && a.cap_rows && (r = hipMemsetAsync(a.out_index, 0xFF, (size_t)a.cap_rows * 4, s)) != hipSuccess) return r;
+        hipLaunchKernelGGL((hmo::od_walk_kernel<false, false, true>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+    }
+    return hipGetLastError();
 }
 
 hipError_t hm_launch_op_diff_fill(const OpDiffArgs &a, hipStream_t s) {

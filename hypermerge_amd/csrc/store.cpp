@@ -1289,11 +1289,11 @@ int hm_store_materialize_sized(hm_store *s, uint32_t n, const uint32_t *doc_hand
     }
 }
 
-// The count pass of n staged op-diff requests: handles and ranges go to the stage buffer, the counts,
-// offsets and summary stay there (A.cnt / A.off / A.aux / A.sum), the chains' work memory is the
-// head of s->past; *sum = the summary, read back.
-static int op_diff_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
-                         uint32_t opts, OpDiffArgs &A, hm_op_diff_summary *sum) {
+// n op-diff requests staged: handles and ranges go to the stage buffer, where the counts, offsets and
+// summary will stay (A.cnt / A.off / A.aux / A.sum); the largest requested document sizes a wave's
+// slice of the chains' work memory (A.slice_words, A.waves; A.work is the caller's to place).
+static int op_diff_stage(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                         uint32_t opts, OpDiffArgs &A) {
     hipStream_t st = hm_engine_stream(s->e);
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_sum = 0, o_need = 128, o_h = 256, o_from = o_h + al(4 * (size_t)n), o_to = o_from + al(4 * (size_t)n),
@@ -1324,9 +1324,12 @@ static int op_diff_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, c
     if (!any_lists) A.opts &= ~HM_ODF_LISTS;                   // (no requested document has lists: the walk without them)
     A.slice_words = need ? need : 1;
     A.waves = hm_od_waves(n, A.slice_words);
-    if ((rc = ensure_buf(s, s->past, al((size_t)A.waves * A.slice_words * 4)))) return rc;
-    A.work = (uint32_t *)s->past.p;
-    SCHK(s, hm_launch_op_diff_count(A, st));
+    return HM_OK;
+}
+
+// the summary a launch left, read back: *sum, and the status of its bad bits
+static int op_diff_summary(hm_store *s, const OpDiffArgs &A, hm_op_diff_summary *sum) {
+    hipStream_t st = hm_engine_stream(s->e);
     SCHK(s, hipMemcpyAsync(s->h_st, A.sum, sizeof(hm_op_diff_summary), hipMemcpyDeviceToHost, st));
     SCHK(s, hipStreamSynchronize(st));
     memcpy(sum, s->h_st, sizeof *sum);
@@ -1334,6 +1337,17 @@ static int op_diff_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, c
     if (sum->bad & HM_OD_BAD_ROWS) return hm_engine_fail(s->e, HM_ERR_INVALID, "a change row outside its document's segments");
     if (sum->bad) return hm_engine_fail(s->e, HM_ERR_NOMEM, "a document outgrows the op-diff work memory");
     return HM_OK;
+}
+
+// The count pass of n op-diff requests; the chains' work memory is the head of s->past.
+static int op_diff_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                         uint32_t opts, OpDiffArgs &A, hm_op_diff_summary *sum) {
+    int rc = op_diff_stage(s, n, doc_handles, from, to, opts, A);
+    if (rc) return rc;
+    if ((rc = ensure_buf(s, s->past, ((size_t)A.waves * A.slice_words * 4 + 255) & ~(size_t)255))) return rc;
+    A.work = (uint32_t *)s->past.p;
+    SCHK(s, hm_launch_op_diff_count(A, hm_engine_stream(s->e)));
+    return op_diff_summary(s, A, sum);
 }
 
 extern "C" {
@@ -1379,8 +1393,10 @@ int hm_store_op_diffs(hm_store *s, uint32_t n, const uint32_t *doc_handles, cons
 
 int hm_store_op_diffs_ex(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
                          const hm_op_diff_out *out, uint32_t *out_index, uint64_t *out_totals, uint32_t opts) {
-    if (!s || !out || (n && (!doc_handles || !from || !to || !out->range || !out->flags)) || (opts & ~HM_ODF_LISTS)) return HM_ERR_INVALID;
+    if (!s || !out || (n && (!doc_handles || !from || !to || !out->range || !out->flags)) || (opts & ~(HM_ODF_LISTS | HM_ODF_ONCE))) return HM_ERR_INVALID;
     if ((out->cap_rows && !out->rows) || (out->cap_surv && !out->surv)) return HM_ERR_INVALID;
+    const bool once = (opts & HM_ODF_ONCE) != 0u;
+    if (once && !out_totals) return HM_ERR_INVALID;           // (a caller that guesses the sizes takes the ones to repeat with)
     const bool want_index = (opts & HM_ODF_LISTS) != 0u;
     if (want_index && out->cap_rows && !out_index) return HM_ERR_INVALID;
     if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
@@ -1390,6 +1406,35 @@ int hm_store_op_diffs_ex(hm_store *s, uint32_t n, const uint32_t *doc_handles, c
         hipStream_t st = hm_engine_stream(s->e);
         OpDiffArgs A;
         hm_op_diff_summary sum;
+        if (once) {
+            // one launch into tables of the caller's capacities: [work][rows][survivors][ranges][flags][index]
+            int rc = op_diff_stage(s, n, doc_handles, from, to, opts & ~HM_ODF_ONCE, A);
+            if (rc) return rc;
+            auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+            const size_t cr = out->cap_rows, cs = out->cap_surv;
+            const size_t sz[5] = {cr * sizeof(hm_op_diff), cs * sizeof(hm_surv_result), 8 * (size_t)n, 4 * (size_t)n, want_index ? 4 * cr : 0};
+            size_t o[5], total = al((size_t)A.waves * A.slice_words * 4);
+            for (int i = 0; i < 5; i++) { o[i] = total; total += al(sz[i] + 1); }
+            if ((rc = ensure_buf(s, s->past, total))) return rc;
+            uint8_t *bp = s->past.p;
+            A.work = (uint32_t *)bp;
+            A.cap_rows = out->cap_rows; A.cap_surv = out->cap_surv;
+            A.out_rows = (hm_op_diff *)(bp + o[0]); A.out_surv = (hm_surv_result *)(bp + o[1]);
+            A.out_range = (uint32_t *)(bp + o[2]); A.out_flags = (uint32_t *)(bp + o[3]); A.out_index = want_index ? (uint32_t *)(bp + o[4]) : nullptr;
+            SCHK(s, hm_launch_op_diff_once(A, st));
+            if ((rc = op_diff_summary(s, A, &sum))) return rc;
+            out_totals[0] = sum.totals[0]; out_totals[1] = sum.totals[1];
+            if (sum.totals[0] > cr || sum.totals[1] > cs)
+                return hm_engine_fail(s->e, HM_ERR_NOMEM, "a capacity below the rows of the op diffs");
+            // (the blocks lie anywhere below the totals)
+            const size_t used[5] = {(size_t)sum.totals[0] * sizeof(hm_op_diff), (size_t)sum.totals[1] * sizeof(hm_surv_result), sz[2], sz[3],
+                                    want_index ? 4 * (size_t)sum.totals[0] : 0};
+            void *dst[5] = {out->rows, out->surv, out->range, out->flags, out_index};
+            for (int i = 0; i < 5; i++)
+                if (used[i]) SCHK(s, hipMemcpyAsync(dst[i], bp + o[i], used[i], hipMemcpyDeviceToHost, st));
+            SCHK(s, hipStreamSynchronize(st));
+            return HM_OK;
+        }
         int rc = op_diff_count(s, n, doc_handles, from, to, opts, A, &sum);
         if (rc) return rc;
         const uint64_t tr = sum.totals[0], ts = sum.totals[1];

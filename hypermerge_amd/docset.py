@@ -19,6 +19,7 @@ from .engine import Engine, lib
 NO_PATCHES = 1          # HM_DOCSET_NO_PATCHES
 BINARY = 2              # HM_DOCSET_BINARY
 NET_DIFFS = 4           # HM_DOCSET_NET_DIFFS
+DEVICE_DIFFS = 8        # HM_DOCSET_DEVICE_DIFFS
 
 
 class _Cfg(ctypes.Structure):
@@ -30,10 +31,12 @@ class _Info(ctypes.Structure):
                                                "hist_len", "n_queued")]
 
 
-def _text(L, t) -> Tuple[str, np.ndarray]:
+def _text(L, t, raw: bool = False) -> Tuple[Any, np.ndarray]:
     n = ctypes.c_size_t()
     p = L.hm_text_data(t, ctypes.byref(n))
-    s = ctypes.string_at(p, n.value).decode("utf-8", "surrogatepass") if n.value else ""
+    s = ctypes.string_at(p, n.value) if n.value else b""
+    if not raw:
+        s = s.decode("utf-8", "surrogatepass")
     k = ctypes.c_uint32()
     rp = L.hm_text_results(t, ctypes.byref(k))
     res = np.zeros(k.value, DOC_RESULT_DT)
@@ -45,13 +48,16 @@ def _text(L, t) -> Tuple[str, np.ndarray]:
 
 class DocSet:
     def __init__(self, engine: Engine, threads: int = 0, patches: bool = True, net_diffs: bool = False,
-                 binary: bool = False):
+                 binary: bool = False, device_diffs: bool = False):
         """binary: results in the HMP1 form the Node host reads (HM_DOCSET_BINARY).  `apply` reads
         JSON only: of a binary docset it reads the calls that fall back to JSON (a string with a
-        lone surrogate among the call's patches)."""
+        lone surrogate among the call's patches); `apply_raw` returns either form as bytes.
+        device_diffs (HM_DOCSET_DEVICE_DIFFS): every round's per-op diffs are rendered from the
+        device's op-diff rows instead of replayed on the host; the same patches."""
         self._L, self.engine = lib(), engine
         h = ctypes.c_void_p()
-        cfg = _Cfg(threads, (0 if patches else NO_PATCHES) | (NET_DIFFS if net_diffs else 0) | (BINARY if binary else 0))
+        cfg = _Cfg(threads, (0 if patches else NO_PATCHES) | (NET_DIFFS if net_diffs else 0) | (BINARY if binary else 0) |
+                   (DEVICE_DIFFS if device_diffs else 0))
         engine._check(self._L.hm_docset_create(engine._h, ctypes.byref(cfg), ctypes.byref(h)), "hm_docset_create")
         self._h = h
 
@@ -85,6 +91,16 @@ class DocSet:
                                                    ids.ctypes.data, len(ids), ctypes.byref(t)), "hm_docset_apply")
         s, res = _text(self._L, t)
         return res, json.loads(s)
+
+    def apply_raw(self, docs: Sequence[int], blocks: Sequence[Sequence[bytes]]) -> Tuple[np.ndarray, bytes]:
+        """`apply` with the call's text as it came: the JSON's bytes, or the HMP1 words of a binary docset."""
+        data, bo, db = pack_offsets(blocks)
+        ids = np.ascontiguousarray(docs, np.uint32)
+        t = ctypes.c_void_p()
+        self.engine._check(self._L.hm_docset_apply(self._h, data.ctypes.data, bo.ctypes.data, db.ctypes.data,
+                                                   ids.ctypes.data, len(ids), ctypes.byref(t)), "hm_docset_apply")
+        s, res = _text(self._L, t, raw=True)
+        return res, s
 
     def info(self, doc: int) -> Dict[str, int]:
         i = _Info()
@@ -229,6 +245,13 @@ class DocSet:
         self.engine._check(self._L.hm_docset_stats(self._h, out.ctypes.data), "hm_docset_stats")
         return {"calls": int(out[0]), "docs": int(out[1]), "moves": int(out[2]), "hit_patches": int(out[3]),
                 "full_patches": int(out[4]), "op_patches": int(out[5]), "replay_mismatch": int(out[6])}
+
+    def diff_stats(self) -> Dict[str, int]:
+        """hm_docset_diff_stats (device_diffs=True): document rounds rendered from device rows, store
+        op-diff calls, and the calls among them that were repeated with larger tables."""
+        out = np.zeros(4, np.uint64)
+        self.engine._check(self._L.hm_docset_diff_stats(self._h, out.ctypes.data), "hm_docset_diff_stats")
+        return {"rounds": int(out[0]), "calls": int(out[1]), "repeated": int(out[2])}
 
 
 # ---- test helpers: the frontend's view of a document rebuilt from patches ----

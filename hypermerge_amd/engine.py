@@ -43,7 +43,7 @@ EXPORTS = ("hm_abi_version", "hm_status_message", "hm_engine_create", "hm_engine
            "hm_docset_materialize", "hm_store_op_diff_sizes", "hm_store_op_diffs", "hm_op_diffs_work_bytes",
            "hm_op_diffs_device", "hm_op_diffs_host", "hm_docset_materialize_patch",
            "hm_store_op_diff_sizes_ex", "hm_store_op_diffs_ex", "hm_op_diffs_work_bytes_ex", "hm_op_diffs_device_ex",
-           "hm_op_diffs_host_ex", "hm_docset_materialize_patch_ex")
+           "hm_op_diffs_host_ex", "hm_docset_materialize_patch_ex", "hm_docset_diff_stats")
 
 _lib = None
 
@@ -116,7 +116,7 @@ def lib():
             "hm_text_data": [vp, vp], "hm_text_results": [vp, vp], "hm_text_free": [vp],
             "hm_docset_doc_info": [vp, u32, vp], "hm_docset_history_prefix": [vp, u32, u32, vp],
             "hm_docset_clock_update": [vp, u32, vp, vp, vp, vp], "hm_docset_view": [vp, u32, vp],
-            "hm_docset_stats": [vp, vp], "hm_docset_routing": [vp, vp], "hm_docset_handles": [vp, u32, vp, vp], "hm_sync_ranges_host": [vp, vp, vp, vp, vp, vp, u32, u32],
+            "hm_docset_stats": [vp, vp], "hm_docset_diff_stats": [vp, vp], "hm_docset_routing": [vp, vp], "hm_docset_handles": [vp, u32, vp, vp], "hm_sync_ranges_host": [vp, vp, vp, vp, vp, vp, u32, u32],
             "hm_store_blocked": [vp, vp, u32, vp], "hm_store_waiting": [vp, u32, vp, vp, vp, vp],
             "hm_store_read_queue": [vp, u32, vp, vp, vp],
             "hm_missing_deps_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), vp, vp],
@@ -195,6 +195,7 @@ OD_CREATE, OD_SET, OD_REMOVE = 0, 1, 2   # HM_OD_* row kinds
 OD_LISTS = 1                              # HM_OD_LISTS request flag
 OD_ELEM_INSERT, OD_ELEM_SET, OD_ELEM_REMOVE = 3, 4, 5   # HM_OD_ELEM_* row kinds (ODF_LISTS)
 ODF_LISTS = 1                             # HM_ODF_LISTS option: answer list / text element assigns
+ODF_ONCE = 2                              # HM_ODF_ONCE option (hm_store_op_diffs_ex): one walk into guessed tables
 OP_DIFF_DT = np.dtype([("op", "<u4"), ("kind", "<u4"), ("n_surv", "<u4"), ("surv_off", "<u4")])
 
 

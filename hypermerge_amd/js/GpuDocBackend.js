@@ -485,11 +485,12 @@ class GpuEngine {
     this.devices = o.devices || [o.device || 0]
     this.mode = o.mode || 'batched'
     this.patches = o.patches !== false
-    // diffs: 'ops' (Automerge's per-op sequence in application order) or 'net' (the diffs that
-    // take the previous patch's document to this one)
+    // diffs: 'ops' (Automerge's per-op sequence in application order, replayed on the host), 'device'
+    // (the same sequence rendered from the device's per-op diff rows: HM_DOCSET_DEVICE_DIFFS) or 'net'
+    // (the diffs that take the previous patch's document to this one)
     this.diffs = o.diffs || 'ops'
     this.docsets = this.devices.map((d) => addon.docsetCreate(d, o.threads || 0, this.patches, o.binary !== false,
-      this.diffs === 'net'))
+      this.diffs === 'net', this.diffs === 'device'))
     this.states = this.docsets.map(() => new Map())     // per docset: document id -> state
     this.byDocId = this.docsets.map(() => new Map())    // per docset: docId given to init -> its latest state
     this.queues = new Map()          // state -> FIFO of jobs
@@ -508,7 +509,7 @@ class GpuEngine {
 
   stats() {
     const t = { calls: 0, docs: 0, moves: 0, hitPatches: 0, fullPatches: 0, opPatches: 0, replayMismatch: 0,
-      incremental: 0, remerged: 0, handedBack: 0 }
+      incremental: 0, remerged: 0, handedBack: 0, deviceRounds: 0, diffCalls: 0, diffCallsRepeated: 0 }
     for (const ds of this.docsets) { const s = addon.docsetStats(ds); for (const k in t) t[k] += s[k] }
     t.dictClocks = CK.dict                      // (clocks in dictionary form: > 1024 actor ids seen)
     return t

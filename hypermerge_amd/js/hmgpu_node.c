@@ -629,17 +629,19 @@ static Docset *get_docset(napi_env env, napi_value v) {
     return d;
 }
 
-/* docsetCreate(device, threads, patches[, binary]) -> docset (binary: results in the HMP1 form) */
+/* docsetCreate(device, threads, patches[, binary[, netDiffs[, deviceDiffs]]]) -> docset (binary: results in
+ * the HMP1 form; deviceDiffs: HM_DOCSET_DEVICE_DIFFS, the rounds' diffs rendered from the device's rows) */
 static napi_value DocsetCreate(napi_env env, napi_callback_info info) {
-    napi_value argv[5];
-    size_t argc = 5;
+    napi_value argv[6];
+    size_t argc = 6;
     if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 3) {
         napi_throw_type_error(env, NULL, "missing arguments");
         return NULL;
     }
-    bool binary = false, net = false;
+    bool binary = false, net = false, device_diffs = false;
     if (argc >= 4) napi_get_value_bool(env, argv[3], &binary);
     if (argc >= 5) napi_get_value_bool(env, argv[4], &net);
+    if (argc >= 6) napi_get_value_bool(env, argv[5], &device_diffs);
     Docset *d = (Docset *)calloc(1, sizeof(Docset));
     hm_config cfg = {(int)get_u32(env, argv[0]), 0};
     int st = hm_engine_create(&cfg, &d->engine);
@@ -647,7 +649,7 @@ static napi_value DocsetCreate(napi_env env, napi_callback_info info) {
     bool patches = true;
     napi_get_value_bool(env, argv[2], &patches);
     hm_docset_config dc = {get_u32(env, argv[1]), (patches ? 0u : HM_DOCSET_NO_PATCHES) | (binary ? HM_DOCSET_BINARY : 0u) |
-                                              (net ? HM_DOCSET_NET_DIFFS : 0u)};
+                                              (net ? HM_DOCSET_NET_DIFFS : 0u) | (device_diffs ? HM_DOCSET_DEVICE_DIFFS : 0u)};
     st = hm_docset_create(d->engine, &dc, &d->ds);
     if (st) { napi_value r = throw_status(env, d->engine, st, "hm_docset_create"); hm_engine_destroy(d->engine); free(d); return r; }
     napi_value out;
@@ -1090,7 +1092,8 @@ static napi_value DocsetInfo(napi_env env, napi_callback_info info) {
 }
 
 /* docsetStats(docset) -> {calls, docs, moves, hitPatches, fullPatches, opPatches, replayMismatch, incremental,
- * remerged, handedBack} (the last three: document rounds by store route, hm_docset_routing) */
+ * remerged, handedBack, deviceRounds, diffCalls, diffCallsRepeated} (incremental .. handedBack: document rounds
+ * by store route, hm_docset_routing; the last three: hm_docset_diff_stats) */
 static napi_value DocsetStats(napi_env env, napi_callback_info info) {
     napi_value argv[1];
     if (!get_args(env, info, 1, argv)) return NULL;
@@ -1106,6 +1109,10 @@ static napi_value DocsetStats(napi_env env, napi_callback_info info) {
     hm_docset_routing(d->ds, r3);
     const char *rn[3] = {"incremental", "remerged", "handedBack"};
     for (int i = 0; i < 3; i++) { napi_value v; napi_create_double(env, (double)r3[i], &v); set(env, o, rn[i], v); }
+    uint64_t d4[4] = {0, 0, 0, 0};
+    hm_docset_diff_stats(d->ds, d4);
+    const char *dn[3] = {"deviceRounds", "diffCalls", "diffCallsRepeated"};
+    for (int i = 0; i < 3; i++) { napi_value v; napi_create_double(env, (double)d4[i], &v); set(env, o, dn[i], v); }
     return o;
 }
 

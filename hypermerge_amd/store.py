@@ -538,7 +538,7 @@ class DocStore:
                     "hm_store_op_diff_sizes")
         return cnt[:n], fl[:n], tot
 
-    def op_diffs(self, handles, frm, to, cap=None, lists=False):
+    def op_diffs(self, handles, frm, to, cap=None, lists=False, once=False):
         """hm_store_op_diffs: what each applied op of the history slices [frm[i], to[i]) of the documents
         `handles` (a handle may repeat) did: per make op a create row, per assign on a map / table
         register the register as it stands after that op.  Returns (rows OP_DIFF_DT, survivors
@@ -548,20 +548,29 @@ class DocStore:
         lists=True (hm_store_op_diffs_ex with HM_ODF_LISTS): list / text element assigns are answered
         as OD_ELEM_INSERT / OD_ELEM_SET / OD_ELEM_REMOVE rows, nothing is flagged, and the rows' index
         table ([rows] u32: the element's index at the moment of the op, NONE for the other rows) is
-        returned as a fifth element."""
+        returned as a fifth element.
+        once=True (HM_ODF_ONCE): one walk, no sizes asked first: cap (None: a row per request) is a
+        guess, and the call is repeated once with the sizes it reports when the guess was too small.
+        A request's rows then lie at ranges[i] in a block of their own (blocks in any order, gaps
+        between them), the tables returned are as long as the call's totals."""
         from .engine import COpDiffOut, OP_DIFF_DT
         hs, f, t = (np.ascontiguousarray(x, np.uint32) for x in (handles, frm, to))
         n = len(hs)
         assert len(f) == n and len(t) == n
         if cap is None:
-            cap = tuple(int(x) for x in self.op_diff_sizes(hs, f, t, lists)[2]) if n else (0, 0)
-        rows, surv = np.zeros(max(cap[0], 1), OP_DIFF_DT), np.zeros(max(cap[1], 1), SURV_RESULT_DT)
-        rng, fl = np.zeros((max(n, 1), 2), np.uint32), np.zeros(max(n, 1), np.uint32)
-        tot, index = np.zeros(2, np.uint64), np.zeros(max(cap[0], 1), np.uint32)
-        out = COpDiffOut(cap[0], cap[1], rows.ctypes.data, surv.ctypes.data, rng.ctypes.data, fl.ctypes.data)
-        self._check(self._L.hm_store_op_diffs_ex(self._h, n, _p(hs), _p(f), _p(t), ctypes.byref(out),
-                                                 _p(index) if lists else None, _p(tot), 1 if lists else 0),
-                    "hm_store_op_diffs")
+            cap = (n, n) if once else tuple(int(x) for x in self.op_diff_sizes(hs, f, t, lists)[2]) if n else (0, 0)
+        opts = (1 if lists else 0) | (2 if once else 0)
+        for attempt in range(2):
+            rows, surv = np.zeros(max(cap[0], 1), OP_DIFF_DT), np.zeros(max(cap[1], 1), SURV_RESULT_DT)
+            rng, fl = np.zeros((max(n, 1), 2), np.uint32), np.zeros(max(n, 1), np.uint32)
+            tot, index = np.zeros(2, np.uint64), np.zeros(max(cap[0], 1), np.uint32)
+            out = COpDiffOut(cap[0], cap[1], rows.ctypes.data, surv.ctypes.data, rng.ctypes.data, fl.ctypes.data)
+            st = self._L.hm_store_op_diffs_ex(self._h, n, _p(hs), _p(f), _p(t), ctypes.byref(out),
+                                              _p(index) if lists else None, _p(tot), opts)
+            if not (once and st == 34 and attempt == 0 and (int(tot[0]) > cap[0] or int(tot[1]) > cap[1])):
+                break
+            cap = (int(tot[0]), int(tot[1]))                  # HM_ERR_NOMEM: the sizes are known now
+        self._check(st, "hm_store_op_diffs")
         base = (rows[:int(tot[0])], surv[:int(tot[1])], rng[:n], fl[:n])
         return base + (index[:int(tot[0])],) if lists else base
 

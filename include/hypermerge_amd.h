@@ -652,8 +652,29 @@ int hm_op_diffs_host(hm_engine *e, const hm_batch *b, const hm_results *r, uint3
  * outside its document (HM_ERR_INVALID; _device: bad & 2).
  * The work memory of hm_op_diffs_device_ex is hm_op_diffs_work_bytes_ex(b, n, opts) bytes: with
  * HM_ODF_LISTS and HM_DOC_HAS_LISTS in b->doc_flags (0 = unknown counts as set) a wave's slice is
- * sized for the order phase as well. */
+ * sized for the order phase as well.
+ *
+ * HM_ODF_ONCE (hm_store_op_diffs_ex only; every other call of this group answers HM_ERR_INVALID,
+ * hm_op_diffs_work_bytes_ex 0): one walk instead of count, scan and fill, for a caller that guesses the
+ * table sizes and grows them.  out_totals is required.  A request's rows take a block of the row
+ * table sized by the ops of its slice's applied changes (an upper bound: an ins emits no row, every
+ * other op at most one), a 64-op step's survivors a block of the survivor table; each block is
+ * reserved with one atomic add on the call's totals, so
+ *   out->range[2i ..] = (block, rows emitted): the blocks of different requests lie in whatever order
+ *                        the waves finished, a block's unused tail is a gap (rows nobody refers to);
+ *                        within a request the rows are in application order
+ *   surv_off             anywhere in the survivor table (absolute, as always)
+ *   out_totals           {sum of the row bounds, survivors}: at least hm_store_op_diff_sizes_ex's
+ *                        rows and at most the ops of the slices; exactly its survivors unless a
+ *                        request is flagged
+ * A block that does not fit under cap_rows / cap_surv is not written and the walk goes on: the totals
+ * are exact whatever the capacities, the call answers HM_ERR_NOMEM with them and no other output
+ * written, and the same call with tables of those sizes succeeds.  A request that turns out flagged
+ * (HM_OD_LISTS: without HM_ODF_LISTS, or without the hint) gets (block, 0); what its walk wrote is
+ * unreferenced and stays counted in the totals.  Rows, survivors, indices, counts and flags are
+ * otherwise those of the call without the bit. */
 #define HM_ODF_LISTS 1u
+#define HM_ODF_ONCE 2u
 #define HM_OD_ELEM_INSERT 3u
 #define HM_OD_ELEM_SET 4u
 #define HM_OD_ELEM_REMOVE 5u
@@ -799,6 +820,15 @@ typedef struct {
 #define HM_DOCSET_BINARY 2u       /* hm_docset_apply's text is the binary form below instead of JSON */
 #define HM_DOCSET_NET_DIFFS 4u    /* diffs take the previous patch's document to the new one (one per changed
                                      register) instead of Automerge's per-op sequence (the default) */
+#define HM_DOCSET_DEVICE_DIFFS 8u /* the per-op sequence of hm_docset_apply's rounds is rendered from the
+                                     device's op-diff rows (hm_store_op_diffs_ex with HM_ODF_LISTS |
+                                     HM_ODF_ONCE over each round's history slice, one call per stride
+                                     class, repeated once with the reported sizes when the guessed tables
+                                     are too small) instead of replayed on the host: the docset then
+                                     keeps no replay state (per-register survivors, list orders) and does
+                                     not read the registers back to check it.  Same patches, byte for
+                                     byte.  HM_ERR_INVALID together with HM_DOCSET_NET_DIFFS or
+                                     HM_DOCSET_NO_PATCHES. */
 /* Binary results ('HMP1', for a host that builds the patch objects itself instead of parsing
  * JSON; a call whose strings hold a lone surrogate falls back to the JSON form, first byte '{'):
  *   u32 header[8] = {0x31504D48, n_docs, n_strings, n_words, n_nums, blob_bytes, ascii, 0}
@@ -885,6 +915,10 @@ int hm_docset_view(hm_docset *ds, uint32_t doc, hm_text **out);
  * register, per-op patches, per-op replays whose registers differ from the device's merged state
  * (always 0 unless the renderer and the kernels disagree) */
 int hm_docset_stats(const hm_docset *ds, uint64_t *out8);
+/* HM_DOCSET_DEVICE_DIFFS: out4 = {document rounds rendered from device rows, hm_store_op_diffs_ex calls,
+ * calls repeated with larger tables, 0}; all 0 on a docset without the flag (whose per-op patches and
+ * replay checks hm_docset_stats counts; with the flag those two stay 0). */
+int hm_docset_diff_stats(const hm_docset *ds, uint64_t *out4);
 /* How the docset's stores merged its document rounds so far (hm_store_last_routing summed over
  * every submit): out3 = {incremental, re-merged, incremental handed back to the re-merge}. */
 int hm_docset_routing(const hm_docset *ds, uint64_t *out3);

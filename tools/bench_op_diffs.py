@@ -26,6 +26,13 @@ C5 store of --c5-docs documents and a C3 store of --c3-docs documents, fed the s
 read-back the route without the option does before its host replay (which still has no entry point
 of its own to time).
 
+--once adds, to whichever stores the other options chose, the one-walk call (HM_ODF_ONCE) on the same
+request sets, taken alternately with the two-pass legs:
+  once_*        hm_store_op_diffs_ex with the bit into tables of exactly the sizes it reports (a right
+                guess): staging + need + one walk, 64 B read back, the rows' and survivors' copy back
+  once_retry_*  the same after a call whose tables were too small (a wrong guess: two walks)
+`once_sets` records the one-walk totals (the row total is the ops of the slices, an upper bound).
+
 Prints one JSON line."""
 import argparse
 import ctypes
@@ -51,6 +58,7 @@ def main():
     ap.add_argument("--lists", action="store_true", help="C5 and C3 stores, element diffs answered")
     ap.add_argument("--c5-docs", type=int, default=100_000)
     ap.add_argument("--c3-docs", type=int, default=500)
+    ap.add_argument("--once", action="store_true", help="add the one-walk legs (HM_ODF_ONCE)")
     args = ap.parse_args()
     from hypermerge_amd import synth
     from hypermerge_amd.engine import Engine
@@ -102,7 +110,7 @@ def run(args, eng, b, opts, note):
     sets = {"full": (np.zeros(n, np.uint32), hist_len.copy()), "last": (before, hist_len.copy())}
     L, p = st._L, lambda a: a.ctypes.data      # noqa: E731
     out, legs = {}, []
-    keep = []
+    keep, keep1 = [], []
     for name, (frm, to) in sets.items():
         cnt, fl, tot = st.op_diff_sizes(hs, frm, to, lists=bool(opts))
         tr, ts = int(tot[0]), int(tot[1])
@@ -134,6 +142,25 @@ def run(args, eng, b, opts, note):
         def read_history(frm=frm, to=to, off=off, hlog=hlog, had=had):
             assert L.hm_store_read_history(st._h, n, p(hs), p(frm), p(to), p(off), p(hlog), p(had)) == 0
         legs += [(f"sizes_{name}", sizes), (f"diffs_{name}", diffs), (f"read_history_{name}", read_history)]
+        if args.once:
+            t1 = np.zeros(2, np.uint64)
+            none = COpDiffOut(0, 0, None, None, p(rg), p(flg))
+            assert L.hm_store_op_diffs_ex(st._h, n, p(hs), p(frm), p(to), ctypes.byref(none), None, p(t1), opts | 2) == (34 if tr else 0)
+            o_r, o_s = int(t1[0]), int(t1[1])
+            out[name]["once_rows"], out[name]["once_survivors"] = o_r, o_s
+            rows1, surv1, index1 = np.zeros(max(o_r, 1), OP_DIFF_DT), np.zeros(max(o_s, 1), SURV_RESULT_DT), np.zeros(max(o_r, 1), np.uint32)
+            rg1, flg1 = np.zeros(2 * n, np.uint32), np.zeros(n, np.uint32)
+            o1 = COpDiffOut(o_r, o_s, p(rows1), p(surv1), p(rg1), p(flg1))
+            small = COpDiffOut(o_r // 2, o_s // 2, p(rows1), p(surv1), p(rg1), p(flg1))
+            keep1.append((rows1, surv1, index1, rg1, flg1, t1, o1, small, none))
+
+            def once(frm=frm, to=to, o1=o1, t1=t1, index1=index1):
+                assert L.hm_store_op_diffs_ex(st._h, n, p(hs), p(frm), p(to), ctypes.byref(o1), p(index1) if opts else None, p(t1), opts | 2) == 0
+
+            def once_retry(frm=frm, to=to, o1=o1, small=small, t1=t1, index1=index1):
+                assert L.hm_store_op_diffs_ex(st._h, n, p(hs), p(frm), p(to), ctypes.byref(small), p(index1) if opts else None, p(t1), opts | 2) == 34
+                assert L.hm_store_op_diffs_ex(st._h, n, p(hs), p(frm), p(to), ctypes.byref(o1), p(index1) if opts else None, p(t1), opts | 2) == 0
+            legs += [(f"once_{name}", once), (f"once_retry_{name}", once_retry)]
     for _ in range(args.warmup):
         for _, f in legs:
             f()

@@ -2268,6 +2268,123 @@ int hm_docset_missing_changes(hm_docset *ds, uint32_t n, const uint32_t *docs, c
     }
 }
 
+int hm_docset_fields(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off, const char *actor_ids,
+                     const uint32_t *actor_off, const double *seqs, const uint32_t *field_off, const char *names,
+                     const uint32_t *name_off, hm_text **out) {
+    if (!ds || !out || (n && (!docs || !entry_off || !field_off))) return HM_ERR_INVALID;
+    *out = nullptr;
+    Busy b(ds);
+    if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
+    try {
+        int rc = check_request(ds, n, docs, entry_off);
+        if (rc) return rc;
+        for (uint32_t i = 0; i < n; i++)
+            if (field_off[i + 1] < field_off[i]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "field_off must not decrease");
+        if (n && entry_off[n] - entry_off[0] && (!actor_ids || !actor_off || !seqs)) return HM_ERR_INVALID;
+        if (n && field_off[n] - field_off[0] && (!names || !name_off)) return HM_ERR_INVALID;
+        for (uint32_t i = 0; i < n; i++) {
+            for (uint32_t k = entry_off[i]; k < entry_off[i + 1]; k++)
+                if (actor_off[k + 1] < actor_off[k]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease");
+            for (uint32_t f = 2 * field_off[i]; f < 2 * field_off[i + 1]; f++)
+                if (name_off[f + 1] < name_off[f]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "name_off must not decrease");
+        }
+        // a request with no device rows: every field empty
+        auto plain = [&](uint32_t i, bool ready) {
+            std::string o = ready ? "{\"ready\":true,\"fields\":[" : "{\"ready\":false,\"fields\":[";
+            for (uint32_t f = field_off[i]; f < field_off[i + 1]; f++) { if (f > field_off[i]) o += ','; o += "[]"; }
+            return o + "]}";
+        };
+        std::vector<std::string> js(n);
+        for (uint32_t i = 0; i < n; i++) {                       // (a document not placed yet: nothing applied)
+            if (ds->doc(docs[i]).cls != NO_CLASS) continue;
+            bool ready = true;
+            for (uint32_t k = entry_off[i]; k < entry_off[i + 1]; k++) ready = ready && seq_u32(seqs[k]) == 0u;
+            js[i] = plain(i, ready);
+        }
+        for (uint32_t c = 0; c < N_CLASS; c++) {
+            std::vector<uint32_t> idx, hs, eoff(1, 0), eseq, foff(1, 0), freg, fmap;
+            std::vector<uint16_t> eact;
+            for (uint32_t i = 0; i < n; i++) {
+                const DocSt &d = ds->doc(docs[i]);
+                if (d.cls != c) continue;
+                const size_t e_keep = eact.size();
+                bool ready = true;
+                for (uint32_t k = entry_off[i]; k < entry_off[i + 1]; k++) {
+                    const uint32_t a = d.actors.find(actor_ids + actor_off[k], actor_off[k + 1] - actor_off[k], 0);
+                    const uint32_t q = seq_u32(seqs[k]);
+                    if (a == HM_NONE || a >= d.rank_of.size()) { ready = ready && q == 0u; continue; }   // (an actor never seen)
+                    eact.push_back(d.rank_of[a]);
+                    eseq.push_back(q);
+                }
+                if (!ready) { eact.resize(e_keep); eseq.resize(e_keep); js[i] = plain(i, false); continue; }
+                idx.push_back(i); hs.push_back(d.handle);
+                eoff.push_back((uint32_t)eact.size());
+                for (uint32_t f = field_off[i]; f < field_off[i + 1]; f++) {
+                    const uint32_t *no = name_off + 2 * (size_t)f;
+                    const uint32_t obj = d.objs.find(names + no[0], no[1] - no[0], 0);
+                    const uint32_t reg = obj == HM_NONE ? HM_NONE : d.regs.find(names + no[1], no[2] - no[1], obj);
+                    fmap.push_back(reg == HM_NONE ? HM_NONE : (uint32_t)freg.size());     // (unknown: an empty field, not sent)
+                    if (reg != HM_NONE) freg.push_back(reg);
+                }
+                foff.push_back((uint32_t)freg.size());
+            }
+            if (idx.empty()) continue;
+            const uint32_t k = (uint32_t)idx.size();
+            std::vector<uint32_t> flags(k), rng(2 * freg.size() + 2);
+            std::vector<hm_field_op> rows(std::max<size_t>(64, 2 * freg.size()));
+            uint32_t total = 0;
+            eact.push_back(0); eseq.push_back(0); freg.push_back(0);             // (never empty tables)
+            rc = hm_store_fields(ds->stores[c], k, hs.data(), eoff.data(), eact.data(), eseq.data(), foff.data(), freg.data(),
+                                 flags.data(), nullptr, rng.data(), rows.data(), (uint32_t)rows.size(), &total);
+            if (rc == HM_ERR_NOMEM && total > rows.size()) {      // (the guess was too small: now with the reported size)
+                rows.resize(total);
+                rc = hm_store_fields(ds->stores[c], k, hs.data(), eoff.data(), eact.data(), eseq.data(), foff.data(), freg.data(),
+                                     flags.data(), nullptr, rng.data(), rows.data(), total, &total);
+            }
+            if (rc) return rc;
+            size_t fm = 0;
+            for (uint32_t j = 0; j < k; j++) {
+                const uint32_t i = idx[j];
+                const DocSt &d = ds->doc(docs[i]);
+                if (flags[j] & HM_FLD_BAD_ROWS) return hm_engine_fail(ds->e, HM_ERR_INVALID, "a survivor outside its document's changes");
+                std::string &o = js[i];
+                o = (flags[j] & HM_FLD_NOT_READY) ? "{\"ready\":false,\"fields\":[" : "{\"ready\":true,\"fields\":[";
+                for (uint32_t f = field_off[i]; f < field_off[i + 1]; f++, fm++) {
+                    if (f > field_off[i]) o += ',';
+                    o += '[';
+                    const uint32_t g = fmap[fm];
+                    for (uint32_t r = 0; g != HM_NONE && r < rng[2 * g + 1]; r++) {
+                        const hm_field_op &p = rows[rng[2 * g] + r];
+                        if (r) o += ',';
+                        o += p.action == HM_LINK ? "{\"action\":\"link\",\"value\":" : "{\"action\":\"set\",\"value\":";
+                        const uint32_t id = (uint32_t)p.value;
+                        switch (p.vtag) {
+                        case HM_V_FALSE: o += "false"; break;
+                        case HM_V_TRUE: o += "true"; break;
+                        case HM_V_INT: case HM_V_FLOAT: jnum(o, p.vtag, p.value); break;
+                        case HM_V_STR: if (id < d.strs.size()) jstr(o, d.strs.ptr(id), d.strs.len(id)); else o += "null"; break;
+                        case HM_V_OBJ: if (id < d.objs.size()) jstr(o, d.objs.ptr(id), d.objs.len(id)); else o += "null"; break;
+                        default: o += "null";
+                        }
+                        if (p.datatype == HM_DT_COUNTER) o += ",\"datatype\":\"counter\"";
+                        else if (p.datatype == HM_DT_TIMESTAMP) o += ",\"datatype\":\"timestamp\"";
+                        o += ",\"actor\":";
+                        if (p.actor < d.by_rank.size()) { const uint32_t a = d.by_rank[p.actor]; jstr(o, d.actors.ptr(a), d.actors.len(a)); }
+                        else o += "null";
+                        o += ",\"seq\":" + std::to_string(p.seq) + (p.covered ? ",\"covered\":true}" : ",\"covered\":false}");
+                    }
+                    o += ']';
+                }
+                o += "]}";
+            }
+        }
+        *out = json_array(js);
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_fields");
+    }
+}
+
 int hm_docset_materialize(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, const uint32_t *entry_off,
                           const char *actor_ids, const uint32_t *actor_off, const double *seqs, hm_text **out) {
     if (!ds || !out || (n && !docs)) return HM_ERR_INVALID;

@@ -17,6 +17,7 @@
 #include "engine_internal.h"
 #include "waiting_kernels.h"
 #include "changes_kernels.h"
+#include "field_kernels.h"
 #include "past_kernels.h"
 #include "op_diff_kernels.h"
 
@@ -768,6 +769,120 @@ int hm_missing_changes_host(hm_engine *e, const hm_batch *hb, const hm_results *
         return HM_OK;
     } catch (...) {
         return fail(e, HM_ERR_DEVICE, "exception in hm_missing_changes_host");
+    }
+}
+
+static int check_fields_tables(hm_engine *e, const hm_batch *b, const hm_results *r) {
+    if (b->n_ops && !b->ops) return fail(e, HM_ERR_INVALID, "row table missing");
+    if (!r->docs || !r->clock || (b->n_changes && (!r->hist || !r->all_deps)) || (b->n_regs && !r->regs) || (b->n_ops && !r->surv))
+        return fail(e, HM_ERR_INVALID, "hm_fields needs the results' docs, clock, hist, all_deps, regs and surv tables");
+    return HM_OK;
+}
+
+int hm_fields_device(hm_engine *e, const hm_batch *b, const hm_results *r, const uint32_t *entry_off,
+                     const uint16_t *entry_actor, const uint32_t *entry_seq, uint32_t n_entries,
+                     const uint32_t *field_off, const uint32_t *field_reg, uint32_t n_fields,
+                     uint32_t *out_flags, uint32_t *out_closure, uint32_t *out_range, hm_field_op *out_rows,
+                     uint32_t cap, uint32_t *out_total, uint32_t *out_bad, void *stream) {
+    try {
+        if (!e || !r) return HM_ERR_INVALID;
+        int st = check_waiting_batch(e, b);
+        if (st) return st;
+        if (!b->n_docs) return HM_OK;
+        if (!entry_off || !field_off || !out_flags || !out_total || !out_bad || (cap && !out_rows) ||
+            (n_entries && (!entry_actor || !entry_seq)) || (n_fields && (!field_reg || !out_range)))
+            return fail(e, HM_ERR_INVALID, "hm_fields: a request table or an output missing");
+        if ((st = check_fields_tables(e, b, r))) return st;
+        HIPCHK(e, hipSetDevice(e->device));
+        FieldArgs A = {};
+        A.n = b->n_docs; A.src = batch_source(b, r);
+        A.regs = r->regs; A.surv = r->surv; A.lim_r = b->n_regs;
+        A.entry_off = entry_off; A.entry_actor = entry_actor; A.entry_seq = entry_seq; A.n_entries = n_entries;
+        A.field_off = field_off; A.field_reg = field_reg; A.n_fields = n_fields;
+        A.out_flags = out_flags; A.out_closure = out_closure; A.out_range = out_range; A.out_rows = out_rows; A.cap = cap;
+        A.total = out_total; A.bad = out_bad;
+        hipError_t hr = hm_launch_fields(A, stream ? (hipStream_t)stream : e->stream);
+        return hr == hipSuccess ? HM_OK : hip_fail(e, hr, "fields_kernel launch");
+    } catch (...) {
+        return fail(e, HM_ERR_DEVICE, "exception in hm_fields_device");
+    }
+}
+
+int hm_fields_host(hm_engine *e, const hm_batch *hb, const hm_results *hr, const uint32_t *entry_off,
+                   const uint16_t *entry_actor, const uint32_t *entry_seq, const uint32_t *field_off,
+                   const uint32_t *field_reg, uint32_t *out_flags, uint32_t *out_closure, uint32_t *out_range,
+                   hm_field_op *out_rows, uint32_t cap, uint32_t *out_total) {
+    try {
+        if (!e || !hr || !out_total) return HM_ERR_INVALID;
+        int st = check_waiting_batch(e, hb);
+        if (st) return st;
+        *out_total = 0;
+        if (!hb->n_docs) return HM_OK;
+        if (!entry_off || !field_off || !out_flags || (cap && !out_rows))
+            return fail(e, HM_ERR_INVALID, "hm_fields: a request table or an output missing");
+        if ((st = check_fields_tables(e, hb, hr))) return st;
+        const size_t S = hb->a_stride, n = hb->n_docs;
+        if (entry_off[0] || field_off[0]) return fail(e, HM_ERR_INVALID, "entry_off and field_off must start at 0");
+        for (size_t i = 0; i < n; i++) {
+            if (entry_off[i + 1] < entry_off[i]) return fail(e, HM_ERR_INVALID, "entry_off must not decrease");
+            if (field_off[i + 1] < field_off[i]) return fail(e, HM_ERR_INVALID, "field_off must not decrease");
+        }
+        const size_t ne = entry_off[n], nf = field_off[n];
+        if ((ne && (!entry_actor || !entry_seq)) || (nf && (!field_reg || !out_range)))
+            return fail(e, HM_ERR_INVALID, "hm_fields: a request table or an output missing");
+        HIPCHK(e, hipSetDevice(e->device));
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        // inputs 0..13, then counters (total, bad), flags, ranges, closure rows, rows
+        const size_t sz[19] = {n * sizeof(hm_doc_row), hb->n_changes * sizeof(hm_change_row), hb->n_ops * sizeof(hm_op_row),
+                               n * sizeof(hm_doc_result), n * S * 4, (size_t)hb->n_changes * 4, (size_t)hb->n_changes * S * 4,
+                               hb->n_regs * sizeof(hm_reg_result), hb->n_ops * sizeof(hm_surv_result),
+                               (n + 1) * 4, ne * 2, ne * 4, (n + 1) * 4, nf * 4,
+                               8, n * 4, nf * 8, out_closure ? n * S * 4 : 0, (size_t)cap * sizeof(hm_field_op)};
+        const void *src[14] = {hb->docs, hb->changes, hb->ops, hr->docs, hr->clock, hr->hist, hr->all_deps, hr->regs, hr->surv,
+                               entry_off, entry_actor, entry_seq, field_off, field_reg};
+        size_t off[19], total = 0;
+        for (int i = 0; i < 19; i++) { off[i] = total; total += al(sz[i] ? sz[i] : 1); }
+        char *base = nullptr;
+        if (hipMalloc((void **)&base, total) != hipSuccess) return fail(e, HM_ERR_NOMEM, "hipMalloc fields staging");
+        hipStream_t s = e->stream;
+        hm_batch b = *hb;
+        b.docs = (const hm_doc_row *)(base + off[0]); b.changes = (const hm_change_row *)(base + off[1]);
+        b.deps = nullptr; b.n_deps = 0; b.ops = (const hm_op_row *)(base + off[2]);
+        hm_results d = {};
+        d.docs = (hm_doc_result *)(base + off[3]); d.clock = (uint32_t *)(base + off[4]); d.hist = (int32_t *)(base + off[5]);
+        d.all_deps = (uint32_t *)(base + off[6]); d.regs = (hm_reg_result *)(base + off[7]); d.surv = (hm_surv_result *)(base + off[8]);
+        uint32_t cnt[2] = {0, 0};
+        hipError_t r = hipMemsetAsync(base + off[14], 0, 8, s);
+        for (int i = 0; i < 14 && r == hipSuccess; i++)
+            if (sz[i]) r = hipMemcpyAsync(base + off[i], src[i], sz[i], hipMemcpyHostToDevice, s);
+        int rc = HM_OK;
+        if (r == hipSuccess)
+            rc = hm_fields_device(e, &b, &d, (const uint32_t *)(base + off[9]), (const uint16_t *)(base + off[10]),
+                                  (const uint32_t *)(base + off[11]), (uint32_t)ne, (const uint32_t *)(base + off[12]),
+                                  (const uint32_t *)(base + off[13]), (uint32_t)nf, (uint32_t *)(base + off[15]),
+                                  out_closure ? (uint32_t *)(base + off[17]) : nullptr, (uint32_t *)(base + off[16]),
+                                  (hm_field_op *)(base + off[18]), cap, (uint32_t *)(base + off[14]),
+                                  (uint32_t *)(base + off[14] + 4), s);
+        if (rc == HM_OK && r == hipSuccess) r = hipMemcpyAsync(cnt, base + off[14], 8, hipMemcpyDeviceToHost, s);
+        if (rc == HM_OK && r == hipSuccess) r = hipStreamSynchronize(s);
+        if (rc == HM_OK && r == hipSuccess && !cnt[1]) {
+            r = hipMemcpy(out_flags, base + off[15], sz[15], hipMemcpyDeviceToHost);
+            if (r == hipSuccess && nf) r = hipMemcpy(out_range, base + off[16], sz[16], hipMemcpyDeviceToHost);
+            if (r == hipSuccess && out_closure) r = hipMemcpy(out_closure, base + off[17], sz[17], hipMemcpyDeviceToHost);
+            if (r == hipSuccess && cnt[0] && cnt[0] <= cap)
+                r = hipMemcpy(out_rows, base + off[18], (size_t)cnt[0] * sizeof(hm_field_op), hipMemcpyDeviceToHost);
+        }
+        (void)hipFree(base);
+        if (rc != HM_OK) return rc;
+        if (r != hipSuccess) return hip_fail(e, r, "hm_fields_host");
+        if (cnt[1] & HM_FD_BAD_RANK) return fail(e, HM_ERR_INVALID, "entry actor rank outside a_stride");
+        if (cnt[1] & HM_FD_BAD_REPEAT) return fail(e, HM_ERR_INVALID, "actor rank repeated within a request");
+        if (cnt[1]) return fail(e, HM_ERR_INVALID, "bad entry_off or field_off");
+        *out_total = cnt[0];
+        if (cnt[0] > cap) return fail(e, HM_ERR_NOMEM, "cap below the rows of the fields");
+        return HM_OK;
+    } catch (...) {
+        return fail(e, HM_ERR_DEVICE, "exception in hm_fields_host");
     }
 }
 

@@ -41,6 +41,7 @@
 #include "store_kernels.h"
 #include "waiting_kernels.h"
 #include "changes_kernels.h"
+#include "field_kernels.h"
 #include "past_kernels.h"
 #include "op_diff_kernels.h"
 
@@ -1155,6 +1156,78 @@ int hm_store_missing_changes(hm_store *s, uint32_t n, const uint32_t *doc_handle
         return HM_OK;
     } catch (...) {
         return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_missing_changes");
+    }
+}
+
+int hm_store_fields(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *entry_off,
+                    const uint16_t *entry_actor, const uint32_t *entry_seq, const uint32_t *field_off,
+                    const uint32_t *field_reg, uint32_t *out_flags, uint32_t *out_closure, uint32_t *out_range,
+                    hm_field_op *out_rows, uint32_t cap, uint32_t *out_total) {
+    if (!s || !out_total || (n && (!doc_handles || !entry_off || !field_off || !out_flags)) || (cap && !out_rows)) return HM_ERR_INVALID;
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        *out_total = 0;
+        if (!n) return HM_OK;
+        if (entry_off[0]) return hm_engine_fail(s->e, HM_ERR_INVALID, "entry_off must start at 0");
+        if (field_off[0]) return hm_engine_fail(s->e, HM_ERR_INVALID, "field_off must start at 0");
+        for (uint32_t i = 0; i < n; i++) {
+            if (entry_off[i + 1] < entry_off[i]) return hm_engine_fail(s->e, HM_ERR_INVALID, "entry_off must not decrease");
+            if (field_off[i + 1] < field_off[i]) return hm_engine_fail(s->e, HM_ERR_INVALID, "field_off must not decrease");
+        }
+        const uint32_t ne = entry_off[n], nf = field_off[n];
+        if ((ne && (!entry_actor || !entry_seq)) || (nf && (!field_reg || !out_range))) return HM_ERR_INVALID;
+        const uint32_t S = s->S;
+        hipStream_t st = hm_engine_stream(s->e);
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t o_cnt = 0, o_h = 256, o_eo = o_h + al(4 * (size_t)n), o_ea = o_eo + al(4 * ((size_t)n + 1)),
+                     o_es = o_ea + al(2 * (size_t)ne + 2), o_fo = o_es + al(4 * (size_t)ne + 4), o_fr = o_fo + al(4 * ((size_t)n + 1)),
+                     o_fl = o_fr + al(4 * (size_t)nf + 4), o_rng = o_fl + al(4 * (size_t)n), o_cl = o_rng + al(8 * (size_t)nf + 8),
+                     o_rows = o_cl + (out_closure ? al(4 * (size_t)n * S) : 0), total = o_rows + al(sizeof(hm_field_op) * (size_t)cap + 8);
+        int rc = ensure_stage(s, total);
+        if (rc) return rc;
+        uint8_t *sp = s->stage.p;
+        SCHK(s, hipMemsetAsync(sp + o_cnt, 0, 8, st));        // (total, bad)
+        SCHK(s, hipMemcpyAsync(sp + o_h, doc_handles, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+        SCHK(s, hipMemcpyAsync(sp + o_eo, entry_off, 4 * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+        SCHK(s, hipMemcpyAsync(sp + o_fo, field_off, 4 * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+        if (ne) {
+            SCHK(s, hipMemcpyAsync(sp + o_ea, entry_actor, 2 * (size_t)ne, hipMemcpyHostToDevice, st));
+            SCHK(s, hipMemcpyAsync(sp + o_es, entry_seq, 4 * (size_t)ne, hipMemcpyHostToDevice, st));
+        }
+        if (nf) SCHK(s, hipMemcpyAsync(sp + o_fr, field_reg, 4 * (size_t)nf, hipMemcpyHostToDevice, st));
+        FieldArgs A = {};
+        A.n = n; A.src = store_source(s); A.src.handles = (const uint32_t *)(sp + o_h);
+        A.regs = s->regs; A.surv = s->surv; A.lim_r = s->cap_r;
+        A.entry_off = (const uint32_t *)(sp + o_eo); A.entry_actor = (const uint16_t *)(sp + o_ea);
+        A.entry_seq = (const uint32_t *)(sp + o_es); A.n_entries = ne;
+        A.field_off = (const uint32_t *)(sp + o_fo); A.field_reg = (const uint32_t *)(sp + o_fr); A.n_fields = nf;
+        A.out_flags = (uint32_t *)(sp + o_fl); A.out_closure = out_closure ? (uint32_t *)(sp + o_cl) : nullptr;
+        A.out_range = (uint32_t *)(sp + o_rng); A.out_rows = (hm_field_op *)(sp + o_rows); A.cap = cap;
+        A.total = (uint32_t *)(sp + o_cnt); A.bad = (uint32_t *)(sp + o_cnt + 4);
+        SCHK(s, hm_launch_fields(A, st));
+        // the per-request outputs travel with the counters; a small row table too, whole, so that the
+        // latency path (one request, a guessed table) waits for the device once
+        const bool whole = cap && sizeof(hm_field_op) * (size_t)cap <= 65536;
+        SCHK(s, hipMemcpyAsync(&s->h_cnt[8], sp + o_cnt, 8, hipMemcpyDeviceToHost, st));
+        SCHK(s, hipMemcpyAsync(out_flags, sp + o_fl, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+        if (nf) SCHK(s, hipMemcpyAsync(out_range, sp + o_rng, 8 * (size_t)nf, hipMemcpyDeviceToHost, st));
+        if (out_closure) SCHK(s, hipMemcpyAsync(out_closure, sp + o_cl, 4 * (size_t)n * S, hipMemcpyDeviceToHost, st));
+        if (whole) SCHK(s, hipMemcpyAsync(out_rows, sp + o_rows, sizeof(hm_field_op) * (size_t)cap, hipMemcpyDeviceToHost, st));
+        SCHK(s, hipStreamSynchronize(st));
+        const uint32_t tot = s->h_cnt[8], bad = s->h_cnt[9];
+        if (bad & HM_FD_BAD_HANDLE) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad handle");
+        if (bad & HM_FD_BAD_RANK) return hm_engine_fail(s->e, HM_ERR_INVALID, "entry actor rank outside the store's a_stride");
+        if (bad & HM_FD_BAD_REPEAT) return hm_engine_fail(s->e, HM_ERR_INVALID, "actor rank repeated within a request");
+        if (bad) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad entry_off or field_off");
+        *out_total = tot;
+        if (tot > cap) return hm_engine_fail(s->e, HM_ERR_NOMEM, "cap below the rows of the fields");
+        if (tot && !whole) {
+            SCHK(s, hipMemcpyAsync(out_rows, sp + o_rows, sizeof(hm_field_op) * (size_t)tot, hipMemcpyDeviceToHost, st));
+            SCHK(s, hipStreamSynchronize(st));
+        }
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_fields");
     }
 }
 

@@ -176,6 +176,42 @@ class DocSet:
         s, _ = _text(self._L, t)
         return json.loads(s)
 
+    def fields(self, docs: Sequence[int], clocks: Sequence[Dict[str, float]],
+               fields: Sequence[Sequence[Tuple[str, str]]]) -> List[Dict[str, Any]]:
+        """The fields proposed changes touch (hm_docset_fields): clocks[i] is the would-be change's
+        base clock {actorId: seq} for document docs[i] (base = {...deps}; base[actor] = seq - 1), read
+        in its insertion order; fields[i] a sequence of (object uuid, key) — an elemId as key for
+        list / text.  Per request {"ready": bool, "fields": [[op, ...], ...]}, a field's current ops
+        winner first, op = {"action", "value", "datatype"?, "actor", "seq", "covered"}."""
+        ids = np.ascontiguousarray(docs, np.uint32)
+        assert len(clocks) == len(ids) and len(fields) == len(ids)
+        eoff = np.zeros(len(ids) + 1, np.uint32)
+        foff = np.zeros(len(ids) + 1, np.uint32)
+        actors: List[bytes] = []
+        seqs: List[float] = []
+        names: List[bytes] = []
+        for i, (clock, fl) in enumerate(zip(clocks, fields)):
+            for a, q in clock.items():
+                actors.append(a.encode("utf-8", "surrogatepass"))
+                seqs.append(float(q))
+            eoff[i + 1] = len(actors)
+            for obj, key in fl:
+                names += [obj.encode("utf-8", "surrogatepass"), key.encode("utf-8", "surrogatepass")]
+            foff[i + 1] = len(names) // 2
+        aoff = np.zeros(len(actors) + 1, np.uint32)
+        np.cumsum([len(x) for x in actors], out=aoff[1:])
+        noff = np.zeros(len(names) + 1, np.uint32)
+        np.cumsum([len(x) for x in names], out=noff[1:])
+        adata = np.frombuffer(b"".join(actors) + b"\0", np.uint8)
+        ndata = np.frombuffer(b"".join(names) + b"\0", np.uint8)
+        sq = np.array(seqs + [0.0], np.float64)
+        t = ctypes.c_void_p()
+        self.engine._check(self._L.hm_docset_fields(self._h, len(ids), ids.ctypes.data, eoff.ctypes.data, adata.ctypes.data,
+                                                    aoff.ctypes.data, sq.ctypes.data, foff.ctypes.data, ndata.ctypes.data,
+                                                    noff.ctypes.data, ctypes.byref(t)), "hm_docset_fields")
+        s, _ = _text(self._L, t)
+        return json.loads(s)
+
     def materialize(self, docs: Sequence[int], history: Optional[Sequence[int]] = None,
                     clocks: Optional[Sequence[Dict[str, float]]] = None) -> List[Dict[str, Any]]:
         """Documents as they were (RepoBackend's MaterializeMsg, many per call): docs[i] at history

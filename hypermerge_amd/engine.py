@@ -43,7 +43,8 @@ EXPORTS = ("hm_abi_version", "hm_status_message", "hm_engine_create", "hm_engine
            "hm_docset_materialize", "hm_store_op_diff_sizes", "hm_store_op_diffs", "hm_op_diffs_work_bytes",
            "hm_op_diffs_device", "hm_op_diffs_host", "hm_docset_materialize_patch",
            "hm_store_op_diff_sizes_ex", "hm_store_op_diffs_ex", "hm_op_diffs_work_bytes_ex", "hm_op_diffs_device_ex",
-           "hm_op_diffs_host_ex", "hm_docset_materialize_patch_ex", "hm_docset_diff_stats")
+           "hm_op_diffs_host_ex", "hm_docset_materialize_patch_ex", "hm_docset_diff_stats",
+           "hm_store_fields", "hm_fields_device", "hm_fields_host", "hm_docset_fields")
 
 _lib = None
 
@@ -145,6 +146,11 @@ def lib():
             "hm_op_diffs_work_bytes_ex": [ctypes.POINTER(CBatch), u32, u32],
             "hm_op_diffs_device_ex": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, vp, vp, u32],
             "hm_op_diffs_host_ex": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, u32],
+            "hm_store_fields": [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp],
+            "hm_fields_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), vp, vp, vp, u32, vp, vp, u32,
+                                 vp, vp, vp, vp, u32, vp, vp, vp],
+            "hm_fields_host": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp],
+            "hm_docset_fields": [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         }
         for f, a in sig.items():
             getattr(L, f).argtypes = a
@@ -212,6 +218,33 @@ class COpDiffSummary(ctypes.Structure):
 
 
 assert ctypes.sizeof(COpDiffSummary) == 64 and OP_DIFF_DT.itemsize == 16
+
+
+FLD_NOT_READY, FLD_BAD_ROWS = 1, 2          # HM_FLD_* request flags
+FIELD_OP_DT = np.dtype([("op", "<u4"), ("seq", "<u4"), ("actor", "<u2"), ("action", "u1"), ("datatype", "u1"),
+                        ("vtag", "u1"), ("covered", "u1"), ("pad", "<u2"), ("value", "<u8")])   # struct hm_field_op
+assert FIELD_OP_DT.itemsize == 24
+
+
+def pack_fields(fields, n: int):
+    """Per request a sequence of registers as the C-ABI's field tables (field_off [n + 1] u32,
+    field_reg u32)."""
+    assert len(fields) == n, len(fields)
+    off = np.zeros(n + 1, np.uint32)
+    regs: list = []
+    for i, f in enumerate(fields):
+        regs.extend(int(r) for r in f)
+        off[i + 1] = len(regs)
+    return off, np.array(regs + [0], np.uint32)
+
+
+def unpack_fields(n, foff, flags, rng, rows):
+    """The tables of a fields call as, per request, (ready, [rows of each field])."""
+    out = []
+    for i in range(n):
+        fl = [rows[int(rng[f, 0]):int(rng[f, 0]) + int(rng[f, 1])].copy() for f in range(int(foff[i]), int(foff[i + 1]))]
+        out.append((not int(flags[i]) & FLD_NOT_READY, fl))
+    return out
 
 
 def pack_entries(have, n: int):
@@ -339,6 +372,45 @@ class Engine:
                                                       p(entry_actor), p(entry_seq), n_entries, flags, p(out_closure),
                                                       p(out_range), p(out_log), cap, p(out_total), p(out_bad), p(stream)),
                     "hm_missing_changes_device")
+
+    def fields(self, batch: Batch, results: Results, have, fields, cap: Optional[int] = None, closure: bool = False):
+        """hm_fields_host: the fields a proposed change touches, for every document of a merged batch.
+        have: per document the would-be change's base clock as pack_entries takes it (its deps in key
+        order with its own actor at seq - 1); fields: per document a sequence of registers.  Returns
+        per document (ready, [FIELD_OP_DT rows of each field, winner first]); closure=True: also the
+        [n_docs, a_stride] transitiveDeps rows.  A document whose merge threw offers nothing."""
+        n, S = batch.n_docs, batch.a_stride
+        off, ea, es = pack_entries(have, n)
+        foff, freg = pack_fields(fields, n)
+        nf = int(foff[-1])
+        flags = np.zeros(max(n, 1), np.uint32)
+        rng = np.zeros((nf + 1, 2), np.uint32)
+        clo = np.zeros((max(n, 1), S), np.uint32)
+        cb, cr = batch.c_struct(), results.c_struct()
+        grow, cap = cap is None, max(64, 2 * nf) if cap is None else cap
+        tot = ctypes.c_uint32()
+        rows = np.zeros(max(cap, 1), FIELD_OP_DT)
+        args = (self._h, ctypes.byref(cb), ctypes.byref(cr), off.ctypes.data, ea.ctypes.data, es.ctypes.data,
+                foff.ctypes.data, freg.ctypes.data, flags.ctypes.data, clo.ctypes.data, rng.ctypes.data)
+        st = self._L.hm_fields_host(*args, rows.ctypes.data, cap, ctypes.byref(tot))
+        if grow and st == 34 and tot.value > cap:     # HM_ERR_NOMEM: tot = the rows needed
+            cap = tot.value
+            rows = np.zeros(cap, FIELD_OP_DT)
+            st = self._L.hm_fields_host(*args, rows.ctypes.data, cap, ctypes.byref(tot))
+        self._check(st, "hm_fields_host")
+        out = unpack_fields(n, foff, flags, rng, rows)
+        return (out, clo[:n]) if closure else out
+
+    def fields_device(self, cbatch: CBatch, cresults: CResults, entry_off: int, entry_actor: int, entry_seq: int,
+                      n_entries: int, field_off: int, field_reg: int, n_fields: int, out_flags: int, out_closure: int,
+                      out_range: int, out_rows: int, cap: int, out_total: int, out_bad: int, stream: int = 0) -> None:
+        """The same with every table, the request arrays and the outputs in device memory (pointers;
+        out_total / out_bad are device words zeroed by the caller; enqueued, not synchronised)."""
+        p = lambda x: ctypes.c_void_p(x) if x else None
+        self._check(self._L.hm_fields_device(self._h, ctypes.byref(cbatch), ctypes.byref(cresults), p(entry_off),
+                                             p(entry_actor), p(entry_seq), n_entries, p(field_off), p(field_reg), n_fields,
+                                             p(out_flags), p(out_closure), p(out_range), p(out_rows), cap, p(out_total),
+                                             p(out_bad), p(stream)), "hm_fields_device")
 
     def materialize_device(self, cbatch: CBatch, cresults: CResults, n: int, doc_index: int, hist_len: int,
                            clock_rows: int, out: "CPastOut", out_summary: int, work: int, stream: int = 0) -> None:

@@ -340,6 +340,32 @@ function missingIndices(ds, ids, clocks, flags) {
 }
 const missingOf = (state, clock, flags) => missingIndices(state.ds, [state.id], [clock], flags)[0].map((i) => state.change(i))
 
+// the fields proposed changes touch, many documents of one docset in one device call: ids[i] with
+// the would-be change's base clock clocks[i] ({...deps, [actor]: seq - 1}, key order kept) and
+// fields[i] = [[objUuid, key], ...] (an elemId as key for list / text).  Per request {ready, fields:
+// [[{action, value, datatype?, actor, seq, covered}, ...], ...]}: each field's current ops, winner
+// first; covered = the would-be change is not concurrent with the op.  A request that is not
+// causally ready has every field empty.  Reads the rounds already applied.
+function fieldsMany(ds, ids, clocks, fields) {
+  const eoff = new Uint32Array(ids.length + 1), foff = new Uint32Array(ids.length + 1)
+  const actors = [], seqs = [], names = []
+  clocks.forEach((clock, i) => {
+    const c = plainClock(clock)
+    for (const a of Object.keys(c)) { actors.push(Buffer.from(a, 'utf8')); seqs.push(Number(c[a])) }
+    eoff[i + 1] = actors.length
+    for (const [obj, key] of fields[i]) names.push(Buffer.from(String(obj), 'utf8'), Buffer.from(String(key), 'utf8'))
+    foff[i + 1] = names.length / 2
+  })
+  const aoff = new Uint32Array(actors.length + 1), noff = new Uint32Array(names.length + 1)
+  actors.forEach((b, k) => { aoff[k + 1] = aoff[k] + b.length })
+  names.forEach((b, k) => { noff[k + 1] = noff[k] + b.length })
+  return JSON.parse(addon.docsetFields(ds, Uint32Array.from(ids), eoff, Buffer.concat(actors), aoff, Float64Array.from(seqs),
+    foff, Buffer.concat(names), noff))
+}
+// the base clock of a would-be change: JS object assignment order (the own actor keeps its place
+// when deps names it, else it goes last)
+const baseClock = (change) => Object.assign({}, change.deps || {}, { [change.actor]: change.seq - 1 })
+
 // documents as they were (RepoBackend's MaterializeMsg, many per device call): ids[i] at the history
 // length reqs[i].history (history.slice(0, n) replayed from Backend.init()) or at the clock
 // reqs[i].clock ({actorId: seq}: each actor's changes up to that seq, loadDocument's cursor).  The
@@ -489,6 +515,12 @@ class GpuEngine {
     // (the same sequence rendered from the device's per-op diff rows: HM_DOCSET_DEVICE_DIFFS) or 'net'
     // (the diffs that take the previous patch's document to this one)
     this.diffs = o.diffs || 'ops'
+    // undo: where an undoable local change's undo ops come from: 'view' (the whole merged document,
+    // read and parsed per request; every earlier op of a field counts as an ancestor of the request)
+    // or 'fields' (one device query for the fields the request touches, with Automerge's exact
+    // isConcurrent / causallyReady rule)
+    this.undo = o.undo || 'view'
+    if (this.undo !== 'view' && this.undo !== 'fields') throw new RangeError(`Unknown undo route: ${this.undo}`)
     this.docsets = this.devices.map((d) => addon.docsetCreate(d, o.threads || 0, this.patches, o.binary !== false,
       this.diffs === 'net', this.diffs === 'device'))
     this.states = this.docsets.map(() => new Map())     // per docset: document id -> state
@@ -547,6 +579,24 @@ class GpuEngine {
       if (!at.length) return
       const idx = missingIndices(ds, at.map((i) => states[i].id), at.map((i) => clocks[i]), flags)
       at.forEach((i, j) => { out[i] = idx[j].map((x) => states[i].change(x)) })
+    })
+    return out
+  }
+
+  // the fields proposed changes touch, many at once: reqs[i] = {state | id, change: {actor, seq, deps}
+  // | clock: the base clock itself, fields: [[objUuid, key], ...]} -> per request {ready, fields}
+  // as fieldsMany gives them (one device call per docset).  Reflects the rounds already applied:
+  // in 'async' mode await idle() first.
+  fields(reqs) {
+    const states = reqs.map((r) => r.state || this.stateOf(r.id))
+    const out = new Array(reqs.length)
+    this.docsets.forEach((ds, k) => {
+      const at = []
+      states.forEach((st, i) => { if (st.shard === k) at.push(i) })
+      if (!at.length) return
+      const got = fieldsMany(ds, at.map((i) => states[i].id), at.map((i) => (reqs[i].change ? baseClock(reqs[i].change) : reqs[i].clock || {})),
+        at.map((i) => reqs[i].fields || []))
+      at.forEach((i, j) => { out[i] = got[j] })
     })
     return out
   }
@@ -971,6 +1021,81 @@ function redoOpsOf(view, ops) {
   return out
 }
 
+// ---- the same from the device's answer for the fields the request touches (undo: 'fields') ----
+// An exact simulation of applyAssign's recordUndo over the request's ops: a request that is not
+// causally ready is queued and records nothing; a field's undo ops are its current ops in field
+// order (or a del); after a set / del / link the field keeps the earlier ops the request does not
+// cover plus the request's own earlier ops (ops of one change are concurrent with each other); an
+// inc adds only to the counter sets the request covers; after every assign the field is ordered by
+// sortBy(actor).reverse(): a stable ascending sort by actor id, then reversed.
+function distinctFields(ops, incs) {
+  const seen = new Set(), out = []
+  for (const op of ops || []) {
+    if (!UNDO_ACTIONS.has(op.action) || (op.action === 'inc' && !incs)) continue
+    const k = op.obj + '\u0000' + op.key
+    if (!seen.has(k)) { seen.add(k); out.push([op.obj, op.key]) }
+  }
+  return out
+}
+const bareOp = (o, obj, key) => {
+  const r = { action: o.action, obj, key, value: o.value }
+  if (o.datatype) r.datatype = o.datatype
+  return r
+}
+const byActorReversed = (ops) => ops.map((o, i) => [o, i])
+  .sort((x, y) => (x[0].actor < y[0].actor ? -1 : x[0].actor > y[0].actor ? 1 : x[1] - y[1])).map((x) => x[0]).reverse()
+
+function undoOpsExact(state, change) {
+  // (an inc's undo is its negation whatever the field holds; its field is asked for too, for the
+  // undo ops of a later set of the request on it, and for the request's readiness)
+  const wanted = distinctFields(change.ops, true)
+  if (!wanted.length) return []
+  const r = fieldsMany(state.ds, [state.id], [baseClock(change)], [wanted])[0]
+  if (!r.ready) return []
+  const sim = new Map()
+  wanted.forEach(([obj, key], i) => sim.set(obj + '\u0000' + key, r.fields[i].map((o) => Object.assign({ own: false }, o))))
+  const out = []
+  for (const op of change.ops || []) {
+    if (!UNDO_ACTIONS.has(op.action)) continue
+    const k = op.obj + '\u0000' + op.key
+    const cur = sim.get(k) || []
+    let next
+    if (op.action === 'inc') {
+      out.push({ action: 'inc', obj: op.obj, key: op.key, value: -op.value })
+      next = cur.map((o) => (o.action === 'set' && typeof o.value === 'number' && o.datatype === 'counter' && !o.own && o.covered
+        ? Object.assign({}, o, { value: o.value + op.value }) : o))
+    } else {
+      if (cur.length) for (const o of cur) out.push(bareOp(o, op.obj, op.key))
+      else out.push({ action: 'del', obj: op.obj, key: op.key })
+      next = cur.filter((o) => o.own || !o.covered)
+      if (op.action === 'set' || op.action === 'link') {
+        const o = { action: op.action, value: op.value, actor: change.actor, seq: change.seq, own: true, covered: false }
+        if (op.datatype) o.datatype = op.datatype
+        next.push(o)
+      }
+    }
+    sim.set(k, byActorReversed(next))
+  }
+  return out
+}
+
+// the redo ops of an undo request: the current ops of the fields its ops touch, read whether or not
+// the request is causally ready (an empty base clock is always ready)
+function redoOpsExact(state, ops) {
+  const wanted = distinctFields(ops)
+  const r = wanted.length ? fieldsMany(state.ds, [state.id], [{}], [wanted])[0] : { fields: [] }
+  const at = new Map()
+  wanted.forEach(([obj, key], i) => at.set(obj + '\u0000' + key, r.fields[i]))
+  const out = []
+  for (const op of ops) {
+    if (op.action === 'inc') { out.push({ action: 'inc', obj: op.obj, key: op.key, value: -op.value }); continue }
+    const cur = at.get(op.obj + '\u0000' + op.key) || []
+    if (cur.length) for (const o of cur) out.push(bareOp(o, op.obj, op.key))
+    else out.push({ action: 'del', obj: op.obj, key: op.key })
+  }
+  return out
+}
+
 function makeBackend(engine) {
   return {
     init: (docId) => engine.init(docId),
@@ -1136,10 +1261,11 @@ class DocBackend {
       const undoable = type === 'change' && change.undoable !== false
       if (undoable || type !== 'change') {
         // run when the request heads its document's queue (every earlier round applied)
+        const exact = this.engine.undo === 'fields'
         job.prepare = () => {
-          const view = JSON.parse(addon.docsetView(state.ds, state.id))
+          const view = exact ? null : JSON.parse(addon.docsetView(state.ds, state.id))
           if (type === 'change') {
-            const ops = undoOpsOf(view, change.ops)
+            const ops = exact ? undoOpsExact(state, change) : undoOpsOf(view, change.ops)
             after = () => {
               state.undoStack = state.undoStack.slice(0, state.undoPos).concat([ops])
               state.undoPos++
@@ -1151,7 +1277,7 @@ class DocBackend {
           if (type === 'undo') {
             ops = state.undoPos > 0 ? state.undoStack[state.undoPos - 1] : undefined
             if (!ops) throw new RangeError('Cannot undo: there is nothing to be undone')
-            const redo = redoOpsOf(view, ops)
+            const redo = exact ? redoOpsExact(state, ops) : redoOpsOf(view, ops)
             after = () => { state.undoPos--; state.redoStack = state.redoStack.concat([redo]) }
           } else {
             ops = state.redoStack[state.redoStack.length - 1]

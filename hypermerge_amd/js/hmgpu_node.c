@@ -1005,6 +1005,42 @@ static napi_value DocsetMissingChanges(napi_env env, napi_callback_info info) {
     return js;
 }
 
+/* docsetFields(docset, ids Uint32Array, entryOff Uint32Array [n + 1], actorIds Buffer, actorOff
+ * Uint32Array [entries + 1], seqs Float64Array (the would-be changes' base clocks, as
+ * docsetMissingChanges takes clocks), fieldOff Uint32Array [n + 1], names Buffer (per field the object
+ * uuid then the key, UTF-8, end to end), nameOff Uint32Array [2 * fields + 1]) -> JSON text, per
+ * request {"ready", "fields": [[{action, value, datatype?, actor, seq, covered}, ...], ...]}: the
+ * current ops of the fields a proposed change touches (refused while a call on the docset is in
+ * flight) */
+static napi_value DocsetFields(napi_env env, napi_callback_info info) {
+    napi_value argv[9];
+    if (!get_args(env, info, 9, argv)) return NULL;
+    Docset *d = get_docset(env, argv[0]);
+    if (!d) return NULL;
+    void *p[8]; size_t len[8];
+    for (int i = 0; i < 8; i++)
+        if (!get_bytes(env, argv[1 + i], &p[i], &len[i])) return NULL;
+    const uint32_t n = (uint32_t)(len[0] / 4);
+    const uint32_t *eoff = (const uint32_t *)p[1], *aoff = (const uint32_t *)p[3];
+    const uint32_t *foff = (const uint32_t *)p[5], *noff = (const uint32_t *)p[7];
+    const uint32_t zero[1] = {0};
+    int ok = len[1] / 4 == (size_t)n + 1 && len[5] / 4 == (size_t)n + 1;
+    const uint32_t ne = ok ? eoff[n] : 0, nf = ok ? foff[n] : 0;
+    ok = ok && eoff[0] == 0 && len[4] / 8 >= ne && (ne == 0 || (len[3] / 4 >= (size_t)ne + 1 && aoff[ne] <= len[2]));
+    ok = ok && foff[0] == 0 && (nf == 0 || (len[7] / 4 >= 2 * (size_t)nf + 1 && noff[2 * (size_t)nf] <= len[6]));
+    if (!ok) { napi_throw_type_error(env, NULL, "docsetFields: table lengths do not agree"); return NULL; }
+    hm_text *t = NULL;
+    int st = hm_docset_fields(d->ds, n, (const uint32_t *)p[0], eoff, p[2] ? (const char *)p[2] : "", ne ? aoff : zero,
+                              ne ? (const double *)p[4] : NULL, foff, p[6] ? (const char *)p[6] : "", nf ? noff : zero, &t);
+    if (st) return throw_status(env, d->engine, st, "hm_docset_fields");
+    size_t tl = 0;
+    const char *s = hm_text_data(t, &tl);
+    napi_value js;
+    napi_create_string_utf8(env, s, tl, &js);
+    hm_text_free(t);
+    return js;
+}
+
 /* docsetMaterialize(docset, ids Uint32Array, histLen Uint32Array | null, entryOff Uint32Array [n + 1] | null,
  * actorIds Buffer, actorOff Uint32Array [entries + 1], seqs Float64Array) -> JSON text, per request
  * {"doc", "clock", "deps", "history", "view"}: the documents as they were at a history length, or at a
@@ -1339,7 +1375,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"docsetCreate", DocsetCreate}, {"docsetOpen", DocsetOpen}, {"docsetApply", DocsetApply}, {"docsetApplyPacked", DocsetApplyPacked},
         {"docsetHistoryPrefix", DocsetHistoryPrefix}, {"docsetClockUpdate", DocsetClockUpdate},
         {"docsetView", DocsetView}, {"docsetBlocked", DocsetBlocked}, {"docsetWaiting", DocsetWaiting},
-        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetMaterialize", DocsetMaterialize}, {"docsetMaterializePatch", DocsetMaterializePatch}, {"docsetMaterializePatchEx", DocsetMaterializePatchEx}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
+        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetFields", DocsetFields}, {"docsetMaterialize", DocsetMaterialize}, {"docsetMaterializePatch", DocsetMaterializePatch}, {"docsetMaterializePatchEx", DocsetMaterializePatchEx}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
         {"cursorsCreate", CursorsCreate}, {"cursorsReserve", CursorsReserve}, {"cursorsUpdate", CursorsUpdate},
         {"cursorsGet", CursorsGet}, {"cursorsEntry", CursorsEntry}, {"cursorsDocsWithActors", CursorsDocsWithActors},
         {"syncRanges", SyncRanges}, {"decodeBlocks", DecodeBlocks}, {"commCreateLocalDocsets", CommCreateLocalDocsets},

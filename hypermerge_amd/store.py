@@ -23,7 +23,7 @@ from .columnar import (ACTIONS, CHANGE_DT, DEP_DT, DOC_DT, DOC_RESULT_DT, OP_DT,
                        SURV_RESULT_DT, DATATYPES, DOC_HAS_COUNTERS, DOC_HAS_LISTS, DT_COUNTER, HEAD,
                        INC, INS, LINK, MAKE_LIST, MAKE_TEXT, NONE, ROOT_ID, SET, DEL, V_NULL, V_OBJ,
                        Batch, CBatch, Results, _value, content_key, js_key)
-from .engine import MC_ONLY_LISTED, MC_RAW, CPastOut, Engine, EngineError, lib, pack_entries
+from .engine import MC_ONLY_LISTED, MC_RAW, CPastOut, Engine, EngineError, lib, pack_entries, pack_fields, unpack_fields, FIELD_OP_DT
 
 
 class StringPool:
@@ -465,6 +465,64 @@ class DocStore:
     def changes_for_actor(self, h: int, actor: str, after: int = 0) -> List[int]:
         """Backend.getChangesForActor: the actor's applied changes with seq > after, history order."""
         return self.missing_changes([h], [{actor: after}], MC_RAW | MC_ONLY_LISTED)[0]
+
+    # -- the fields a proposed change touches (undo bookkeeping of applyLocalChange) ------------------
+    def fields_rows(self, handles, have, fields, cap: Optional[int] = None):
+        """hm_store_fields over rank entries and registers: `have` as engine.pack_entries takes it
+        (the would-be change's deps in key order with its own actor at seq - 1), fields: per request
+        a sequence of registers.  Returns (per request (ready, [FIELD_OP_DT rows of each field, winner
+        first]), the [n, S] transitiveDeps rows)."""
+        hs = np.ascontiguousarray(handles, np.uint32)
+        n = len(hs)
+        off, ea, es = pack_entries(have, n)
+        foff, freg = pack_fields(fields, n)
+        nf = int(foff[-1])
+        flags = np.zeros(max(n, 1), np.uint32)
+        rng = np.zeros((nf + 1, 2), np.uint32)
+        clo = np.zeros((max(n, 1), self.S), np.uint32)
+        tot = ctypes.c_uint32()
+        grow, cap = cap is None, max(64, 2 * nf) if cap is None else cap
+        rows = np.zeros(max(cap, 1), FIELD_OP_DT)
+        args = (self._h, n, _p(hs), _p(off), _p(ea), _p(es), _p(foff), _p(freg), _p(flags), _p(clo), _p(rng))
+        st = self._L.hm_store_fields(*args, _p(rows), cap, ctypes.byref(tot))
+        if grow and st == 34 and tot.value > cap:     # HM_ERR_NOMEM: tot = the rows needed
+            cap = tot.value
+            rows = np.zeros(cap, FIELD_OP_DT)
+            st = self._L.hm_store_fields(*args, _p(rows), cap, ctypes.byref(tot))
+        self._check(st, "hm_store_fields")
+        return unpack_fields(n, foff, flags, rng, rows), clo[:n]
+
+    def fields(self, handles, clocks, fields):
+        """The fields proposed changes touch, many requests per call: clocks[i] is the would-be
+        change's base clock {actorId: seq} for document handles[i] (base = {...deps}; base[actor] =
+        seq - 1), read in its insertion order; fields[i] a sequence of registers, each a number or
+        an (object uuid, key) pair (looked up, never interned: an unknown one is an empty field).  An actor the document
+        has never seen is dropped when its seq is 0 and makes the request not ready otherwise.  Per
+        request (ready, [per field its current ops, winner first, as dicts of op / action / datatype /
+        vtag / value / actor (id) / seq / covered])."""
+        have, sent, late = [], [], set()
+        for j, (h, clock) in enumerate(zip(handles, clocks)):
+            rank = {a: i for i, a in enumerate(self.enc[h].actors)}
+            if any(a not in rank and q > 0 for a, q in clock.items()):
+                late.add(j)
+                continue
+            have.append([(rank[a], q) for a, q in clock.items() if a in rank])
+            sent.append(j)
+        def reg_of(h, f):
+            if isinstance(f, tuple):
+                enc = self.enc[h]
+                o = enc.objs.get(f[0])
+                return 0xFFFFFFFF if o is None else enc.regs.get((o, f[1]), 0xFFFFFFFF)
+            return f
+        regs = [[reg_of(handles[j], f) for f in fields[j]] for j in sent]
+        got, _ = self.fields_rows([handles[j] for j in sent], have, regs) if sent else ([], None)
+        out = [(False, [[] for _ in fields[j]]) for j in range(len(handles))]
+        for j, (ready, fl) in zip(sent, got):
+            actors = self.enc[handles[j]].actors
+            out[j] = (ready, [[dict(op=int(r["op"]), action=int(r["action"]), datatype=int(r["datatype"]), vtag=int(r["vtag"]),
+                                    value=int(r["value"]), actor=actors[int(r["actor"])], seq=int(r["seq"]),
+                                    covered=bool(r["covered"])) for r in f] for f in fl])
+        return out
 
     # -- a document as it was (MaterializeMsg / loadDocument at a clock) ------------------------------
     def _selector(self, hs: np.ndarray, history, clocks):

@@ -690,6 +690,78 @@ int hm_op_diffs_host_ex(hm_engine *e, const hm_batch *b, const hm_results *r, ui
                         const uint32_t *from, const uint32_t *to, const hm_op_diff_out *out, uint32_t *out_index,
                         uint64_t *out_totals, uint32_t opts);
 
+/* The fields a proposed local change touches (the undo bookkeeping of Automerge 0.12
+ * applyLocalChange, src/DocBackend.ts:187-205: applyAssign's recordUndo reads fieldOps of every
+ * (obj, key) the request assigns and tests isConcurrent against the request), read off the resident
+ * tables without touching the document.
+ *   request   = a document, the would-be change's base clock as ordered (actor rank, seq) entries
+ *               — its deps in key order with its own actor at seq - 1: base = {...deps};
+ *               base[actor] = seq - 1, so the own actor keeps its place if deps names it and goes
+ *               last otherwise — and a list of registers
+ *   ready     = every entry has seq <= opSet.clock[actor] (causallyReady).  A request that is not
+ *               ready gets HM_FLD_NOT_READY and no rows (Automerge queues it: an empty undo list)
+ *   closure   = transitiveDeps(entries), exactly hm_store_missing_changes's fold (order dependent
+ *               when the entries are not causally closed): applyChange's allDeps of the request
+ *   per register, in request order: its current survivors, winner first then the conflicts
+ *               (fieldOps, the order of hm_reg_result / hm_surv_result); per survivor one hm_field_op:
+ *               the document-local op index, the op row's action (HM_SET | HM_LINK) and datatype, the
+ *               resolved vtag / value, its change's (actor rank, seq) and
+ *               covered = closure[actor] >= seq: the request is not concurrent with it, so a set /
+ *               del / link of the request removes it and an inc adds to it when it is a counter set
+ *   a register at or past the document's n_regs, or one never touched, answers zero rows.
+ *
+ * Requests i = 0..n-1: document doc_handles[i] (a handle may repeat), entries entry_off[i] ..
+ * entry_off[i+1]-1 (entry_off[0] = 0, not decreasing; a rank at most once per request), registers
+ * field_reg[field_off[i] .. field_off[i+1]-1] (field_off[0] = 0, not decreasing; a register may
+ * repeat).  out_flags [n] = HM_FLD_* per request (HM_FLD_BAD_ROWS: a survivor whose op lies in no
+ * change of the document, or a register row outside the tables — not a merge's tables; its row has
+ * actor 0xFFFF); out_closure (optional, [n*S]) = the closure row (zeros when not ready); out_range
+ * [2 * n_fields] = (first row, rows) per field, n_fields = field_off[n]; the requests' blocks lie in
+ * unspecified order, inside a block the rows are in field order, then survivor order.  *out_total =
+ * rows needed; HM_ERR_NOMEM when that exceeds cap (flags, closure rows, the ranges' counts and
+ * *out_total are still valid, out_rows is not; out_rows may be NULL when cap is 0).  HM_ERR_INVALID
+ * (the outputs' content is then unspecified, *out_total 0): a handle outside the store, a rank >=
+ * a_stride, a rank repeated within a request, bad entry_off / field_off.  No batch in flight.  n == 0
+ * launches nothing.  A call's rows stay below 2^32.  One kernel launch per call; the per-request
+ * outputs and a row table of at most 64 KiB come back with the counters (one wait for the device),
+ * a larger table's rows in a second copy. */
+typedef struct {          /* 24 B */
+    uint32_t op;          /* document-local op index, as hm_doc_log orders them */
+    uint32_t seq;         /* of the op's change */
+    uint16_t actor;       /* rank of the op's change */
+    uint8_t  action;      /* HM_SET | HM_LINK */
+    uint8_t  datatype;    /* HM_DT_* of the op row */
+    uint8_t  vtag;        /* HM_V_* of the resolved value (counters may turn INT -> FLOAT) */
+    uint8_t  covered;     /* 1: closure[actor] >= seq */
+    uint16_t pad;
+    uint64_t value;       /* resolved value (counter: base + causally-later incs) */
+} hm_field_op;
+#define HM_FLD_NOT_READY 1u
+#define HM_FLD_BAD_ROWS 2u
+int hm_store_fields(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *entry_off,
+                    const uint16_t *entry_actor, const uint32_t *entry_seq, const uint32_t *field_off,
+                    const uint32_t *field_reg, uint32_t *out_flags, uint32_t *out_closure, uint32_t *out_range,
+                    hm_field_op *out_rows, uint32_t cap, uint32_t *out_total);
+/* The same for the documents of a merged cold batch: request i = document i of b (n = b->n_docs), read
+ * from b's docs / changes / ops and r's docs / clock / hist / all_deps / regs / surv; a document whose
+ * status is not HM_OK offers nothing (no rows; ready exactly when every entry's seq is 0).  n_entries /
+ * n_fields = rows of the entry / field tables (= entry_off[n_docs] / field_off[n_docs]).
+ * _device: every table, the request arrays and the outputs are device memory, enqueued on `stream`
+ * (NULL = the engine's) without synchronising; *out_total and *out_bad are device words the caller
+ * zeroes first (*out_bad != 0 afterwards: 2 a rank >= a_stride, 4 a repeated rank, 8 bad entry_off,
+ * 16 bad field_off: the offsets are checked on the device; such a request has empty ranges); blocks
+ * are written only while first row + rows <= cap.
+ * _host: host tables in, host rows out (staged, synchronous), errors as hm_store_fields. */
+int hm_fields_device(hm_engine *e, const hm_batch *b, const hm_results *r, const uint32_t *entry_off,
+                     const uint16_t *entry_actor, const uint32_t *entry_seq, uint32_t n_entries,
+                     const uint32_t *field_off, const uint32_t *field_reg, uint32_t n_fields,
+                     uint32_t *out_flags, uint32_t *out_closure, uint32_t *out_range, hm_field_op *out_rows,
+                     uint32_t cap, uint32_t *out_total, uint32_t *out_bad, void *stream);
+int hm_fields_host(hm_engine *e, const hm_batch *b, const hm_results *r, const uint32_t *entry_off,
+                   const uint16_t *entry_actor, const uint32_t *entry_seq, const uint32_t *field_off,
+                   const uint32_t *field_reg, uint32_t *out_flags, uint32_t *out_closure, uint32_t *out_range,
+                   hm_field_op *out_rows, uint32_t cap, uint32_t *out_total);
+
 /* minimumClock row of a document (rank-indexed, 0 = absent); used for the
  * min_cmp of the next merges (Clock.cmp(DocBackend.clock, minimumClock)). */
 int hm_doc_set_min_clock(hm_store *s, uint32_t doc, const uint32_t *clock);
@@ -883,6 +955,22 @@ int hm_docset_waiting(hm_docset *ds, uint32_t n, const uint32_t *docs, hm_text *
 int hm_docset_missing_changes(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off,
                               const char *actor_ids, const uint32_t *actor_off, const double *seqs,
                               uint32_t flags, hm_text **out);
+/* the fields a proposed change touches (hm_store_fields per stride class, repeated once with the
+ * reported size when the guessed row table was too small): request i = document docs[i] (may repeat),
+ * the would-be change's base clock given as hm_docset_missing_changes takes a clock (base = {...deps};
+ * base[actor] = seq - 1, in key order) — an id the document has never seen is dropped when its seq is
+ * 0 and makes the request not ready otherwise — and the fields field_off[i] .. field_off[i+1]-1.
+ * Field f = two strings: the object uuid names[name_off[2f] .. name_off[2f+1]) and the key (an elemId
+ * for list / text) names[name_off[2f+1] .. name_off[2f+2]); they are looked up in the document's
+ * interners, nothing is interned: an unknown object or key is an empty field.  Result text = JSON
+ * array, per request {"ready": bool, "fields": [[op, ...], ...]}, a field's ops winner first, op =
+ * {"action": "set"|"link", "value": v[, "datatype": "counter"|"timestamp"], "actor": id, "seq": n,
+ * "covered": bool} (a link's value is the object uuid).  A request that is not ready has every field
+ * empty; a document not placed yet is ready exactly when every seq is 0.  Works whatever the
+ * docset's flags. */
+int hm_docset_fields(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off,
+                     const char *actor_ids, const uint32_t *actor_off, const double *seqs,
+                     const uint32_t *field_off, const char *names, const uint32_t *name_off, hm_text **out);
 /* documents as they were (hm_store_materialize per stride class): request i = document docs[i] (may
  * repeat) at history length hist_len[i], or at the clock given as hm_docset_missing_changes takes one
  * (entries entry_off[i] .. entry_off[i+1]-1 of actor id strings and seqs; an id the document has

@@ -847,6 +847,19 @@ int hm_store_inc_states(hm_store *s, uint32_t *out) {
     return HM_OK;
 }
 
+int hm_store_arena_info(hm_store *s, uint64_t out_cap[4], uint64_t out_used[4]) {
+    if (!s || !out_cap || !out_used) return HM_ERR_INVALID;
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    SCHK(s, hipSetDevice(hm_engine_device(s->e)));
+    hipStream_t st = hm_engine_stream(s->e);
+    // (the bump pointers through the page-locked stats block: no submit is using it here)
+    SCHK(s, hipMemcpyAsync(s->h_st->bump, s->st->bump, sizeof s->h_st->bump, hipMemcpyDeviceToHost, st));
+    SCHK(s, hipStreamSynchronize(st));
+    out_cap[0] = s->cap_c; out_cap[1] = s->cap_d; out_cap[2] = s->cap_o; out_cap[3] = s->cap_r;
+    for (int k = 0; k < 4; k++) out_used[k] = s->h_st->bump[k];
+    return HM_OK;
+}
+
 int hm_store_last_kernel_ms(const hm_store *s, float *out2) {
     if (!s || !out2) return HM_ERR_INVALID;
     out2[0] = s->last_ms[0]; out2[1] = s->last_ms[1];

@@ -53,6 +53,9 @@ struct PlanStats {
     unsigned long long tot_c, tot_d, tot_o, tot_r;
     unsigned long long bump[4];                // arena bump pointers (device-side segment allocation;
                                                //   last: one memset clears every per-phase field)
+    unsigned long long bump0[4];               // bump[] as plan_kernel found it (written on every plan attempt,
+                                               //   after the memset's range): alloc_kernel's room verdict reads
+                                               //   this copy, which no thread of that launch changes
     uint32_t n_valid, pad_v;                   // documents whose IncState can route a submit to the incremental
 };                                             //   kernels (HM_IST_VALID without NOCKEY): kept by every writer
 #define HM_IST_COUNTS(f) (((f) & (HM_IST_VALID | HM_IST_NOCKEY)) == HM_IST_VALID)

@@ -280,6 +280,9 @@ __global__ __launch_bounds__(PLAN_WG) void plan_kernel(PlanArgs a) {
         if (a.defer) a.defer[0] = 0;
         if (a.bail) a.bail[0] = 0;
         if (a.fail) a.fail[0] = 0;
+        // the arenas' fill as this plan attempt finds it (no kernel before alloc_kernel moves the
+        // bump pointers): the one value alloc_kernel's room verdict is taken from
+        for (int k = 0; k < 4; k++) a.st->bump0[k] = a.st->bump[k];
     }
     uint32_t err = 0;
     const uint32_t h = live ? a.handles[i] : 0u;
@@ -313,6 +316,10 @@ __global__ __launch_bounds__(PLAN_WG) void plan_kernel(PlanArgs a) {
             remapped |= y != x;
         }
     }
+    // A wave with a failing lane skips the rest: its documents add nothing to `need` and get no
+    // plan row.  That is safe only because st->err is then set before alloc_kernel starts, and a
+    // set err stops every thread of alloc_kernel (nothing reads need or the plan rows of a failed
+    // submit; the host fails it without compacting).
     const bool wave_ok = __ballot(err != 0) == 0;
     if (err) atomicOr(&a.st->err, err);                            // (rare) one atomic per failing lane
     if (wave_ok) {
@@ -455,11 +462,16 @@ __global__ __launch_bounds__(ALLOC_WG) void alloc_kernel(PlanArgs a) {
     const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
     const bool live = i < a.n;
     // the plan failed a check, or the arenas cannot take the growth: nothing moves (the host finds
-    // out from the stats; every later kernel of the submit sees route 0 and empty lists)
+    // out from the stats; every later kernel of the submit sees route 0 and empty lists).
+    // The verdict is uniform over the launch: err, need and bump0 (the bump pointers as plan_kernel
+    // found them) were written before this kernel started and no thread of it changes them — the
+    // live bump[] is advancing under the atomics below, so a verdict from it would differ between
+    // threads whenever the free rows lie in [need, 2 need).  So either every thread returns here,
+    // before the ballots and barriers, or none does.
     {
         const PlanStats *st = a.st;
-        const bool stop = st->err != 0 || st->bump[0] + st->need[0] > a.cap[0] || st->bump[1] + st->need[1] > a.cap[1] ||
-                          st->bump[2] + st->need[2] > a.cap[2] || st->bump[3] + st->need[3] > a.cap[3];
+        const bool stop = st->err != 0 || st->bump0[0] + st->need[0] > a.cap[0] || st->bump0[1] + st->need[1] > a.cap[1] ||
+                          st->bump0[2] + st->need[2] > a.cap[2] || st->bump0[3] + st->need[3] > a.cap[3];
         if (stop) {
             if (live) a.descs[i].inc = 0;
             if (i == 0 && st->err == 0) a.st->mx[1] = 1u;         // no room: the host compacts and plans again

@@ -250,6 +250,13 @@ class DocStore:
         self._check(self._L.hm_store_inc_states(self._h, _p(out)), "hm_store_inc_states")
         return int(out[0])
 
+    def arena(self) -> Dict[str, List[int]]:
+        """The four row arenas (changes, deps, ops, registers): capacities and bump pointers in
+        rows (hm_store_arena_info).  free = cap - used is what a submit's growth must fit."""
+        cap, used = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
+        self._check(self._L.hm_store_arena_info(self._h, _p(cap), _p(used)), "hm_store_arena_info")
+        return {"cap": [int(x) for x in cap], "used": [int(x) for x in used]}
+
     def last_kernel_ms(self) -> Dict[str, float]:
         """Device time of the last submit (HIP events): the incremental kernels and the re-merge."""
         out = np.zeros(2, np.float32)

@@ -362,6 +362,12 @@ int hm_store_last_kernel_ms(const hm_store *s, float *out2);
  * that builds or drops a state; a store with none plans its submits as whole re-merges and
  * launches no incremental kernel).  Synchronous; no batch may be in flight. */
 int hm_store_inc_states(hm_store *s, uint32_t *out);
+/* The store's four row arenas, in the order changes, deps, ops, registers: out_cap = their
+ * capacities, out_used = their bump pointers (rows handed out to segments, dead ones included),
+ * both in rows.  A submit whose growing segments fit the free rows of every arena allocates in
+ * place; one that does not compacts the store into larger arenas first.  Read-only (diagnostics,
+ * tests); synchronous; no batch may be in flight. */
+int hm_store_arena_info(hm_store *s, uint64_t out_cap[4], uint64_t out_used[4]);
 
 /* Diagnostics of check builds (libhmgpu_check.so, built beside libhmgpu.so): out2[0] = documents
  * whose next rows merge_small_kernel loaded asynchronously and re-read with counted loads,

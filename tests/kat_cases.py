@@ -180,6 +180,41 @@ CASES = [
                                          ins("L", "zzzz:9", 1), ins("L", f"{A}:3", 2), ins("L", f"{A}:2", 3),
                                          ins("L", "_head", 4), s(f"{A}:4", "v", obj="L"), d(f"{A}:1", obj="L"))],
      {"state": {"map": [["l", {"value": {"list": [{"value": "v"}]}}]]}}),
+    # counters away from the root map (A.2 does not look at where the register lives): an inc by a
+    # change that has seen the counter set adds, a concurrent one (cccc knows nothing) does not
+    ("counter_in_nested_map", [ch(A, 1, {}, mk("makeMap", "m1"), link("child", "m1"), s("n", 10, obj="m1", datatype="counter")),
+                               ch(B, 1, {A: 1}, inc("n", 5, obj="m1")), ch(Cc, 1, {}, inc("n", 100, obj="m1"))],
+     {"state": {"map": [["child", {"value": {"map": [["n", {"value": 15, "datatype": "counter"}]]}}]]}}),
+    # ... and on a list element: updateListElement after an inc finds the element in place ('set')
+    ("counter_on_list_element", [ch(A, 1, {}, mk("makeList", "L"), link("l", "L"),
+                                    ins("L", "_head", 1), s(f"{A}:1", 10, obj="L", datatype="counter"),
+                                    ins("L", f"{A}:1", 2), s(f"{A}:2", "x", obj="L")),
+                                 ch(B, 1, {A: 1}, inc(f"{A}:1", 5, obj="L")), ch(A, 2, {}, inc(f"{A}:1", -2, obj="L")),
+                                 ch(Cc, 1, {}, inc(f"{A}:1", 100, obj="L"))],
+     {"state": {"map": [["l", {"value": {"list": [{"value": 13, "datatype": "counter"}, {"value": "x"}]}}]]}}),
+    # an inc on an element that was inserted and never assigned leaves it hidden
+    ("inc_on_unassigned_element", [ch(A, 1, {}, mk("makeList", "L"), link("l", "L"), ins("L", "_head", 1),
+                                      ins("L", f"{A}:1", 2), s(f"{A}:2", "x", obj="L"), inc(f"{A}:1", 3, obj="L"))],
+     {"state": {"map": [["l", {"value": {"list": [{"value": "x"}]}}]]}}),
+    # objects under list elements: a map, and a list in a list, each made by another actor than the
+    # list's; bbbb's concurrent scalar on the same element is the conflict (cccc > bbbb wins)
+    ("objects_under_list_elements", [ch(A, 1, {}, mk("makeList", "L"), link("l", "L"), ins("L", "_head", 1),
+                                        ins("L", f"{A}:1", 2)),
+                                     ch(B, 1, {A: 1}, s(f"{A}:1", "scalar", obj="L")),
+                                     ch(Cc, 1, {A: 1}, mk("makeMap", "M"), link(f"{A}:1", "M", obj="L"), s("k", "v", obj="M"),
+                                        mk("makeList", "L2"), link(f"{A}:2", "L2", obj="L"),
+                                        ins("L2", "_head", 1), s(f"{Cc}:1", 7, obj="L2"))],
+     {"state": {"map": [["l", {"value": {"list": [
+         {"value": {"map": [["k", {"value": "v"}]]}, "conflicts": [[B, "scalar"]]},
+         {"value": {"list": [{"value": 7}]}}]}}]]}}),
+    # a table row as frontends write it (makeMap + link under a row id), a timestamp in it, and a
+    # scalar set straight on the table
+    ("table_row_and_timestamp", [ch(A, 1, {}, mk("makeTable", "T"), link("tab", "T"), mk("makeMap", "row"),
+                                    link("r-1", "row", obj="T"), s("at", 1500000000000, obj="row", datatype="timestamp")),
+                                 ch(B, 1, {A: 1}, s("note", 3, obj="T"))],
+     {"state": {"map": [["tab", {"value": {"table": [
+         ["note", {"value": 3}],
+         ["r-1", {"value": {"map": [["at", {"value": 1500000000000, "datatype": "timestamp"}]]}}]]}}]]}}),
 ]
 
 

@@ -239,8 +239,8 @@ class World:
 
 def plain(state: Any) -> Any:
     """render.doc_state's canonical form -> the plain JS value a frontend materializes."""
-    if isinstance(state, dict) and "map" in state:
-        return {k: plain(e["value"]) for k, e in state["map"]}
+    if isinstance(state, dict) and ("map" in state or "table" in state):
+        return {k: plain(e["value"]) for k, e in state.get("map", state.get("table", []))}
     if isinstance(state, dict) and ("list" in state or "text" in state):
         return [plain(e["value"]) for e in state.get("list", state.get("text", []))]
     return state

@@ -2467,49 +2467,81 @@ int hm_docset_materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs,
     return hm_docset_materialize_patch_ex(ds, n, docs, hist_len, 0u, out);
 }
 
+static int materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, const uint32_t *entry_off,
+                             const char *actor_ids, const uint32_t *actor_off, const double *seqs, uint32_t opts, hm_text **out);
+
 int hm_docset_materialize_patch_ex(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, uint32_t opts, hm_text **out) {
     if (!ds || !out || (n && (!docs || !hist_len)) || (opts & ~HM_ODF_LISTS)) return HM_ERR_INVALID;
+    return materialize_patch(ds, n, docs, hist_len, nullptr, nullptr, nullptr, nullptr, opts, out);
+}
+
+int hm_docset_materialize_patch_at(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off, const char *actor_ids,
+                                   const uint32_t *actor_off, const double *seqs, uint32_t opts, hm_text **out) {
+    if (!ds || !out || !entry_off || (n && !docs) || (opts & ~HM_ODF_LISTS)) return HM_ERR_INVALID;
+    return materialize_patch(ds, n, docs, nullptr, entry_off, actor_ids, actor_off, seqs, opts, out);
+}
+
+// hm_docset_materialize_patch_ex (a history length per request) and _at (entry_off != NULL: a clock per
+// request, as hm_docset_materialize takes it; the reply then carries "queued" too)
+static int materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, const uint32_t *entry_off,
+                             const char *actor_ids, const uint32_t *actor_off, const double *seqs, uint32_t opts, hm_text **out) {
     *out = nullptr;
     Busy b(ds);
     if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
     try {
-        int rc = check_request(ds, n, docs);
+        int rc = check_request(ds, n, docs, entry_off);
         if (rc) return rc;
+        if (entry_off && n && entry_off[n] - entry_off[0] && (!actor_ids || !actor_off || !seqs)) return HM_ERR_INVALID;
         if (n && !(ds->patches && ds->op_diffs))
             return hm_engine_fail(ds->e, HM_ERR_UNSUPPORTED, "hm_docset_materialize_patch renders per-op diffs: not with HM_DOCSET_NO_PATCHES / HM_DOCSET_NET_DIFFS");
         static const char TAIL[] = ",\"canUndo\":false,\"canRedo\":false,\"diffs\":[";
         std::vector<std::string> js(n);
         for (uint32_t i = 0; i < n; i++)                         // (a document not placed yet: Backend.init())
             if (ds->doc(docs[i]).cls == NO_CLASS)
-                js[i] = "{\"doc\":" + std::to_string(docs[i]) + ",\"history\":0,\"patch\":{\"clock\":{},\"deps\":{}" + TAIL + "]}}";
+                js[i] = "{\"doc\":" + std::to_string(docs[i]) + ",\"history\":0," + (entry_off ? "\"queued\":0," : "") +
+                        "\"patch\":{\"clock\":{},\"deps\":{}" + TAIL + "]}}";
         for (uint32_t c = 0; c < N_CLASS; c++) {
             const uint32_t S = STRIDES[c];
-            std::vector<uint32_t> idx, hs, hl;
+            std::vector<uint32_t> idx, hs, hl;                   // (hl: the history lengths, or the clock rows)
             for (uint32_t i = 0; i < n; i++) {
                 const DocSt &d = ds->doc(docs[i]);
                 if (d.cls != c) continue;
-                idx.push_back(i); hs.push_back(d.handle); hl.push_back(hist_len[i]);
+                idx.push_back(i); hs.push_back(d.handle);
+                if (hist_len) { hl.push_back(hist_len[i]); continue; }
+                hl.resize(hl.size() + S, 0u);
+                uint32_t *row = hl.data() + hl.size() - S;
+                for (uint32_t k = entry_off[i]; k < entry_off[i + 1]; k++) {
+                    if (actor_off[k + 1] < actor_off[k]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease");
+                    const uint32_t a = d.actors.find(actor_ids + actor_off[k], actor_off[k + 1] - actor_off[k], 0);
+                    if (a == HM_NONE || a >= d.rank_of.size() || d.rank_of[a] >= S) continue;   // (an actor the document has never seen)
+                    row[d.rank_of[a]] = seq_u32(seqs[k]);
+                }
             }
             if (idx.empty()) continue;
             const uint32_t k = (uint32_t)idx.size();
-            PastTables T;                                        // the prefix's clock and deps: its merge from Backend.init()
+            PastTables T;                                        // the selection's clock and deps: its merge from Backend.init()
             T.k = k; T.S = S;
-            if ((rc = hm_store_materialize_sized(ds->stores[c], k, hs.data(), hl.data(), nullptr, PastTables::alloc_heads, &T, nullptr))) return rc;
-            // the diffs: what each op of the prefix did, from the resident tables
-            const std::vector<uint32_t> from(k, 0u);
+            if ((rc = hm_store_materialize_sized(ds->stores[c], k, hs.data(), hist_len ? hl.data() : nullptr, hist_len ? nullptr : hl.data(),
+                                                 PastTables::alloc_heads, &T, nullptr))) return rc;
+            // the diffs: what each op of the selection did, from the resident tables
+            const std::vector<uint32_t> from(hist_len ? k : 0u, 0u);
             uint64_t tot[2] = {0, 0};
-            if ((rc = hm_store_op_diff_sizes_ex(ds->stores[c], k, hs.data(), from.data(), hl.data(), nullptr, nullptr, tot, opts))) return rc;
+            if ((rc = hist_len ? hm_store_op_diff_sizes_ex(ds->stores[c], k, hs.data(), from.data(), hl.data(), nullptr, nullptr, tot, opts)
+                               : hm_store_op_diff_sizes_at(ds->stores[c], k, hs.data(), hl.data(), nullptr, nullptr, tot, opts))) return rc;
             if (tot[0] > 0xFFFFFFFFull || tot[1] > 0xFFFFFFFFull) return hm_engine_fail(ds->e, HM_ERR_NOMEM, "a call's rows stay below 2^32");
             std::vector<hm_op_diff> rows(tot[0] + 1);
             std::vector<hm_surv_result> surv(tot[1] + 1);
             std::vector<uint32_t> range(2 * (size_t)k), flags(k), index(tot[0] + 1);   // (index: element rows, HM_ODF_LISTS)
             hm_op_diff_out po = {(uint32_t)tot[0], (uint32_t)tot[1], rows.data(), surv.data(), range.data(), flags.data()};
-            if ((rc = hm_store_op_diffs_ex(ds->stores[c], k, hs.data(), from.data(), hl.data(), &po, index.data(), nullptr, opts))) return rc;
+            if ((rc = hist_len ? hm_store_op_diffs_ex(ds->stores[c], k, hs.data(), from.data(), hl.data(), &po, index.data(), nullptr, opts)
+                               : hm_store_op_diffs_at(ds->stores[c], k, hs.data(), hl.data(), &po, index.data(), nullptr, opts))) return rc;
             for (uint32_t j = 0; j < k; j++) {
                 DocSt &d = ds->doc(docs[idx[j]]);
                 if (!d.ready) d.setup();
                 std::string &o = js[idx[j]];
-                o = "{\"doc\":" + std::to_string(docs[idx[j]]) + ",\"history\":" + std::to_string(T.res[j].hist_len) + ",\"patch\":";
+                o = "{\"doc\":" + std::to_string(docs[idx[j]]) + ",\"history\":" + std::to_string(T.res[j].hist_len);
+                if (!hist_len) o += ",\"queued\":" + std::to_string(T.res[j].n_queued);
+                o += ",\"patch\":";
                 if (flags[j] & HM_OD_LISTS) { o += "null,\"host\":true}"; continue; }   // (list / text elements: the caller replays)
                 if (T.res[j].status != HM_OK) { o += "null}"; continue; }
                 o += "{\"clock\":";

@@ -559,12 +559,14 @@ int hm_materialize_device(hm_engine *e, const hm_batch *b, const hm_results *r, 
 
 // the words of a wave's slice for any document of b: its launch hints, or the batch totals without them
 // (HM_ODF_LISTS: by the list formula when a document of b may carry HM_DOC_HAS_LISTS; doc_flags 0 = unknown)
-static unsigned long long od_batch_slice(const hm_batch *b, uint32_t opts) {
+// (at_clock: the clock forms, whose select phase keeps a bit per log change after the other words)
+static unsigned long long od_batch_slice(const hm_batch *b, uint32_t opts, bool at_clock = false) {
     const bool hints = b->max_ops || b->max_regs || b->max_objs;
     const bool lists = (opts & HM_ODF_LISTS) && (!b->doc_flags || (b->doc_flags & HM_DOC_HAS_LISTS));
     const unsigned long long ops = hints ? b->max_ops : b->n_ops, regs = hints ? b->max_regs : b->n_regs,
                              objs = hints ? (b->max_objs ? b->max_objs : 1u) : (unsigned long long)b->n_ops + b->n_docs;
-    const unsigned long long w = lists ? hm_od_slice_words_lists(ops, regs, objs) : hm_od_slice_words(ops, regs, objs);
+    const unsigned long long w = (lists ? hm_od_slice_words_lists(ops, regs, objs) : hm_od_slice_words(ops, regs, objs)) +
+                                 (at_clock ? hm_od_slice_words_clock(hints && b->max_changes ? b->max_changes : b->n_changes) : 0ull);
     return w ? w : 1ull;
 }
 // [counts 4n][offsets 4n][zero and flags 2n] u32, the scan's per-chunk words, then the waves' slices
@@ -580,6 +582,33 @@ size_t hm_op_diffs_work_bytes_ex(const hm_batch *b, uint32_t n, uint32_t opts) {
     return od_fixed_bytes(n) + (size_t)hm_od_waves(n, sw) * (size_t)sw * 4;
 }
 
+size_t hm_op_diffs_at_work_bytes(const hm_batch *b, uint32_t n, uint32_t opts) {
+    if (!b || !n || (opts & ~HM_ODF_LISTS)) return 0;
+    const unsigned long long sw = od_batch_slice(b, opts, true);
+    return od_fixed_bytes(n) + (size_t)hm_od_waves(n, sw) * (size_t)sw * 4;
+}
+
+static int op_diffs_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                           const uint32_t *from, const uint32_t *to, const uint32_t *clock_rows, const hm_op_diff_out *out,
+                           uint32_t *out_index, hm_op_diff_summary *out_summary, void *work, void *stream, uint32_t opts);
+static int op_diffs_host(hm_engine *e, const hm_batch *hb, const hm_results *hr, uint32_t n, const uint32_t *doc_index,
+                         const uint32_t *from, const uint32_t *to, const uint32_t *clock_rows, const hm_op_diff_out *out,
+                         uint32_t *out_index, uint64_t *out_totals, uint32_t opts);
+
+int hm_op_diffs_at_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                          const uint32_t *clock_rows, const hm_op_diff_out *out, uint32_t *out_index,
+                          hm_op_diff_summary *out_summary, void *work, void *stream, uint32_t opts) {
+    if (n && !clock_rows) return HM_ERR_INVALID;
+    return op_diffs_device(e, b, r, n, doc_index, nullptr, nullptr, clock_rows, out, out_index, out_summary, work, stream, opts);
+}
+
+int hm_op_diffs_at_host(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                        const uint32_t *clock_rows, const hm_op_diff_out *out, uint32_t *out_index,
+                        uint64_t *out_totals, uint32_t opts) {
+    if (n && !clock_rows) return HM_ERR_INVALID;
+    return op_diffs_host(e, b, r, n, doc_index, nullptr, nullptr, clock_rows, out, out_index, out_totals, opts);
+}
+
 int hm_op_diffs_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
                        const uint32_t *from, const uint32_t *to, const hm_op_diff_out *out,
                        hm_op_diff_summary *out_summary, void *work, void *stream) {
@@ -589,11 +618,19 @@ int hm_op_diffs_device(hm_engine *e, const hm_batch *b, const hm_results *r, uin
 int hm_op_diffs_device_ex(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
                           const uint32_t *from, const uint32_t *to, const hm_op_diff_out *out, uint32_t *out_index,
                           hm_op_diff_summary *out_summary, void *work, void *stream, uint32_t opts) {
+    if (n && (!from || !to)) return e ? fail(e, HM_ERR_INVALID, "hm_op_diffs: work, a range array or a per-request output missing") : HM_ERR_INVALID;
+    return op_diffs_device(e, b, r, n, doc_index, from, to, nullptr, out, out_index, out_summary, work, stream, opts);
+}
+
+// hm_op_diffs_device_ex (clock_rows NULL) and hm_op_diffs_at_device (from / to NULL)
+static int op_diffs_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                           const uint32_t *from, const uint32_t *to, const uint32_t *clock_rows, const hm_op_diff_out *out,
+                           uint32_t *out_index, hm_op_diff_summary *out_summary, void *work, void *stream, uint32_t opts) {
     try {
         if (!e || !r || !out || !out_summary || (opts & ~HM_ODF_LISTS)) return HM_ERR_INVALID;
         int st = check_batch(e, b);
         if (st) return st;
-        if (n && (!work || !from || !to || !out->range || !out->flags))
+        if (n && (!work || !out->range || !out->flags))
             return fail(e, HM_ERR_INVALID, "hm_op_diffs: work, a range array or a per-request output missing");
         if (((uintptr_t)work | (uintptr_t)b->ops) & 15u)       // (the counts and the op rows are read as 16-byte words)
             return fail(e, HM_ERR_INVALID, "hm_op_diffs: work and b->ops must be 16-byte aligned");
@@ -605,12 +642,12 @@ int hm_op_diffs_device_ex(hm_engine *e, const hm_batch *b, const hm_results *r, 
         hipStream_t s = stream ? (hipStream_t)stream : e->stream;
         OpDiffArgs A = {};
         A.n = n; A.src = batch_source(b, r); A.src.handles = doc_index;
-        A.from = from; A.to = to;
+        A.from = from; A.to = to; A.clock = clock_rows;
         A.cnt = (uint32_t *)work; A.off = A.cnt + 4 * (size_t)n; A.aux = A.off + 4 * (size_t)n;
         A.part = (unsigned long long *)((char *)work + ((((size_t)n * 40) + 255) & ~(size_t)255));
         A.sum = out_summary;
         A.opts = opts; A.out_index = (opts & HM_ODF_LISTS) ? out_index : nullptr;
-        A.slice_words = od_batch_slice(b, opts); A.waves = hm_od_waves(n, A.slice_words);
+        A.slice_words = od_batch_slice(b, opts, clock_rows != nullptr); A.waves = hm_od_waves(n, A.slice_words);
         A.work = (uint32_t *)((char *)work + od_fixed_bytes(n));
         A.cap_rows = out->cap_rows; A.cap_surv = out->cap_surv;
         A.out_rows = out->rows; A.out_surv = out->surv; A.out_range = out->range; A.out_flags = out->flags;
@@ -630,6 +667,14 @@ int hm_op_diffs_host(hm_engine *e, const hm_batch *hb, const hm_results *hr, uin
 int hm_op_diffs_host_ex(hm_engine *e, const hm_batch *hb, const hm_results *hr, uint32_t n, const uint32_t *doc_index,
                         const uint32_t *from, const uint32_t *to, const hm_op_diff_out *out, uint32_t *out_index,
                         uint64_t *out_totals, uint32_t opts) {
+    if (n && (!from || !to)) return e ? fail(e, HM_ERR_INVALID, "hm_op_diffs: a range array or an output missing") : HM_ERR_INVALID;
+    return op_diffs_host(e, hb, hr, n, doc_index, from, to, nullptr, out, out_index, out_totals, opts);
+}
+
+// hm_op_diffs_host_ex (clock_rows NULL) and hm_op_diffs_at_host (from / to NULL)
+static int op_diffs_host(hm_engine *e, const hm_batch *hb, const hm_results *hr, uint32_t n, const uint32_t *doc_index,
+                         const uint32_t *from, const uint32_t *to, const uint32_t *clock_rows, const hm_op_diff_out *out,
+                         uint32_t *out_index, uint64_t *out_totals, uint32_t opts) {
     try {
         if (!e || !hr || !out || (opts & ~HM_ODF_LISTS)) return HM_ERR_INVALID;
         const bool want_index = (opts & HM_ODF_LISTS) != 0u;
@@ -637,7 +682,7 @@ int hm_op_diffs_host_ex(hm_engine *e, const hm_batch *hb, const hm_results *hr, 
         if (st) return st;
         if (out_totals) out_totals[0] = out_totals[1] = 0;
         if (!n) return HM_OK;
-        if (!from || !to || !out->range || !out->flags || (out->cap_rows && !out->rows) || (out->cap_surv && !out->surv) ||
+        if (!out->range || !out->flags || (out->cap_rows && !out->rows) || (out->cap_surv && !out->surv) ||
             (want_index && out->cap_rows && !out_index))
             return fail(e, HM_ERR_INVALID, "hm_op_diffs: a range array or an output missing");
         if (!hr->docs || (hb->n_changes && (!hr->hist || !hr->all_deps)))
@@ -652,11 +697,11 @@ int hm_op_diffs_host_ex(hm_engine *e, const hm_batch *hb, const hm_results *hr, 
         // inputs 0..8, then the summary, the work memory, the four outputs and the index table
         const size_t sz[16] = {nd * sizeof(hm_doc_row), hb->n_changes * sizeof(hm_change_row), hb->n_ops * sizeof(hm_op_row),
                                nd * sizeof(hm_doc_result), (size_t)hb->n_changes * 4, (size_t)hb->n_changes * S * 4,
-                               doc_index ? (size_t)n * 4 : 0, (size_t)n * 4, (size_t)n * 4,
-                               sizeof(hm_op_diff_summary), hm_op_diffs_work_bytes_ex(hb, n, opts),
+                               doc_index ? (size_t)n * 4 : 0, clock_rows ? (size_t)n * S * 4 : (size_t)n * 4, clock_rows ? 0 : (size_t)n * 4,
+                               sizeof(hm_op_diff_summary), clock_rows ? hm_op_diffs_at_work_bytes(hb, n, opts) : hm_op_diffs_work_bytes_ex(hb, n, opts),
                                (size_t)out->cap_rows * sizeof(hm_op_diff), (size_t)out->cap_surv * sizeof(hm_surv_result),
                                (size_t)n * 8, (size_t)n * 4, want_index ? (size_t)out->cap_rows * 4 : 0};
-        const void *src[9] = {hb->docs, hb->changes, hb->ops, hr->docs, hr->hist, hr->all_deps, doc_index, from, to};
+        const void *src[9] = {hb->docs, hb->changes, hb->ops, hr->docs, hr->hist, hr->all_deps, doc_index, clock_rows ? clock_rows : from, to};
         size_t off[16], total = 0;
         for (int i = 0; i < 16; i++) { off[i] = total; total += al(sz[i] ? sz[i] : 1); }
         char *base = nullptr;
@@ -677,8 +722,9 @@ int hm_op_diffs_host_ex(hm_engine *e, const hm_batch *hb, const hm_results *hr, 
             if (sz[i]) rr = hipMemcpyAsync(base + off[i], src[i], sz[i], hipMemcpyHostToDevice, s);
         int rc = HM_OK;
         if (rr == hipSuccess)
-            rc = hm_op_diffs_device_ex(e, &b, &d, n, doc_index ? (const uint32_t *)(base + off[6]) : nullptr,
-                                       (const uint32_t *)(base + off[7]), (const uint32_t *)(base + off[8]), &o,
+            rc = op_diffs_device(e, &b, &d, n, doc_index ? (const uint32_t *)(base + off[6]) : nullptr,
+                                 clock_rows ? nullptr : (const uint32_t *)(base + off[7]), clock_rows ? nullptr : (const uint32_t *)(base + off[8]),
+                                 clock_rows ? (const uint32_t *)(base + off[7]) : nullptr, &o,
                                        (uint32_t *)(base + off[15]), (hm_op_diff_summary *)(base + off[9]), base + off[10], s, opts);
         if (rc == HM_OK && rr == hipSuccess) rr = hipMemcpyAsync(&sum, base + off[9], sizeof sum, hipMemcpyDeviceToHost, s);
         if (rc == HM_OK && rr == hipSuccess) rr = hipStreamSynchronize(s);

@@ -35,6 +35,12 @@
 // (HM_OD_ELEM_* rows, their index in out_index) instead of flagged; its slice is
 // hm_od_slice_words_lists.  The walk is a second pair of instantiations: with opts = 0 the kernels
 // are the ones they were.
+//
+// OpDiffArgs.clock: the clock forms, a third and fourth pair of instantiations.  Request i = (handles[i],
+// clock[i * S ..]) covers the changes applied at that clock (hist >= 0, seq <= K[actor], all_deps row
+// <= K), from the empty document: a select phase per request leaves a bit per log change behind the
+// slice's other words (hm_od_slice_words_clock) and the walk reads it where it otherwise tests the
+// history position.  Count, scan, fill, outputs and flags are the same; there is no one-walk form.
 #define HM_OD_BAD_HANDLE 1u
 #define HM_OD_BAD_ROWS 2u
 #define HM_OD_BAD_WORK 4u
@@ -59,6 +65,12 @@ __host__ __device__ inline unsigned long long hm_od_slice_words_lists(unsigned l
     return 3ull * n_ops + 17ull * n_regs + 2ull * n_objs + 1ull;
 }
 
+// The clock forms (OpDiffArgs.clock) add the select phase's bitmap to a document's slice, after its other
+// words: a bit per log change of the document, set when the change is applied at the request's clock
+__host__ __device__ inline unsigned long long hm_od_slice_words_clock(unsigned long long n_changes) {
+    return (n_changes + 31ull) / 32ull;
+}
+
 // workgroups (one wave each) of a call whose largest document needs slice_words: as many as the
 // requests, the waves a 256-CU device keeps resident (8,704 B of LDS each: 16 to a CU) and a
 // 256 MiB work budget allow, at least one
@@ -72,7 +84,7 @@ inline uint32_t hm_od_waves(uint32_t n, unsigned long long slice_words) {
 struct OpDiffArgs {
     uint32_t n;
     DocSource src;
-    const uint32_t *from, *to;                 // [n]
+    const uint32_t *from, *to;                 // [n] (not read when clock is given)
     uint32_t *cnt, *aux, *off;                 // [4n], [2n], [4n]
     unsigned long long *part;                  // [hm_past_scan_chunks(n) * HM_PAST_PART]
     hm_op_diff_summary *sum;
@@ -87,6 +99,10 @@ struct OpDiffArgs {
     // HM_ODF_* of the call; with HM_ODF_LISTS the fill writes out_index [cap_rows] beside out_rows
     uint32_t opts;
     uint32_t *out_index;
+    // != NULL: the clock forms.  Request i takes the changes applied at clock[i * S ..] (per rank the
+    // largest seq selected): hist >= 0, seq <= K[actor] and all_deps row <= K; every row is in range,
+    // the patch from the empty document.  The slice grows by hm_od_slice_words_clock(changes).
+    const uint32_t *clock;                     // [n * S]
 };
 // the largest slice a request of the call needs, left in out_words[0]; out_words[1] = 1 when opts has
 // HM_ODF_LISTS and a requested document carries HM_DOC_HAS_LISTS (device, two words zeroed by the

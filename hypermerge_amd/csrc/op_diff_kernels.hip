@@ -34,6 +34,11 @@
 //                    request takes a row block sized by the ops of its slice and, per step, a survivor
 //                    block sized by the step's first walks, each with one atomicAdd on the call's
 //                    totals (changes_kernel's pattern), and writes as it goes
+//  od_walk_kernel    <FILL, LISTS, false, true>: the clock forms (OpDiffArgs.clock): a request names a clock
+//                    instead of a slice and gets the whole patch of the changes applied at it.  A select
+//                    phase (select_at) leaves a bit per log change in the slice; collect, mark and
+//                    scatter read it where the slice forms test the history position, and every
+//                    marked op is in range
 //
 // Every loop over a chain is bounded by the document's op rows, so tables that are not a merge's
 // (overlapping op ranges) cannot hang a wave; no row past a lim_* of the source is read.
@@ -59,7 +64,8 @@ __global__ __launch_bounds__(256) void od_need_kernel(OpDiffArgs A, unsigned lon
     const DocRef s = doc_of(A.src, q);
     if (s.bad) return;
     const bool lm = (A.opts & HM_ODF_LISTS) && (s.flags & HM_DOC_HAS_LISTS);
-    atomicMax(out_words, lm ? hm_od_slice_words_lists(s.n_o, s.n_r, s.n_objs) : hm_od_slice_words(s.n_o, s.n_r, s.n_objs));
+    atomicMax(out_words, (lm ? hm_od_slice_words_lists(s.n_o, s.n_r, s.n_objs) : hm_od_slice_words(s.n_o, s.n_r, s.n_objs)) +
+                             (A.clock ? hm_od_slice_words_clock(s.n_c) : 0ull));
     if (lm) atomicOr(out_words + 1, 1ull);                     // (a document of the call has lists)
 }
 
@@ -187,17 +193,25 @@ __device__ __forceinline__ bool key_less(const uint32_t *a, const uint32_t *b) {
 // the parent a node hangs under: every _head child (top bit clear) under the one virtual root
 __device__ __forceinline__ uint32_t parent_id(uint32_t w0) { return (w0 & 0x80000000u) ? w0 : 0u; }
 
+// is log change i of the document applied at the request's clock (the select phase's bitmap)
+__device__ __forceinline__ bool selected(const uint32_t *sel, uint32_t i) { return (sel[i >> 5] >> (i & 31u)) & 1u; }
+
 // returns the nodes; ok = false: an ins row that cannot be a merge's (a register, object or parent
 // outside the document, more applied ins ops than registers)
-__device__ uint32_t list_order(const DocSource &D, const DocRef &s, uint32_t lim, const ListSlice &X, uint32_t lane,
+template <bool CLOCK>
+__device__ uint32_t list_order(const DocSource &D, const DocRef &s, uint32_t lim, const uint32_t *sel, const ListSlice &X, uint32_t lane,
                                uint32_t *ctr, bool &ok) {
     if (lane == 0) *ctr = 0u;
     for (uint32_t i = lane; i < s.n_r; i += 64u) { X.pos[i] = HM_NONE; X.vis[i] = 0u; X.fen[i] = HM_NONE; X.fc[i] = HM_NONE; }
     for (uint32_t i = lane; i < s.n_objs; i += 64u) X.ofirst[i] = HM_NONE;
     __syncthreads();
     for (uint32_t i = lane; i < s.n_c; i += 64u) {             // collect
-        const int32_t hp = D.hist[s.c_off + i];
-        if (hp < 0 || (uint32_t)hp >= lim) continue;
+        if (CLOCK) {
+            if (!selected(sel, i)) continue;
+        } else {
+            const int32_t hp = D.hist[s.c_off + i];
+            if (hp < 0 || (uint32_t)hp >= lim) continue;
+        }
         const hm_change_row c = D.changes[s.c_off + i];
         if (!c.n_ops) continue;
         if (c.op_first < s.o_off || (unsigned long long)c.op_first + c.n_ops > (unsigned long long)s.o_off + s.n_o) continue;   // (the walk reports it)
@@ -285,9 +299,53 @@ __device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
     return v;
 }
 
-template <bool FILL, bool LISTS, bool ONCE = false>
+// The select phase of the clock forms: which log changes of the document are applied at clock K, a bit
+// per log change in sel[] (hm_od_slice_words_clock words): hist >= 0, seq <= K[actor] and the all_deps
+// row <= K in every column.  64 changes a step, a lane per change for the cheap part; the row is then
+// read by the change's own lane at strides up to 16 (at most 64 B a lane), and above that by the whole
+// wave, a lane per column, 256 B a read, for the changes the cheap part left (a uniform loop over the
+// step's ballot).  Returns 1 + the largest selected history position (0: nothing selected), in every lane.
+__device__ uint32_t select_at(const DocSource &D, const DocRef &s, const uint32_t *K, uint32_t *sel, uint32_t lane) {
+    const uint32_t S = D.S;
+    uint32_t top = 0;
+    for (uint32_t base = 0; base < s.n_c; base += 64u) {
+        const uint32_t i = base + lane;
+        bool c = false;
+        if (i < s.n_c) {
+            const int32_t hp = D.hist[s.c_off + i];
+            const hm_change_row r = D.changes[s.c_off + i];
+            c = hp >= 0 && (uint32_t)hp < s.n_c && r.actor < S && r.seq <= K[r.actor];
+            if (c && S <= 16u) {
+                const uint32_t *row = D.all_deps + (size_t)(s.c_off + i) * S;
+                for (uint32_t a = 0; a < S; a++) c &= row[a] <= K[a];
+            }
+            if (c && S <= 16u) top = max(top, (uint32_t)hp + 1u);
+        }
+        unsigned long long m = __ballot(c);
+        if (S > 16u) {
+            for (uint32_t j = 0; j < 64u; j++) {               // (uniform: m is the wave's)
+                if (!((m >> j) & 1ull)) continue;
+                const uint32_t *row = D.all_deps + (size_t)(s.c_off + base + j) * S;
+                bool ok = true;
+                for (uint32_t a = lane; a < S; a += 64u) ok &= row[a] <= K[a];
+                if (__ballot(!ok)) m &= ~(1ull << j);
+            }
+            if (i < s.n_c && ((m >> lane) & 1ull)) top = max(top, (uint32_t)D.hist[s.c_off + i] + 1u);
+        }
+        if (lane == 0) {
+            sel[base >> 5] = (uint32_t)m;
+            if (base + 32u < s.n_c) sel[(base >> 5) + 1u] = (uint32_t)(m >> 32);
+        }
+    }
+    for (uint32_t d = 32; d; d >>= 1) top = max(top, __shfl_xor(top, d));
+    __syncthreads();
+    return top;
+}
+
+template <bool FILL, bool LISTS, bool ONCE = false, bool CLOCK = false>
 __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
     static_assert(!(FILL && ONCE), "the one-walk form has no fill pass");
+    static_assert(!(CLOCK && ONCE), "the one-walk form takes no clock");
     __shared__ Lds L;
     const uint32_t lane = threadIdx.x;
     const DocSource &D = A.src;
@@ -298,7 +356,7 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
     uint32_t *const wbase = A.work + (size_t)blockIdx.x * A.slice_words;
     for (unsigned long long q = blockIdx.x; q < A.n; q += gridDim.x) {
         DocRef s = doc_of(D, q);
-        const uint32_t from = A.from[q], to = A.to[q];
+        const uint32_t from = CLOCK ? 0u : A.from[q], to = CLOCK ? 0u : A.to[q];
         uint4 cn = make_uint4(0, 0, 0, 0), of = make_uint4(0, 0, 0, 0);
         uint32_t fl = 0;
         if (FILL) {
@@ -313,7 +371,11 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
         uint32_t bad = s.bad ? HM_OD_BAD_HANDLE : 0u;
         // element assigns are answered for a document that says it has lists; without the hint they are flagged
         const bool lm = LISTS && (s.flags & HM_DOC_HAS_LISTS);
-        if ((lm ? hm_od_slice_words_lists(s.n_o, s.n_r, s.n_objs) : hm_od_slice_words(s.n_o, s.n_r, s.n_objs)) > A.slice_words) { bad |= HM_OD_BAD_WORK; s.n_c = 0; }
+        unsigned long long sel_at = 0;                         // CLOCK: the bitmap follows the document's other words
+        if (CLOCK) {
+            sel_at = lm ? hm_od_slice_words_lists(s.n_o, s.n_r, s.n_objs) : hm_od_slice_words(s.n_o, s.n_r, s.n_objs);
+            if (sel_at + hm_od_slice_words_clock(s.n_c) > A.slice_words) { bad |= HM_OD_BAD_WORK; s.n_c = 0; }
+        } else if ((lm ? hm_od_slice_words_lists(s.n_o, s.n_r, s.n_objs) : hm_od_slice_words(s.n_o, s.n_r, s.n_objs)) > A.slice_words) { bad |= HM_OD_BAD_WORK; s.n_c = 0; }
         Slice W;
         W.prev = wbase; W.next = W.prev + s.n_o; W.chg = W.next + s.n_o; W.last = W.chg + s.n_o; W.otype = W.last + s.n_r;
         ListSlice X = {};
@@ -321,7 +383,11 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
             X.pos = W.otype + s.n_objs; X.vis = X.pos + s.n_r; X.fen = X.vis + s.n_r; X.fc = X.fen + s.n_r + 1u;
             X.ofirst = X.fc + s.n_r; X.key = X.ofirst + s.n_objs; X.nxt = X.key + 4u * (size_t)s.n_r; X.sum = X.nxt + 4u * (size_t)s.n_r;
         }
-        const uint32_t lim = to < s.n_c ? to : s.n_c;          // history positions of interest lie below it
+        // CLOCK: history positions of interest are the selected ones, all of them in range (the patch
+        // from the empty document)
+        uint32_t *const sel = CLOCK ? wbase + sel_at : nullptr;
+        const uint32_t lim = CLOCK ? select_at(D, s, A.clock + (size_t)q * D.S, sel, lane)
+                                   : (to < s.n_c ? to : s.n_c);   // history positions of interest lie below it
         uint32_t rows = 0, surv = 0;                           // emitted so far
         bool lists = false, rows_ok = true;
         // ONCE: the request's row block (the ops of its slice bound its rows: an ins emits none, every
@@ -347,7 +413,7 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
         if (from < lim) {
             for (uint32_t i = lane; i < s.n_r; i += 64u) W.last[i] = HM_NONE;
             for (uint32_t i = lane; i < s.n_objs; i += 64u) W.otype[i] = 0u;
-            if (LISTS && lm) X.n = list_order(D, s, lim, X, lane, &L.src[0], rows_ok);
+            if (LISTS && lm) X.n = list_order<CLOCK>(D, s, lim, sel, X, lane, &L.src[0], rows_ok);
         }
         const uint32_t n_tiles = from < lim ? (lim + OTILE - 1u) / OTILE : 0u;
         for (uint32_t t = 0; t < n_tiles; t++) {
@@ -355,7 +421,8 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
             __syncthreads();
             for (uint32_t i = lane; i < s.n_c; i += 64u) {     // mark
                 const int32_t hp = D.hist[s.c_off + i];
-                if (hp >= 0 && (uint32_t)hp < lim && (uint32_t)hp / OTILE == t) L.tile.mark((uint32_t)hp);
+                if (CLOCK ? selected(sel, i) && (uint32_t)hp / OTILE == t
+                          : hp >= 0 && (uint32_t)hp < lim && (uint32_t)hp / OTILE == t) L.tile.mark((uint32_t)hp);
             }
             __syncthreads();
             const uint32_t tile_n = L.tile.rank(lane);         // rank
@@ -363,7 +430,8 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
             if (!tile_n) continue;
             for (uint32_t i = lane; i < s.n_c; i += 64u) {     // scatter
                 const int32_t hp = D.hist[s.c_off + i];
-                if (hp < 0 || (uint32_t)hp >= lim || (uint32_t)hp / OTILE != t) continue;
+                if (CLOCK ? !selected(sel, i) || (uint32_t)hp / OTILE != t
+                          : hp < 0 || (uint32_t)hp >= lim || (uint32_t)hp / OTILE != t) continue;
                 uint32_t k;
                 if (!L.tile.slot((uint32_t)hp, k)) continue;
                 const hm_change_row c = D.changes[s.c_off + i];
@@ -402,7 +470,7 @@ __global__ __launch_bounds__(OWG) void od_walk_kernel(OpDiffArgs A) {
                 __syncthreads();
                 const uint32_t ot = assign && obj < s.n_objs ? W.otype[obj] : 0u;
                 const bool list = ot == 1u + HM_MAKE_LIST || ot == 1u + HM_MAKE_TEXT;
-                const bool in_range = valid && p >= from;
+                const bool in_range = valid && (CLOCK || p >= from);
                 lists |= in_range && list && !(LISTS && lm);
                 const bool chain = assign && (!list || (LISTS && lm)) && reg != HM_NONE && reg < s.n_r;
                 const bool el = LISTS && chain && list;         // an element assign that is answered
@@ -532,7 +600,10 @@ hipError_t hm_launch_op_diff_need(const OpDiffArgs &a, unsigned long long *out_w
 hipError_t hm_launch_op_diff_count(const OpDiffArgs &a, hipStream_t s) {
     hipError_t r = hipMemsetAsync(a.sum, 0, sizeof(hm_op_diff_summary), s);
     if (r != hipSuccess || !a.n) return r;                     // (no request: the zero summary is the answer)
-    if (a.opts & HM_ODF_LISTS) hipLaunchKernelGGL((hmo::od_walk_kernel<false, true>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+    if (a.clock) {
+        if (a.opts & HM_ODF_LISTS) hipLaunchKernelGGL((hmo::od_walk_kernel<false, true, false, true>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+        else hipLaunchKernelGGL((hmo::od_walk_kernel<false, false, false, true>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+    } else if (a.opts & HM_ODF_LISTS) hipLaunchKernelGGL((hmo::od_walk_kernel<false, true>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
     else hipLaunchKernelGGL((hmo::od_walk_kernel<false, false>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
     if ((r = hipGetLastError()) != hipSuccess) return r;
     return hm_launch_past_scan(scan_args(a), s);
@@ -541,6 +612,7 @@ hipError_t hm_launch_op_diff_count(const OpDiffArgs &a, hipStream_t s) {
 hipError_t hm_launch_op_diff_once(const OpDiffArgs &a, hipStream_t s) {
     hipError_t r = hipMemsetAsync(a.sum, 0, sizeof(hm_op_diff_summary), s);
     if (r != hipSuccess || !a.n) return r;
+    if (a.clock) return hipErrorInvalidValue;                  // (the one-walk form takes no clock)
     if (a.opts & HM_ODF_LISTS) hipLaunchKernelGGL((hmo::od_walk_kernel<false, true, true>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
     else {                                                     // (no document of the call has lists: no row has an index)
         if (a.out_index && a.cap_rows && (r = hipMemsetAsync(a.out_index, 0xFF, (size_t)a.cap_rows * 4, s)) != hipSuccess) return r;
@@ -551,11 +623,17 @@ hipError_t hm_launch_op_diff_once(const OpDiffArgs &a, hipStream_t s) {
 
 hipError_t hm_launch_op_diff_fill(const OpDiffArgs &a, hipStream_t s) {
     if (!a.n) return hipSuccess;
-    if (a.opts & HM_ODF_LISTS) hipLaunchKernelGGL((hmo::od_walk_kernel<true, true>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
-    else if (a.out_index && a.cap_rows) {                      // (no document of the call has lists: no row has an index)
+    const dim3 grid(a.waves ? a.waves : 1u);
+    if (a.opts & HM_ODF_LISTS) {
+        if (a.clock) hipLaunchKernelGGL((hmo::od_walk_kernel<true, true, false, true>), grid, dim3(OWG), 0, s, a);
+        else hipLaunchKernelGGL((hmo::od_walk_kernel<true, true>), grid, dim3(OWG), 0, s, a);
+        return hipGetLastError();
+    }
+    if (a.out_index && a.cap_rows) {                           // (no document of the call has lists: no row has an index)
         const hipError_t r = hipMemsetAsync(a.out_index, 0xFF, (size_t)a.cap_rows * 4, s);
         if (r != hipSuccess) return r;
-        hipLaunchKernelGGL((hmo::od_walk_kernel<true, false>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
-    } else hipLaunchKernelGGL((hmo::od_walk_kernel<true, false>), dim3(a.waves ? a.waves : 1u), dim3(OWG), 0, s, a);
+    }
+    if (a.clock) hipLaunchKernelGGL((hmo::od_walk_kernel<true, false, false, true>), grid, dim3(OWG), 0, s, a);
+    else hipLaunchKernelGGL((hmo::od_walk_kernel<true, false>), grid, dim3(OWG), 0, s, a);
     return hipGetLastError();
 }

@@ -1375,27 +1375,30 @@ int hm_store_materialize_sized(hm_store *s, uint32_t n, const uint32_t *doc_hand
     }
 }
 
-// n op-diff requests staged: handles and ranges go to the stage buffer, where the counts, offsets and
+// n op-diff requests staged: handles and ranges (clock_rows != NULL: the clock table [n * a_stride]
+// instead, from / to unused) go to the stage buffer, where the counts, offsets and
 // summary will stay (A.cnt / A.off / A.aux / A.sum); the largest requested document sizes a wave's
 // slice of the chains' work memory (A.slice_words, A.waves; A.work is the caller's to place).
 static int op_diff_stage(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
-                         uint32_t opts, OpDiffArgs &A) {
+                         const uint32_t *clock_rows, uint32_t opts, OpDiffArgs &A) {
     hipStream_t st = hm_engine_stream(s->e);
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_sum = 0, o_need = 128, o_h = 256, o_from = o_h + al(4 * (size_t)n), o_to = o_from + al(4 * (size_t)n),
+    const size_t sel_b = clock_rows ? 4 * (size_t)n * s->S : 4 * (size_t)n;
+    const size_t o_sum = 0, o_need = 128, o_h = 256, o_from = o_h + al(4 * (size_t)n), o_to = o_from + al(sel_b),
                  o_cnt = o_to + al(4 * (size_t)n), o_off = o_cnt + al(16 * (size_t)n), o_aux = o_off + al(16 * (size_t)n),
                  o_part = o_aux + al(8 * (size_t)n), total = o_part + al((size_t)hm_past_scan_chunks(n) * HM_PAST_PART * 8);
     int rc = ensure_stage(s, total);
     if (rc) return rc;
     uint8_t *sp = s->stage.p;
     SCHK(s, hipMemcpyAsync(sp + o_h, doc_handles, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-    SCHK(s, hipMemcpyAsync(sp + o_from, from, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-    SCHK(s, hipMemcpyAsync(sp + o_to, to, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    SCHK(s, hipMemcpyAsync(sp + o_from, clock_rows ? clock_rows : from, sel_b, hipMemcpyHostToDevice, st));
+    if (!clock_rows) SCHK(s, hipMemcpyAsync(sp + o_to, to, 4 * (size_t)n, hipMemcpyHostToDevice, st));
     SCHK(s, hipMemsetAsync(sp + o_need, 0, 16, st));
     A = OpDiffArgs{};
     A.n = n; A.src = store_source(s); A.src.handles = (const uint32_t *)(sp + o_h);
     A.opts = opts;
-    A.from = (const uint32_t *)(sp + o_from); A.to = (const uint32_t *)(sp + o_to);
+    if (clock_rows) A.clock = (const uint32_t *)(sp + o_from);
+    else { A.from = (const uint32_t *)(sp + o_from); A.to = (const uint32_t *)(sp + o_to); }
     A.cnt = (uint32_t *)(sp + o_cnt); A.off = (uint32_t *)(sp + o_off); A.aux = (uint32_t *)(sp + o_aux);
     A.part = (unsigned long long *)(sp + o_part);
     A.sum = (hm_op_diff_summary *)(sp + o_sum);
@@ -1427,8 +1430,8 @@ static int op_diff_summary(hm_store *s, const OpDiffArgs &A, hm_op_diff_summary 
 
 // The count pass of n op-diff requests; the chains' work memory is the head of s->past.
 static int op_diff_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
-                         uint32_t opts, OpDiffArgs &A, hm_op_diff_summary *sum) {
-    int rc = op_diff_stage(s, n, doc_handles, from, to, opts, A);
+                         const uint32_t *clock_rows, uint32_t opts, OpDiffArgs &A, hm_op_diff_summary *sum) {
+    int rc = op_diff_stage(s, n, doc_handles, from, to, clock_rows, opts, A);
     if (rc) return rc;
     if ((rc = ensure_buf(s, s->past, ((size_t)A.waves * A.slice_words * 4 + 255) & ~(size_t)255))) return rc;
     A.work = (uint32_t *)s->past.p;
@@ -1436,23 +1439,16 @@ static int op_diff_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, c
     return op_diff_summary(s, A, sum);
 }
 
-extern "C" {
-
-int hm_store_op_diff_sizes(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
-                           uint32_t *out_counts, uint32_t *out_flags, uint64_t *out_totals) {
-    return hm_store_op_diff_sizes_ex(s, n, doc_handles, from, to, out_counts, out_flags, out_totals, 0u);
-}
-
-int hm_store_op_diff_sizes_ex(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
-                              uint32_t *out_counts, uint32_t *out_flags, uint64_t *out_totals, uint32_t opts) {
-    if (!s || (n && (!doc_handles || !from || !to)) || (opts & ~HM_ODF_LISTS)) return HM_ERR_INVALID;
+// hm_store_op_diff_sizes_ex (clock_rows NULL) and hm_store_op_diff_sizes_at (from / to NULL)
+static int op_diff_sizes(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                         const uint32_t *clock_rows, uint32_t *out_counts, uint32_t *out_flags, uint64_t *out_totals, uint32_t opts) {
     if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
     try {
         if (out_totals) out_totals[0] = out_totals[1] = 0;
         if (!n) return HM_OK;
         OpDiffArgs A;
         hm_op_diff_summary sum;
-        int rc = op_diff_count(s, n, doc_handles, from, to, opts, A, &sum);
+        int rc = op_diff_count(s, n, doc_handles, from, to, clock_rows, opts, A, &sum);
         if (rc) return rc;
         if (out_totals) { out_totals[0] = sum.totals[0]; out_totals[1] = sum.totals[1]; }
         if (out_counts || out_flags) {
@@ -1469,6 +1465,73 @@ int hm_store_op_diff_sizes_ex(hm_store *s, uint32_t n, const uint32_t *doc_handl
         return HM_OK;
     } catch (...) {
         return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_op_diff_sizes");
+    }
+}
+
+// the count, scan and fill form of hm_store_op_diffs_ex (clock_rows NULL) and hm_store_op_diffs_at (from / to NULL)
+static int op_diffs_filled(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                           const uint32_t *clock_rows, const hm_op_diff_out *out, uint32_t *out_index, uint64_t *out_totals, uint32_t opts) {
+    const bool want_index = (opts & HM_ODF_LISTS) != 0u;
+    hipStream_t st = hm_engine_stream(s->e);
+    OpDiffArgs A;
+    hm_op_diff_summary sum;
+    int rc = op_diff_count(s, n, doc_handles, from, to, clock_rows, opts, A, &sum);
+    if (rc) return rc;
+    const uint64_t tr = sum.totals[0], ts = sum.totals[1];
+    if (out_totals) { out_totals[0] = tr; out_totals[1] = ts; }
+    if (tr > out->cap_rows || ts > out->cap_surv)
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "a capacity below the rows of the op diffs");
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // [work][rows][survivors][ranges][flags][index]
+    const size_t sz[5] = {tr * sizeof(hm_op_diff), ts * sizeof(hm_surv_result), 8 * (size_t)n, 4 * (size_t)n, want_index ? 4 * (size_t)tr : 0};
+    size_t o[5], total = al((size_t)A.waves * A.slice_words * 4);
+    for (int i = 0; i < 5; i++) { o[i] = total; total += al(sz[i] + 1); }
+    if ((rc = ensure_buf(s, s->past, total))) return rc;
+    uint8_t *bp = s->past.p;
+    A.work = (uint32_t *)bp;
+    A.cap_rows = (uint32_t)tr; A.cap_surv = (uint32_t)ts;
+    A.out_rows = (hm_op_diff *)(bp + o[0]); A.out_surv = (hm_surv_result *)(bp + o[1]);
+    A.out_range = (uint32_t *)(bp + o[2]); A.out_flags = (uint32_t *)(bp + o[3]); A.out_index = want_index ? (uint32_t *)(bp + o[4]) : nullptr;
+    SCHK(s, hm_launch_op_diff_fill(A, st));
+    void *dst[5] = {out->rows, out->surv, out->range, out->flags, out_index};
+    for (int i = 0; i < 5; i++)
+        if (sz[i]) SCHK(s, hipMemcpyAsync(dst[i], bp + o[i], sz[i], hipMemcpyDeviceToHost, st));
+    SCHK(s, hipStreamSynchronize(st));
+    return HM_OK;
+}
+
+extern "C" {
+
+int hm_store_op_diff_sizes(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                           uint32_t *out_counts, uint32_t *out_flags, uint64_t *out_totals) {
+    return hm_store_op_diff_sizes_ex(s, n, doc_handles, from, to, out_counts, out_flags, out_totals, 0u);
+}
+
+int hm_store_op_diff_sizes_ex(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *from, const uint32_t *to,
+                              uint32_t *out_counts, uint32_t *out_flags, uint64_t *out_totals, uint32_t opts) {
+    if (!s || (n && (!doc_handles || !from || !to)) || (opts & ~HM_ODF_LISTS)) return HM_ERR_INVALID;
+    return op_diff_sizes(s, n, doc_handles, from, to, nullptr, out_counts, out_flags, out_totals, opts);
+}
+
+int hm_store_op_diff_sizes_at(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *clock_rows,
+                              uint32_t *out_counts, uint32_t *out_flags, uint64_t *out_totals, uint32_t opts) {
+    if (!s || (n && (!doc_handles || !clock_rows)) || (opts & ~HM_ODF_LISTS)) return HM_ERR_INVALID;
+    return op_diff_sizes(s, n, doc_handles, nullptr, nullptr, clock_rows, out_counts, out_flags, out_totals, opts);
+}
+
+int hm_store_op_diffs_at(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *clock_rows,
+                         const hm_op_diff_out *out, uint32_t *out_index, uint64_t *out_totals, uint32_t opts) {
+    // (HM_ODF_ONCE is the docset round's form: not offered with a clock)
+    if (!s || !out || (n && (!doc_handles || !clock_rows || !out->range || !out->flags)) || (opts & ~HM_ODF_LISTS)) return HM_ERR_INVALID;
+    if ((out->cap_rows && !out->rows) || (out->cap_surv && !out->surv)) return HM_ERR_INVALID;
+    if ((opts & HM_ODF_LISTS) && out->cap_rows && !out_index) return HM_ERR_INVALID;
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        if (out_totals) out_totals[0] = out_totals[1] = 0;
+        if (!n) return HM_OK;
+        return op_diffs_filled(s, n, doc_handles, nullptr, nullptr, clock_rows, out, out_index, out_totals, opts);
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_op_diffs_at");
     }
 }
 
@@ -1494,7 +1557,7 @@ int hm_store_op_diffs_ex(hm_store *s, uint32_t n, const uint32_t *doc_handles, c
         hm_op_diff_summary sum;
         if (once) {
             // one launch into tables of the caller's capacities: [work][rows][survivors][ranges][flags][index]
-            int rc = op_diff_stage(s, n, doc_handles, from, to, opts & ~HM_ODF_ONCE, A);
+            int rc = op_diff_stage(s, n, doc_handles, from, to, nullptr, opts & ~HM_ODF_ONCE, A);
             if (rc) return rc;
             auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
             const size_t cr = out->cap_rows, cs = out->cap_surv;
@@ -1521,29 +1584,7 @@ int hm_store_op_diffs_ex(hm_store *s, uint32_t n, const uint32_t *doc_handles, c
             SCHK(s, hipStreamSynchronize(st));
             return HM_OK;
         }
-        int rc = op_diff_count(s, n, doc_handles, from, to, opts, A, &sum);
-        if (rc) return rc;
-        const uint64_t tr = sum.totals[0], ts = sum.totals[1];
-        if (out_totals) { out_totals[0] = tr; out_totals[1] = ts; }
-        if (tr > out->cap_rows || ts > out->cap_surv)
-            return hm_engine_fail(s->e, HM_ERR_NOMEM, "a capacity below the rows of the op diffs");
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        // [work][rows][survivors][ranges][flags][index]
-        const size_t sz[5] = {tr * sizeof(hm_op_diff), ts * sizeof(hm_surv_result), 8 * (size_t)n, 4 * (size_t)n, want_index ? 4 * (size_t)tr : 0};
-        size_t o[5], total = al((size_t)A.waves * A.slice_words * 4);
-        for (int i = 0; i < 5; i++) { o[i] = total; total += al(sz[i] + 1); }
-        if ((rc = ensure_buf(s, s->past, total))) return rc;
-        uint8_t *bp = s->past.p;
-        A.work = (uint32_t *)bp;
-        A.cap_rows = (uint32_t)tr; A.cap_surv = (uint32_t)ts;
-        A.out_rows = (hm_op_diff *)(bp + o[0]); A.out_surv = (hm_surv_result *)(bp + o[1]);
-        A.out_range = (uint32_t *)(bp + o[2]); A.out_flags = (uint32_t *)(bp + o[3]); A.out_index = want_index ? (uint32_t *)(bp + o[4]) : nullptr;
-        SCHK(s, hm_launch_op_diff_fill(A, st));
-        void *dst[5] = {out->rows, out->surv, out->range, out->flags, out_index};
-        for (int i = 0; i < 5; i++)
-            if (sz[i]) SCHK(s, hipMemcpyAsync(dst[i], bp + o[i], sz[i], hipMemcpyDeviceToHost, st));
-        SCHK(s, hipStreamSynchronize(st));
-        return HM_OK;
+        return op_diffs_filled(s, n, doc_handles, from, to, nullptr, out, out_index, out_totals, opts);
     } catch (...) {
         return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_op_diffs");
     }

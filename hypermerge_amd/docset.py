@@ -212,6 +212,23 @@ class DocSet:
         s, _ = _text(self._L, t)
         return json.loads(s)
 
+    @staticmethod
+    def _clock_entries(n: int, clocks: Sequence[Dict[str, float]]):
+        """{actorId: seq} per request as the entry tables of hm_docset_materialize(_patch_at)"""
+        assert len(clocks) == n
+        eoff = np.zeros(n + 1, np.uint32)
+        names: List[bytes] = []
+        seqs: List[float] = []
+        for i, clock in enumerate(clocks):
+            for a, q in clock.items():
+                names.append(a.encode("utf-8", "surrogatepass"))
+                seqs.append(float(q))
+            eoff[i + 1] = len(names)
+        aoff = np.zeros(len(names) + 1, np.uint32)
+        np.cumsum([len(x) for x in names], out=aoff[1:])
+        data = np.frombuffer(b"".join(names) + b"\0", np.uint8)
+        return eoff, data, aoff, np.array(seqs + [0.0], np.float64)
+
     def materialize(self, docs: Sequence[int], history: Optional[Sequence[int]] = None,
                     clocks: Optional[Sequence[Dict[str, float]]] = None) -> List[Dict[str, Any]]:
         """Documents as they were (RepoBackend's MaterializeMsg, many per call): docs[i] at history
@@ -224,19 +241,7 @@ class DocSet:
             hl = np.ascontiguousarray(np.minimum(np.asarray(history, np.int64), 0xFFFFFFFF), np.uint32)
             assert len(hl) == len(ids)
         if clocks is not None:
-            assert len(clocks) == len(ids)
-            eoff = np.zeros(len(ids) + 1, np.uint32)
-            names: List[bytes] = []
-            seqs: List[float] = []
-            for i, clock in enumerate(clocks):
-                for a, q in clock.items():
-                    names.append(a.encode("utf-8", "surrogatepass"))
-                    seqs.append(float(q))
-                eoff[i + 1] = len(names)
-            aoff = np.zeros(len(names) + 1, np.uint32)
-            np.cumsum([len(x) for x in names], out=aoff[1:])
-            data = np.frombuffer(b"".join(names) + b"\0", np.uint8)
-            sq = np.array(seqs + [0.0], np.float64)
+            eoff, data, aoff, sq = self._clock_entries(len(ids), clocks)
         p = lambda a: None if a is None else a.ctypes.data
         t = ctypes.c_void_p()
         self.engine._check(self._L.hm_docset_materialize(self._h, len(ids), ids.ctypes.data, p(hl), p(eoff), p(data), p(aoff),
@@ -244,7 +249,8 @@ class DocSet:
         s, _ = _text(self._L, t)
         return json.loads(s)
 
-    def materialize_patch(self, docs: Sequence[int], history: Sequence[int], lists: bool = False) -> List[Dict[str, Any]]:
+    def materialize_patch(self, docs: Sequence[int], history: Optional[Sequence[int]] = None,
+                          clocks: Optional[Sequence[Dict[str, float]]] = None, lists: bool = False) -> List[Dict[str, Any]]:
         """The patches of documents as they were (RepoBackend's MaterializeMsg reply, many per call):
         docs[i] at history length history[i].  Per request {"doc", "history", "patch"}: the patch is
         Backend.applyChanges(Backend.init(), history.slice(0, n))'s {clock, deps, canUndo, canRedo, diffs}
@@ -252,8 +258,24 @@ class DocSet:
         / text elements has "patch": None and "host": True and is replayed by the caller
         (hm_docset_materialize_patch).  lists=True (hm_docset_materialize_patch_ex with HM_ODF_LISTS):
         the element diffs (insert / set / remove at the index of that moment) come from the device too,
-        and no document fed through this package has "patch": None."""
+        and no document fed through this package has "patch": None.
+        clocks instead of history (exactly one of the two): docs[i] at the clock clocks[i] ({actorId:
+        seq}, an id the document never saw is dropped), the patch loadDocument sends for a document
+        opened at a cursor (hm_docset_materialize_patch_at).  Per request {"doc", "history": the changes
+        applied at the clock, "queued": the selected changes that are not, "patch"}; the diffs are in
+        the resident history order."""
         ids = np.ascontiguousarray(docs, np.uint32)
+        if (history is None) == (clocks is None):
+            raise ValueError("materialize_patch takes exactly one of history and clocks")
+        if clocks is not None:
+            eoff, data, aoff, sq = self._clock_entries(len(ids), clocks)
+            t = ctypes.c_void_p()
+            self.engine._check(self._L.hm_docset_materialize_patch_at(self._h, len(ids), ids.ctypes.data if len(ids) else None,
+                                                                      eoff.ctypes.data, data.ctypes.data, aoff.ctypes.data, sq.ctypes.data,
+                                                                      1 if lists else 0, ctypes.byref(t)),
+                               "hm_docset_materialize_patch_at")
+            s, _ = _text(self._L, t)
+            return json.loads(s)
         hl = np.ascontiguousarray(np.minimum(np.asarray(history, np.int64), 0xFFFFFFFF), np.uint32)
         assert len(hl) == len(ids)
         t = ctypes.c_void_p()

@@ -44,7 +44,9 @@ EXPORTS = ("hm_abi_version", "hm_status_message", "hm_engine_create", "hm_engine
            "hm_op_diffs_device", "hm_op_diffs_host", "hm_docset_materialize_patch",
            "hm_store_op_diff_sizes_ex", "hm_store_op_diffs_ex", "hm_op_diffs_work_bytes_ex", "hm_op_diffs_device_ex",
            "hm_op_diffs_host_ex", "hm_docset_materialize_patch_ex", "hm_docset_diff_stats",
-           "hm_store_fields", "hm_fields_device", "hm_fields_host", "hm_docset_fields")
+           "hm_store_fields", "hm_fields_device", "hm_fields_host", "hm_docset_fields",
+           "hm_store_op_diff_sizes_at", "hm_store_op_diffs_at", "hm_op_diffs_at_work_bytes", "hm_op_diffs_at_device",
+           "hm_op_diffs_at_host", "hm_docset_materialize_patch_at")
 
 _lib = None
 
@@ -146,6 +148,12 @@ def lib():
             "hm_op_diffs_work_bytes_ex": [ctypes.POINTER(CBatch), u32, u32],
             "hm_op_diffs_device_ex": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, vp, vp, u32],
             "hm_op_diffs_host_ex": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, u32],
+            "hm_store_op_diff_sizes_at": [vp, u32, vp, vp, vp, vp, vp, u32],
+            "hm_store_op_diffs_at": [vp, u32, vp, vp, vp, vp, vp, u32],
+            "hm_op_diffs_at_work_bytes": [ctypes.POINTER(CBatch), u32, u32],
+            "hm_op_diffs_at_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, vp, u32],
+            "hm_op_diffs_at_host": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, u32],
+            "hm_docset_materialize_patch_at": [vp, u32, vp, vp, vp, vp, vp, u32, vp],
             "hm_store_fields": [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp],
             "hm_fields_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), vp, vp, vp, u32, vp, vp, u32,
                                  vp, vp, vp, vp, u32, vp, vp, vp],
@@ -168,6 +176,7 @@ def lib():
         L.hm_materialize_work_bytes.restype = ctypes.c_size_t
         L.hm_op_diffs_work_bytes.restype = ctypes.c_size_t
         L.hm_op_diffs_work_bytes_ex.restype = ctypes.c_size_t
+        L.hm_op_diffs_at_work_bytes.restype = ctypes.c_size_t
         L.hm_docset_destroy.restype = None
         L.hm_docset_engine.restype = ctypes.c_void_p
         L.hm_text_data.restype = ctypes.c_void_p
@@ -471,6 +480,48 @@ class Engine:
                                                   p(frm), p(to), ctypes.byref(out), p(out_index), p(out_summary), p(work),
                                                   p(stream), ODF_LISTS if lists else 0),
                     "hm_op_diffs_device")
+
+    def op_diffs_at_host(self, batch: Batch, results: Results, docs, clocks, cap=None, lists=False):
+        """hm_op_diffs_at_host: the per-op patch of documents docs[i] of a merged batch (None: every
+        document, one request each) as they stood at the clocks clocks[i] ([n, a_stride] rank rows): what
+        op_diffs_host returns, for the changes applied at each clock, from the empty document."""
+        from .columnar import SURV_RESULT_DT
+        opts = ODF_LISTS if lists else 0
+        idx = None if docs is None else np.ascontiguousarray(docs, np.uint32)
+        n = batch.n_docs if idx is None else len(idx)
+        crow = np.ascontiguousarray(clocks, np.uint32).reshape(n, batch.a_stride)
+        cb, cr = batch.c_struct(), results.c_struct()
+        tot = (ctypes.c_uint64 * 2)()
+        caps = cap if cap is not None else (0, 0)
+        for _ in range(2):
+            rows, surv = np.zeros(max(caps[0], 1), OP_DIFF_DT), np.zeros(max(caps[1], 1), SURV_RESULT_DT)
+            rng, fl = np.zeros((max(n, 1), 2), np.uint32), np.zeros(max(n, 1), np.uint32)
+            index = np.zeros(max(caps[0], 1), np.uint32)
+            out = COpDiffOut(caps[0], caps[1], rows.ctypes.data, surv.ctypes.data, rng.ctypes.data, fl.ctypes.data)
+            st = self._L.hm_op_diffs_at_host(self._h, ctypes.byref(cb), ctypes.byref(cr), n,
+                                             idx.ctypes.data if idx is not None and n else None,
+                                             crow.ctypes.data if n else None, ctypes.byref(out),
+                                             index.ctypes.data if lists else None, tot, opts)
+            if st == 34 and cap is None and (tot[0] > caps[0] or tot[1] > caps[1]):   # HM_ERR_NOMEM: sized by the totals
+                caps = (int(tot[0]), int(tot[1]))
+                continue
+            break
+        self._check(st, "hm_op_diffs_at_host")
+        base = (rows[:int(tot[0])], surv[:int(tot[1])], rng[:n], fl[:n])
+        return base + (index[:int(tot[0])],) if lists else base
+
+    def op_diffs_at_work_bytes(self, cbatch: CBatch, n: int, lists=False) -> int:
+        return int(self._L.hm_op_diffs_at_work_bytes(ctypes.byref(cbatch), n, ODF_LISTS if lists else 0))
+
+    def op_diffs_at_device(self, cbatch: CBatch, cresults: CResults, n: int, doc_index: int, clock_rows: int,
+                           out: "COpDiffOut", out_summary: int, work: int, stream: int = 0, lists=False, out_index: int = 0) -> None:
+        """hm_op_diffs_at_device: the same with every table and the clock rows in device memory (pointers;
+        `work` of op_diffs_at_work_bytes(cbatch, n, lists) bytes; enqueued, not synchronised)."""
+        p = lambda x: ctypes.c_void_p(x) if x else None
+        self._check(self._L.hm_op_diffs_at_device(self._h, ctypes.byref(cbatch), ctypes.byref(cresults), n, p(doc_index),
+                                                  p(clock_rows), ctypes.byref(out), p(out_index), p(out_summary), p(work),
+                                                  p(stream), ODF_LISTS if lists else 0),
+                    "hm_op_diffs_at_device")
 
     def small_occupancy(self, batch: Batch) -> Sequence[int]:
         """(resident one-wave workgroups per CU, CUs, op rows per lane, size class, lists, counters) of

@@ -381,6 +381,19 @@ function plainOf(view, uuid) {
   for (const [k, e] of ov.keys) o[k] = val(e)
   return o
 }
+// {actorId: seq} per request as the entry tables docsetMaterialize and docsetMaterializePatchAt take
+function clockEntries(clocks) {
+  const eoff = new Uint32Array(clocks.length + 1)
+  const names = [], seqs = []
+  clocks.forEach((clock, j) => {
+    const c = plainClock(clock)
+    for (const a of Object.keys(c)) { names.push(Buffer.from(a, 'utf8')); seqs.push(Number(c[a])) }
+    eoff[j + 1] = names.length
+  })
+  const aoff = new Uint32Array(names.length + 1)
+  names.forEach((b, k) => { aoff[k + 1] = aoff[k] + b.length })
+  return [eoff, Buffer.concat(names), aoff, Float64Array.from(seqs)]
+}
 function materializeAtMany(ds, ids, reqs) {
   const out = new Array(ids.length)
   const byHist = [], byClock = []
@@ -393,17 +406,8 @@ function materializeAtMany(ds, ids, reqs) {
     take(byHist, addon.docsetMaterialize(ds, Uint32Array.from(byHist.map((i) => ids[i])), hl, null, null, null, null))
   }
   if (byClock.length) {
-    const eoff = new Uint32Array(byClock.length + 1)
-    const names = [], seqs = []
-    byClock.forEach((i, j) => {
-      const c = plainClock(reqs[i].clock)
-      for (const a of Object.keys(c)) { names.push(Buffer.from(a, 'utf8')); seqs.push(Number(c[a])) }
-      eoff[j + 1] = names.length
-    })
-    const aoff = new Uint32Array(names.length + 1)
-    names.forEach((b, k) => { aoff[k + 1] = aoff[k] + b.length })
-    take(byClock, addon.docsetMaterialize(ds, Uint32Array.from(byClock.map((i) => ids[i])), null, eoff, Buffer.concat(names),
-      aoff, Float64Array.from(seqs)))
+    take(byClock, addon.docsetMaterialize(ds, Uint32Array.from(byClock.map((i) => ids[i])), null,
+      ...clockEntries(byClock.map((i) => reqs[i].clock))))
   }
   return out
 }
@@ -626,7 +630,11 @@ class GpuEngine {
   // patch: null (an element's diff needs its index at that moment): the caller replays that one on
   // the host.  With { lists: true } the element diffs (insert / set / remove at the index of that
   // moment) come from the device as well and no document applied through this engine gets patch:
-  // null.  Reflects the rounds already applied: in 'async' mode await idle() first.
+  // null.  reqs[i] = {state | id, clock: {actorId: seq}} instead: the patch of the document as it stood
+  // at that clock (loadDocument at a cursor: each actor's changes up to that seq, applied from
+  // Backend.init()), per request {history, queued, patch} with queued = the selected changes whose
+  // ancestors the clock leaves out; the diffs come in the resident history order.
+  // Reflects the rounds already applied: in 'async' mode await idle() first.
   materializePatch(reqs, opts) {
     const lists = !!(opts && opts.lists)
     const states = reqs.map((r) => r.state || this.stateOf(r.id))
@@ -635,10 +643,19 @@ class GpuEngine {
       const at = []
       states.forEach((st, i) => { if (st.shard === k) at.push(i) })
       if (!at.length) return
-      const hl = Uint32Array.from(at.map((i) => Math.min(Math.max(Math.floor(Number(reqs[i].history) || 0), 0), 0xffffffff)))
-      const ids = Uint32Array.from(at.map((i) => states[i].id))
-      const got = JSON.parse(lists ? addon.docsetMaterializePatchEx(ds, ids, hl, 1) : addon.docsetMaterializePatch(ds, ids, hl))
-      at.forEach((i, j) => { out[i] = { history: got[j].history, patch: got[j].patch } })
+      const byHist = at.filter((i) => reqs[i].clock === undefined || reqs[i].clock === null)
+      const byClock = at.filter((i) => !(reqs[i].clock === undefined || reqs[i].clock === null))
+      if (byHist.length) {
+        const hl = Uint32Array.from(byHist.map((i) => Math.min(Math.max(Math.floor(Number(reqs[i].history) || 0), 0), 0xffffffff)))
+        const ids = Uint32Array.from(byHist.map((i) => states[i].id))
+        const got = JSON.parse(lists ? addon.docsetMaterializePatchEx(ds, ids, hl, 1) : addon.docsetMaterializePatch(ds, ids, hl))
+        byHist.forEach((i, j) => { out[i] = { history: got[j].history, patch: got[j].patch } })
+      }
+      if (byClock.length) {
+        const ids = Uint32Array.from(byClock.map((i) => states[i].id))
+        const got = JSON.parse(addon.docsetMaterializePatchAt(ds, ids, ...clockEntries(byClock.map((i) => reqs[i].clock)), lists ? 1 : 0))
+        byClock.forEach((i, j) => { out[i] = { history: got[j].history, queued: got[j].queued, patch: got[j].patch } })
+      }
     })
     return out
   }
@@ -1183,7 +1200,11 @@ class DocBackend {
   // device from the resident log.  patch is null when the prefix assigns list / text elements:
   // that prefix is replayed on the host (INTEGRATION.md), unless { lists: true } asks the device
   // for the element diffs too.  undefined before init.
-  materializePatchAt(n, opts) { return this.back ? this.engine.materializePatch([{ state: this.back, history: n }], opts)[0] : undefined }
+  materializePatchAt(nOrClock, opts) {
+    if (!this.back) return undefined
+    const at = nOrClock !== null && typeof nOrClock === 'object' ? { clock: nOrClock.clock } : { history: nOrClock }
+    return this.engine.materializePatch([Object.assign({ state: this.back }, at)], opts)[0]
+  }
 
   // changes: Change objects (the reference's), or raw hypercore blocks / JSON texts of them
   applyRemoteChanges(changes) { this.remoteChangesQ.push(changes) }

@@ -1109,6 +1109,38 @@ static napi_value DocsetMaterializePatch(napi_env env, napi_callback_info info) 
  * is left to a document that assigns list elements without its lists hint */
 static napi_value DocsetMaterializePatchEx(napi_env env, napi_callback_info info) { return materialize_patch(env, info, 1); }
 
+/* docsetMaterializePatchAt(docset, ids Uint32Array, entryOff Uint32Array [n + 1], actorIds Buffer,
+ * actorOff Uint32Array [entries + 1], seqs Float64Array, opts) -> JSON text, per request {"doc", "history",
+ * "queued", "patch"}: the patch of the document as it stood at a clock, given as docsetMaterialize takes
+ * one (hm_docset_materialize_patch_at; opts as docsetMaterializePatchEx) */
+static napi_value DocsetMaterializePatchAt(napi_env env, napi_callback_info info) {
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return NULL;
+    Docset *d = get_docset(env, argv[0]);
+    if (!d) return NULL;
+    const uint32_t opts = get_u32(env, argv[6]);
+    void *p[5]; size_t len[5];
+    for (int i = 0; i < 5; i++)
+        if (!get_bytes(env, argv[1 + i], &p[i], &len[i])) return NULL;
+    const uint32_t n = (uint32_t)(len[0] / 4);
+    const uint32_t *eoff = (const uint32_t *)p[1], *aoff = (const uint32_t *)p[3];
+    const uint32_t zero[1] = {0};
+    int ok = eoff != NULL && len[1] / 4 == (size_t)n + 1 && eoff[0] == 0;
+    const uint32_t ne = ok ? eoff[n] : 0;
+    ok = ok && len[4] / 8 >= ne && (ne == 0 || (len[3] / 4 >= (size_t)ne + 1 && aoff[ne] <= len[2]));
+    if (!ok) { napi_throw_type_error(env, NULL, "docsetMaterializePatchAt: clock entries whose table lengths agree"); return NULL; }
+    hm_text *t = NULL;
+    int st = hm_docset_materialize_patch_at(d->ds, n, (const uint32_t *)p[0], eoff, p[2] ? (const char *)p[2] : "",
+                                            ne ? aoff : zero, ne ? (const double *)p[4] : NULL, opts, &t);
+    if (st) return throw_status(env, d->engine, st, "hm_docset_materialize_patch_at");
+    size_t tl = 0;
+    const char *s = hm_text_data(t, &tl);
+    napi_value js;
+    napi_create_string_utf8(env, s, tl, &js);
+    hm_text_free(t);
+    return js;
+}
+
 /* docsetInfo(docset, doc) ->{aStride, nChanges, nOps, nActors, nObjs, nRegs, histLen, nQueued} */
 static napi_value DocsetInfo(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -1375,7 +1407,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"docsetCreate", DocsetCreate}, {"docsetOpen", DocsetOpen}, {"docsetApply", DocsetApply}, {"docsetApplyPacked", DocsetApplyPacked},
         {"docsetHistoryPrefix", DocsetHistoryPrefix}, {"docsetClockUpdate", DocsetClockUpdate},
         {"docsetView", DocsetView}, {"docsetBlocked", DocsetBlocked}, {"docsetWaiting", DocsetWaiting},
-        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetFields", DocsetFields}, {"docsetMaterialize", DocsetMaterialize}, {"docsetMaterializePatch", DocsetMaterializePatch}, {"docsetMaterializePatchEx", DocsetMaterializePatchEx}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
+        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetFields", DocsetFields}, {"docsetMaterialize", DocsetMaterialize}, {"docsetMaterializePatch", DocsetMaterializePatch}, {"docsetMaterializePatchEx", DocsetMaterializePatchEx}, {"docsetMaterializePatchAt", DocsetMaterializePatchAt}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
         {"cursorsCreate", CursorsCreate}, {"cursorsReserve", CursorsReserve}, {"cursorsUpdate", CursorsUpdate},
         {"cursorsGet", CursorsGet}, {"cursorsEntry", CursorsEntry}, {"cursorsDocsWithActors", CursorsDocsWithActors},
         {"syncRanges", SyncRanges}, {"decodeBlocks", DecodeBlocks}, {"commCreateLocalDocsets", CommCreateLocalDocsets},

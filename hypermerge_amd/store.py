@@ -639,6 +639,38 @@ class DocStore:
         base = (rows[:int(tot[0])], surv[:int(tot[1])], rng[:n], fl[:n])
         return base + (index[:int(tot[0])],) if lists else base
 
+    def op_diff_sizes_at(self, handles, clocks, lists=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """hm_store_op_diff_sizes_at: op_diff_sizes for op_diffs_at's requests."""
+        hs = np.ascontiguousarray(handles, np.uint32)
+        n = len(hs)
+        _, rows = self._selector(hs, None, clocks)
+        cnt, fl, tot = np.zeros((max(n, 1), 2), np.uint32), np.zeros(max(n, 1), np.uint32), np.zeros(2, np.uint64)
+        self._check(self._L.hm_store_op_diff_sizes_at(self._h, n, _p(hs), _p(rows), _p(cnt), _p(fl), _p(tot), 1 if lists else 0),
+                    "hm_store_op_diff_sizes_at")
+        return cnt[:n], fl[:n], tot
+
+    def op_diffs_at(self, handles, clocks, cap=None, lists=False):
+        """hm_store_op_diffs_at: the per-op patch of the documents `handles` (a handle may repeat) as they
+        stood at the clocks clocks[i] (an [n, S] array of rank-indexed rows, or {actorId: seq} per
+        request, as materialize takes them): what each op of the changes applied at that clock did,
+        from the empty document, in the resident history order.  Returns what op_diffs returns (with
+        lists=True the index table as a fifth element).  cap = (rows, survivors) the tables hold; None:
+        the sizes are asked first."""
+        from .engine import COpDiffOut, OP_DIFF_DT
+        hs = np.ascontiguousarray(handles, np.uint32)
+        n = len(hs)
+        _, crow = self._selector(hs, None, clocks)
+        if cap is None:
+            cap = tuple(int(x) for x in self.op_diff_sizes_at(hs, crow, lists)[2]) if n else (0, 0)
+        rows, surv = np.zeros(max(cap[0], 1), OP_DIFF_DT), np.zeros(max(cap[1], 1), SURV_RESULT_DT)
+        rng, fl = np.zeros((max(n, 1), 2), np.uint32), np.zeros(max(n, 1), np.uint32)
+        tot, index = np.zeros(2, np.uint64), np.zeros(max(cap[0], 1), np.uint32)
+        out = COpDiffOut(cap[0], cap[1], rows.ctypes.data, surv.ctypes.data, rng.ctypes.data, fl.ctypes.data)
+        self._check(self._L.hm_store_op_diffs_at(self._h, n, _p(hs), _p(crow), ctypes.byref(out),
+                                                 _p(index) if lists else None, _p(tot), 1 if lists else 0), "hm_store_op_diffs_at")
+        base = (rows[:int(tot[0])], surv[:int(tot[1])], rng[:n], fl[:n])
+        return base + (index[:int(tot[0])],) if lists else base
+
     def set_min_clock(self, h: int, clock: Dict[str, int]) -> None:
         """minimumClock (actor id -> seq); its actors must already be in the document's actor table."""
         e = self.enc[h]

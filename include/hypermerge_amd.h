@@ -696,6 +696,37 @@ int hm_op_diffs_host_ex(hm_engine *e, const hm_batch *b, const hm_results *r, ui
                         const uint32_t *from, const uint32_t *to, const hm_op_diff_out *out, uint32_t *out_index,
                         uint64_t *out_totals, uint32_t opts);
 
+/* The same rows for a document as it stood at a clock (RepoBackend's loadDocument at a cursor: each
+ * actor's changes.slice(0, cursor[actor])) instead of a history slice.  Request i = (doc_handles[i],
+ * clock_rows[i * a_stride ..]): per actor rank the largest seq selected, as hm_store_materialize's
+ * clock selector takes it.  A change is applied at clock K when it is applied in the resident
+ * document, its seq <= K[its actor] and every entry of its causal past (its all_deps row) is <= K:
+ * exactly what applyChanges(Backend.init(), the selected changes) applies; the other selected
+ * changes are hm_store_materialize's n_queued and contribute nothing.  The rows are the whole patch
+ * from the empty document: every applied-at-K op is in range, and a register's survivors, a counter's
+ * value and an element's index count the applied-at-K ops alone.  Row order is the resident history
+ * order restricted to those changes (as for hm_store_materialize's clock selector), not loadDocument's
+ * actor-major hand-over order; both lead a frontend to the same document.  The all-zero clock gives
+ * no rows; a clock at or above every seq gives the call over [0, history size).  A handle may repeat
+ * with different clocks.
+ * Outputs, request-order layout, out_index, flags, HM_ERR_NOMEM with exact totals, HM_ERR_INVALID and
+ * the refusal between submit and wait are those of the _ex calls; opts takes HM_ODF_LISTS only
+ * (HM_ODF_ONCE: HM_ERR_INVALID, hm_op_diffs_at_work_bytes 0).  Nothing is re-merged: a select phase
+ * per request leaves a bit per log change in the wave's work memory and the walk reads it. */
+int hm_store_op_diff_sizes_at(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *clock_rows,
+                              uint32_t *out_counts, uint32_t *out_flags, uint64_t *out_totals, uint32_t opts);
+int hm_store_op_diffs_at(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *clock_rows,
+                         const hm_op_diff_out *out, uint32_t *out_index, uint64_t *out_totals, uint32_t opts);
+/* Over a merged cold batch, as hm_op_diffs_device_ex / _host_ex: clock_rows [n * b->a_stride] in
+ * device (_device) or host (_host) memory; `work` of hm_op_diffs_at_work_bytes(b, n, opts) bytes. */
+size_t hm_op_diffs_at_work_bytes(const hm_batch *b, uint32_t n, uint32_t opts);
+int hm_op_diffs_at_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                          const uint32_t *clock_rows, const hm_op_diff_out *out, uint32_t *out_index,
+                          hm_op_diff_summary *out_summary, void *work, void *stream, uint32_t opts);
+int hm_op_diffs_at_host(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                        const uint32_t *clock_rows, const hm_op_diff_out *out, uint32_t *out_index,
+                        uint64_t *out_totals, uint32_t opts);
+
 /* The fields a proposed local change touches (the undo bookkeeping of Automerge 0.12
  * applyLocalChange, src/DocBackend.ts:187-205: applyAssign's recordUndo reads fieldOps of every
  * (obj, key) the request assigns and tests isConcurrent against the request), read off the resident
@@ -1003,6 +1034,17 @@ int hm_docset_materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs,
  * project produces. */
 int hm_docset_materialize_patch_ex(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, uint32_t opts,
                                    hm_text **out);
+/* The patch of a document as it stood at a clock (the patch loadDocument sends when it opens a document
+ * at a cursor, src/RepoBackend.ts:238-257): the clocks are given as hm_docset_materialize takes them
+ * (entries entry_off[i] .. entry_off[i+1] of request i, actor id strings, an id the document has never
+ * seen is dropped).  Per request {"doc", "history": changes applied at the clock, "queued": selected
+ * but not applied, "patch": {clock, deps, canUndo: false, canRedo: false, diffs}}: clock and deps from
+ * hm_store_materialize at that clock, the diffs rendered from hm_store_op_diffs_at's rows, in the
+ * resident history order (not loadDocument's actor-major hand-over order; both lead a frontend to
+ * the same document).  opts, "host": true, the empty patch of a document not placed yet and the
+ * refusals are those of hm_docset_materialize_patch_ex. */
+int hm_docset_materialize_patch_at(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off, const char *actor_ids,
+                                   const uint32_t *actor_off, const double *seqs, uint32_t opts, hm_text **out);
 /* the merged document: {uuid: {"type", "keys": [[key, entry]], "elems": [[elemId, entry]]}} */
 int hm_docset_view(hm_docset *ds, uint32_t doc, hm_text **out);
 /* counters: calls, documents, class moves, net patches from the hit registers, net patches from every

@@ -33,6 +33,19 @@ request sets, taken alternately with the two-pass legs:
   once_retry_*  the same after a call whose tables were too small (a wrong guess: two walks)
 `once_sets` records the one-walk totals (the row total is the ops of the slices, an upper bound).
 
+--at-clock times the clock-selected call instead, on whichever stores the other options chose: one request
+per document, its clock the causal past of the change in the middle of its history (that change's
+all_deps row with its own seq: closed, and in general no history prefix).  Legs:
+  at_sizes      hm_store_op_diff_sizes_at, totals only
+  at_diffs      hm_store_op_diffs_at into pageable host tables
+  at_baseline   the route the parent commit offers for the same answer: hm_store_materialize at the clock
+                (select, gather and re-merge on the device, every table copied back) followed by
+                hm_op_diffs_host_ex over the gathered batch's whole history
+  prefix_diffs  hm_store_op_diffs(_ex) over [0, middle + 1) of the same documents: the walk over the same
+                number of tiles without the select phase (it answers more changes than the clock does:
+                `sets` records both), the nearest the host clock comes to the select phase's share
+The baseline's rows are checked against the call's (kinds and survivor counts, row for row).
+
 Prints one JSON line."""
 import argparse
 import ctypes
@@ -59,6 +72,7 @@ def main():
     ap.add_argument("--c5-docs", type=int, default=100_000)
     ap.add_argument("--c3-docs", type=int, default=500)
     ap.add_argument("--once", action="store_true", help="add the one-walk legs (HM_ODF_ONCE)")
+    ap.add_argument("--at-clock", action="store_true", help="the clock-selected legs instead (hm_store_op_diffs_at)")
     args = ap.parse_args()
     from hypermerge_amd import synth
     from hypermerge_amd.engine import Engine
@@ -73,7 +87,7 @@ def main():
     res = run(args, eng, synth.generate(synth.config("C4", n_docs=args.docs), threads=min(16, os.cpu_count() or 1)), 1 if args.ex else 0, note)
     res["opts"] = "HM_ODF_LISTS" if args.ex else 0
     print(json.dumps(res))
-    assert res["tail_equal"]
+    assert res.get("tail_equal", True) and res.get("baseline_equal", True)
 
 
 def run(args, eng, b, opts, note):
@@ -106,6 +120,8 @@ def run(args, eng, b, opts, note):
         rounds += 1
     note(f"{rounds} rounds fed")
 
+    if args.at_clock:
+        return run_at_clock(args, eng, b, st, hist_len, opts, rounds)
     hs = np.arange(n, dtype=np.uint32)
     sets = {"full": (np.zeros(n, np.uint32), hist_len.copy()), "last": (before, hist_len.copy())}
     L, p = st._L, lambda a: a.ctypes.data      # noqa: E731
@@ -182,6 +198,81 @@ def run(args, eng, b, opts, note):
         out[name]["rows_by_kind"] = [int(x) for x in np.bincount(k[0]["kind"][:out[name]["rows"]], minlength=6)]
     res = {"docs": n, "a_stride": S, "rounds": rounds, "log_changes": int(nch.sum()), "log_ops": int(len(b.ops)),
            "reps": args.reps, "warmup": args.warmup, "tail_equal": ok, "sets": out}
+    for name, v in ms.items():
+        res[name] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v), "runs_ms": [round(x, 3) for x in v]}
+    return res
+
+
+def run_at_clock(args, eng, b, st, hist_len, opts, rounds):
+    """the --at-clock legs over the resident store st of b's documents"""
+    from hypermerge_amd.columnar import SURV_RESULT_DT
+    from hypermerge_amd.engine import OP_DIFF_DT, COpDiffOut
+    from hypermerge_amd.store import CPastOut
+    n, S = b.n_docs, b.a_stride
+    L, p = st._L, lambda a: a.ctypes.data      # noqa: E731
+    hs = np.arange(n, dtype=np.uint32)
+    # each document's clock: the causal past of the change at the middle history position
+    mid = (hist_len // 2).astype(np.uint32)
+    to = np.minimum(mid + 1, hist_len).astype(np.uint32)
+    off = np.zeros(n + 1, np.uint32)
+    np.cumsum((to.astype(np.int64) - mid).clip(0), out=off[1:])
+    hlog, had = np.zeros(max(int(off[-1]), 1), np.uint32), np.zeros((max(int(off[-1]), 1), S), np.uint32)
+    assert L.hm_store_read_history(st._h, n, p(hs), p(mid), p(to), p(off), p(hlog), p(had)) == 0
+    K = np.zeros((n, S), np.uint32)
+    have = np.nonzero(to > mid)[0]
+    K[have] = had[off[have]]
+    ch = b.changes[b.docs["change_off"][have].astype(np.int64) + hlog[off[have]]]
+    K[have, ch["actor"]] = ch["seq"]
+    zero = np.zeros(n, np.uint32)
+
+    def tables(tr, ts):
+        rows, surv = np.zeros(max(tr, 1), OP_DIFF_DT), np.zeros(max(ts, 1), SURV_RESULT_DT)
+        rg, flg, index = np.zeros(2 * n, np.uint32), np.zeros(n, np.uint32), np.zeros(max(tr, 1), np.uint32)
+        return rows, surv, rg, flg, index, COpDiffOut(tr, ts, p(rows), p(surv), p(rg), p(flg))
+    t2 = np.zeros(2, np.uint64)
+    cnt, fl, tot = st.op_diff_sizes_at(hs, K, lists=bool(opts))
+    A = tables(int(tot[0]), int(tot[1]))
+    _, _, ptot = st.op_diff_sizes(hs, zero, to, lists=bool(opts))
+    P = tables(int(ptot[0]), int(ptot[1]))
+    gb, gr, clog, olog = st.materialize(hs, clocks=K)           # (sizes the baseline's tables)
+    pout = CPastOut(len(gb.changes), len(gb.deps), len(gb.ops), len(gr.regs), p(gb.docs), p(gb.changes), p(gb.deps), p(gb.ops),
+                    p(clog), p(olog), gr.c_struct())
+    B = tables(int(tot[0]), int(tot[1]))
+    cb, cr, hl = gb.c_struct(), gr.c_struct(), np.ascontiguousarray(gr.docs["hist_len"], np.uint32)   # (the same every run)
+    sets = {"requests": n, "applied_at_clock": int(gr.docs["hist_len"].sum()), "queued_at_clock": int(gr.docs["n_queued"].sum()),
+            "prefix_positions": int(to.sum()), "rows": int(tot[0]), "survivors": int(tot[1]), "flagged": int((fl != 0).sum()),
+            "prefix_rows": int(ptot[0]), "gathered_changes": len(gb.changes), "gathered_ops": len(gb.ops)}
+
+    def at_sizes():
+        assert L.hm_store_op_diff_sizes_at(st._h, n, p(hs), p(K), None, None, p(t2), opts) == 0
+
+    def at_diffs():
+        assert L.hm_store_op_diffs_at(st._h, n, p(hs), p(K), ctypes.byref(A[5]), p(A[4]), p(t2), opts) == 0
+
+    def at_baseline():
+        assert L.hm_store_materialize(st._h, n, p(hs), None, p(K), ctypes.byref(pout), None) == 0
+        assert L.hm_op_diffs_host_ex(eng._h, ctypes.byref(cb), ctypes.byref(cr), n, None, p(zero), p(hl), ctypes.byref(B[5]), p(B[4]), p(t2), opts) == 0
+
+    def prefix_diffs():
+        if opts:
+            assert L.hm_store_op_diffs_ex(st._h, n, p(hs), p(zero), p(to), ctypes.byref(P[5]), p(P[4]), p(t2), opts) == 0
+        else:
+            assert L.hm_store_op_diffs(st._h, n, p(hs), p(zero), p(to), ctypes.byref(P[5]), p(t2)) == 0
+    legs = [("at_sizes", at_sizes), ("at_diffs", at_diffs), ("at_baseline", at_baseline), ("prefix_diffs", prefix_diffs)]
+    for _ in range(args.warmup):
+        for _, f in legs:
+            f()
+    ms = {name: [] for name, _ in legs}
+    for _ in range(args.reps):
+        for name, f in legs:
+            t0 = time.perf_counter()
+            f()
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+    tr = int(tot[0])
+    same = bool((A[2] == B[2]).all() and (A[0]["kind"][:tr] == B[0]["kind"][:tr]).all() and (A[0]["n_surv"][:tr] == B[0]["n_surv"][:tr]).all() and
+                (A[4][:tr] == B[4][:tr]).all())
+    res = {"docs": n, "a_stride": S, "rounds": rounds, "log_changes": int(b.docs["n_changes"].sum()), "log_ops": int(len(b.ops)),
+           "reps": args.reps, "warmup": args.warmup, "baseline_equal": same, "sets": sets}
     for name, v in ms.items():
         res[name] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v), "runs_ms": [round(x, 3) for x in v]}
     return res

@@ -17,6 +17,15 @@ from missing_changes_ref import closure
 NONE = 0xFFFFFFFF
 
 
+def js_key_order(obj):
+    """The (key, value) pairs of a dict in the order Object.keys lists a JS object's: the keys that
+    are canonical array indices (an actor id written in decimal digits only, such as "19613698", is
+    one) ascending by number, then the others in insertion order."""
+    index = lambda k: k.isdigit() and str(int(k)) == k and int(k) < 0xFFFFFFFF
+    return sorted(((k, v) for k, v in obj.items() if index(k)), key=lambda kv: int(kv[0])) + \
+        [(k, v) for k, v in obj.items() if not index(k)]
+
+
 def base_entries(rank, actor, seq, deps):
     """The entries of the would-be change (actor, seq, deps {actorId: seq}): base = {...deps};
     base[actor] = seq - 1 in JS key order, over the ranks in ``rank`` ({actorId: rank}).  Returns
@@ -24,7 +33,7 @@ def base_entries(rank, actor, seq, deps):
     base = dict(deps)
     base[actor] = seq - 1                      # (keeps its place when deps names it, else goes last)
     ents, unknown = [], False
-    for a, q in base.items():
+    for a, q in js_key_order(base):
         if a in rank:
             ents.append((rank[a], int(q)))
         elif q > 0:

@@ -319,3 +319,53 @@ def gen_doc(seed, n_actors=None, n_changes=None, fault=None, profile="default"):
 
 def gen_docs(profile, seeds, **kw):
     return [gen_doc(s, profile=profile, **kw) for s in seeds]
+
+
+def withheld(chs, seed):
+    """(kept, dropped): a delivery that never brings one to three of the document's changes (never
+    all of them).  ``kept`` is the arrival list without any copy of the chosen (actor, seq), so every
+    change that depends on one of them stays queued; ``dropped`` is one copy of each, sorted by
+    (actor, seq): a frontend's changes that have not arrived yet."""
+    rng = random.Random(seed)
+    names = sorted({(c["actor"], c["seq"]) for c in chs})
+    k = min(rng.randint(1, 3), len(names) - 1)
+    gone = set(rng.sample(names, k))
+    kept = [c for c in chs if (c["actor"], c["seq"]) not in gone]
+    first = {}
+    for c in chs:
+        first.setdefault((c["actor"], c["seq"]), c)
+    return kept, [first[n] for n in sorted(gone)]
+
+
+def base_clock(c):
+    """A change as a would-be local change: its base clock by actor id, {...deps}; base[actor] = seq - 1."""
+    base = dict(c["deps"])
+    base[c["actor"]] = c["seq"] - 1
+    return base
+
+
+def assigned(c):
+    """The (obj, key) of a change's set / del / link / inc ops, each once, in op order."""
+    out = []
+    for op in c["ops"]:
+        if op["action"] in ("set", "del", "link", "inc") and (op["obj"], op["key"]) not in out:
+            out.append((op["obj"], op["key"]))
+    return out
+
+
+def quiet_tail(chs, k=3):
+    """(head, tail): up to k changes that can arrive in a round of their own once everything else
+    has been applied, without a new actor, a new object or a change left waiting — what a resident
+    store may apply incrementally.  A tail change is the last of its actor (not the actor's first),
+    no other change depends on it, and it makes no object; head is the arrival list without any copy
+    of the tail changes.  The tail changes are concurrent, so they apply in any order."""
+    top, need, first = {}, {}, {}
+    for c in chs:
+        first.setdefault((c["actor"], c["seq"]), c)
+        top[c["actor"]] = max(top.get(c["actor"], 0), c["seq"])
+        for a, q in c["deps"].items():
+            need[a] = max(need.get(a, 0), q)
+    final = [n for n in sorted(first) if n[1] == top[n[0]] and n[1] > 1 and need.get(n[0], 0) < n[1]
+             and not any(op["action"] in MAKES.values() for op in first[n]["ops"])]
+    tail = set(final[:k])
+    return [c for c in chs if (c["actor"], c["seq"]) not in tail], [first[n] for n in sorted(tail)]

@@ -2,7 +2,8 @@
 // The fields a proposed change touches, answered by the JS restatement (oracle/js/backend.js) itself:
 // stdin {docs: [{changes: [...], reqs: [{actor, seq, deps, fields: [[obj, key], ...]}]}]}.  Per request
 // the document is rebuilt from its changes; each field's current ops are read (what fieldOps copies:
-// obj.keys.get(key), winner first), then the would-be change is applied with one `del` per field: a
+// obj.keys.get(key), winner first), the document's queue is emptied (a would-be change that is not
+// ready is then the queue's only entry), then the would-be change is applied with one `del` per field: a
 // del keeps exactly the ops that isConcurrent with it, so an op that is gone afterwards is covered.
 // ready = the change was applied, not queued (causallyReady).  The fields of a request are distinct.
 // Printed: {docs: [[{ready, fields: [[{action, value, datatype?, actor, seq, covered}]]}]]}
@@ -19,6 +20,9 @@ process.stdin.on('end', () => {
     const cur = (obj, key) => { const o = s.objs.get(obj); return o ? o.keys.get(key) || [] : [] }
     const before = req.fields.map(([obj, key]) => cur(obj, key).slice())
     const ops = req.fields.filter(([obj]) => s.objs.has(obj)).map(([obj, key]) => ({ action: 'del', obj, key }))
+    // the answer is about the would-be change alone: changes of the document that wait for its
+    // (actor, seq) must not apply behind it (they would rewrite the fields, or name what its real ops make)
+    s.queue = []
     J.Backend.applyChanges(s, [{ actor: req.actor, seq: req.seq, deps: req.deps, ops }])
     const ready = (s.clock.get(req.actor) || 0) === req.seq
     const fields = req.fields.map(([obj, key], f) => {

@@ -147,17 +147,11 @@ def requests_for(b, o, d, rng, k):
     return out
 
 
-@pytest.mark.skipif(NODE is None, reason="node not installed")
-@pytest.mark.parametrize("name,n,kw", [("C2", 12, {"arrival": 2, "shuffle_pct": 30}), ("C3", 4, {"changes_per_actor": 15}),
-                                       ("C5", 12, {})])
-def test_reference_matches_js_restatement(name, n, kw):
-    b0 = synth.generate(synth.config(name, n_docs=n, **kw), threads=2)
-    docs = [decode_doc(b0, i) for i in range(b0.n_docs)]
-    b = encode(docs, 8)
-    o = O.merge(b)
-    rng = np.random.default_rng(9)
-    keep = [d for d in range(b.n_docs) if int(o.docs["status"][d]) == 0]
-    reqs = {d: requests_for(b, o, d, rng, 8) for d in keep}
+def against_js(docs, b, o, reqs):
+    """The would-be changes reqs {document: [request]} (requests_for's form) through the JS restatement
+    of applyLocalChange's bookkeeping against the reference on (b, o): ready flags and every field's
+    ops.  Returns (rows, rows not covered, requests not ready)."""
+    keep = sorted(reqs)
     payload = {"docs": [{"changes": docs[d], "reqs": [{k: r[k] for k in ("actor", "seq", "deps", "fields")} for r in reqs[d]]}
                         for d in keep]}
     p = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "run_fields.js")], input=json.dumps(payload),
@@ -172,10 +166,24 @@ def test_reference_matches_js_restatement(name, n, kw):
             ready, _, fl = doc_ref(b, o, d, ents, r["regs"])
             ready = ready and not unknown
             want = {"ready": ready, "fields": [as_ops(b, d, rows) if ready else [] for rows in fl]}
-            assert g == want, (name, d, r)
+            assert g == want, (d, r)
             n_late += not ready
             n_rows += sum(len(f) for f in want["fields"])
             n_unc += sum(1 for f in want["fields"] for x in f if not x["covered"])
+    return n_rows, n_unc, n_late
+
+
+@pytest.mark.skipif(NODE is None, reason="node not installed")
+@pytest.mark.parametrize("name,n,kw", [("C2", 12, {"arrival": 2, "shuffle_pct": 30}), ("C3", 4, {"changes_per_actor": 15}),
+                                       ("C5", 12, {})])
+def test_reference_matches_js_restatement(name, n, kw):
+    b0 = synth.generate(synth.config(name, n_docs=n, **kw), threads=2)
+    docs = [decode_doc(b0, i) for i in range(b0.n_docs)]
+    b = encode(docs, 8)
+    o = O.merge(b)
+    rng = np.random.default_rng(9)
+    keep = [d for d in range(b.n_docs) if int(o.docs["status"][d]) == 0]
+    n_rows, n_unc, n_late = against_js(docs, b, o, {d: requests_for(b, o, d, rng, 8) for d in keep})
     assert n_rows > 100 and n_unc > 10 and n_late > 5
 
 
@@ -200,6 +208,11 @@ def test_reference_on_hand_cases():
     assert base_entries(rank, A, 3, {B: 1, A: 1}) == ([(1, 1), (0, 2)], False)      # the own actor keeps its place
     assert base_entries(rank, A, 3, {B: 1}) == ([(1, 1), (0, 2)], False)            # ... or goes last
     assert base_entries(rank, Cc, 2, {})[1] and base_entries(rank, A, 3, {Cc: 1})[1]
+    # an actor id in decimal digits only is an array index to JS: Object.keys lists it first, by number
+    # (found by the fuzz documents' random hex names, tests/test_fuzz_docs.py)
+    digits = {"19613698": 0, "5a5c4689": 1, "777": 2, "0123": 3}
+    assert base_entries(digits, "5a5c4689", 7, {"5a5c4689": 2, "19613698": 3, "0123": 1, "777": 4}) == \
+        ([(2, 4), (0, 3), (1, 6), (3, 1)], False)
     # not ready: aaaa:3 is not applied
     assert doc_ref(b, o, 0, [(0, 3)], [y, x]) == (False, [0] * 8, [[], []])
 

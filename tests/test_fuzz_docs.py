@@ -16,12 +16,27 @@ from hypermerge_amd.columnar import (DEL, DT_COUNTER, INC, INS, LINK, MAKE_LIST,
 from hypermerge_amd.render import doc_state
 import oracle.oracle as O
 
-from fuzz_docs import FAULTS, gen_doc_info, gen_docs
+from clock_diffs_ref import applied_at, causal_past, selected_at
+from fields_ref import NONE as FNONE
+from fields_ref import base_entries
+from fields_ref import doc_ref as fields_doc_ref
+from fuzz_docs import FAULTS, assigned, base_clock, gen_doc_info, gen_docs, withheld
+from missing_changes_ref import closure
+from missing_changes_ref import doc_ref as changes_doc_ref
+from past_ref import source_of
 from repo_harness import plain
+from test_fields_gpu import rand_have
+from test_fields_ref import against_js as fields_against_js
+from test_fields_ref import requests_for
 from test_list_diffs_ref import _against_js as element_diffs_against_js
+from test_past_ref import prefix_replay_property
 from op_diffs_cases import sources
 from op_diffs_ref import LISTS, op_diffs, render
 from test_op_diffs_ref import _js_calls
+from waiting_ref import doc_ref as waiting_doc_ref
+
+# sha256 of a sample of gen_doc's output, as it was before withheld() was added beside it
+GEN_DOC_DIGEST = "e29921eb3f15d75b843b6b106a38b98bc72e6646d7a7697fd6c2e9dcbd06acb3"
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NODE = shutil.which("node")
@@ -160,7 +175,7 @@ def map_diffs_against_js(docs):
             whole += diffs
             at = h
         full = op_diffs(src, ad, S, 0, at + 9)
-        assert bool(full.flags & LISTS) == has_element_assigns(docs[d]), d
+        assert bool(full.flags & LISTS) == has_element_assigns([docs[d][i] for i in order], docs[d]), d   # (queued ones never ran)
         if not full.flags:
             assert render(b, d, src, full) == whole, d
     return answered
@@ -228,3 +243,181 @@ def test_census_of_the_default_documents():
     for k in ("link_under_elem", "list_in_list", "inc_counter_elem", "unassigned_elem", "table_row", "many_lists",
               "small", "large"):
         assert c[k] >= 1, (k, c)
+
+
+# ---- documents for the resident-state queries: full, and with one to three changes withheld -----
+QUERY_SETS = {"default": (range(1000, 1060), 8), "wide": (range(1100, 1112), 64), "long": (range(1200, 1204), 8)}
+
+
+@lru_cache(maxsize=None)
+def query_docs(profile):
+    """[(full arrival list, kept, dropped)] of QUERY_SETS[profile]: document i withheld with seed 7000 + i"""
+    seeds, _ = QUERY_SETS[profile]
+    out = []
+    for i, chs in enumerate(gen_docs(profile, seeds)):
+        kept, dropped = withheld(chs, 7000 + i)
+        out.append((chs, kept, dropped))
+    return tuple(out)
+
+
+@lru_cache(maxsize=None)
+def withheld_merge(profile):
+    """(batch, the oracle's merge) of the withheld documents at the profile's stride"""
+    b = encode([kept for _, kept, _ in query_docs(profile)], QUERY_SETS[profile][1])
+    return b, O.merge(b)
+
+
+def test_withheld_keeps_no_copy_of_what_it_drops_and_gen_doc_is_unchanged():
+    for profile in QUERY_SETS:
+        for chs, kept, dropped in query_docs(profile):
+            gone = [(c["actor"], c["seq"]) for c in dropped]
+            assert 1 <= len(gone) <= 3 and gone == sorted(set(gone))
+            assert kept and not any((c["actor"], c["seq"]) in gone for c in kept)
+            assert [c for c in chs if (c["actor"], c["seq"]) not in gone] == kept
+    import hashlib
+    digest = hashlib.sha256(json.dumps([gen_docs("default", range(5)), gen_docs("wide", range(2)), gen_docs("long", range(1))],
+                                       sort_keys=True).encode()).hexdigest()
+    assert digest == GEN_DOC_DIGEST, digest
+
+
+@needs_node
+@pytest.mark.parametrize("profile", ["default", "wide"])
+def test_js_restatement_matches_oracle_on_withheld_documents(profile):
+    """history, clock, state and the queued count of documents that end blocked"""
+    docs = [kept for _, kept, _ in query_docs(profile)]
+    b, r = assert_js_equals_oracle(docs)
+    assert (r.docs["status"] == 0).all() and 2 * int((r.docs["n_queued"] > 0).sum()) >= len(docs)
+
+
+def proposal(b, d, c):
+    """a dropped change as a would-be local change for document d of b (test_fields_ref.requests_for's form):
+    its base clock, and the (obj, key) of its assigns as fields"""
+    fields = [list(f) for f in assigned(c)]
+    regs = []
+    for obj, key in fields:
+        oid = b.doc_objs[d].index(obj) if obj in b.doc_objs[d] else None
+        regs.append(b.doc_regs[d].index((oid, key)) if (oid, key) in b.doc_regs[d] else FNONE)
+    assert base_entries({}, c["actor"], c["seq"], c["deps"])[1] == any(q > 0 for q in base_clock(c).values())
+    return {"actor": c["actor"], "seq": c["seq"], "deps": dict(c["deps"]), "fields": fields, "regs": regs}
+
+
+@needs_node
+def test_fields_reference_matches_js_on_fuzz_documents():
+    """12 default and 4 wide documents, full and withheld: test_fields_ref.requests_for's would-be
+    changes, and on the withheld ones every dropped change as the proposal it is."""
+    sets = [query_docs("default")[:12], query_docs("wide")[:4]]
+    docs = [chs for qs in sets for chs, _, _ in qs] + [kept for qs in sets for _, kept, _ in qs]
+    dropped = [[] for qs in sets for _ in qs] + [dr for qs in sets for _, _, dr in qs]
+    b = encode(docs, 64)
+    o = O.merge(b)
+    assert (o.docs["status"] == 0).all()
+    rng = np.random.default_rng(9)
+    reqs = {d: requests_for(b, o, d, rng, 8) + [proposal(b, d, c) for c in dropped[d]] for d in range(b.n_docs)}
+    n_rows, n_unc, n_late = fields_against_js(docs, b, o, reqs)
+    print(n_rows, n_unc, n_late)
+    assert n_rows > 1000 and n_unc > 100 and n_late > 30
+
+
+def test_closure_folds_agree():
+    """missing_changes_ref.closure (fields_ref folds with the same function) and clock_diffs_ref's
+    causal_past are both defined on one entry that names an applied change: its allDeps row with its
+    own seq.  A closed clock folded entry by entry, in any order, is itself."""
+    n = 0
+    for profile in QUERY_SETS:
+        b, o = withheld_merge(profile)
+        S = b.a_stride
+        rng = np.random.default_rng(3)
+        for d in range(b.n_docs):
+            c0, nc = int(b.docs["change_off"][d]), int(b.docs["n_changes"][d])
+            src = source_of(b, o.hist, d)
+            ad = o.all_deps[c0 * S:(c0 + nc) * S]
+            for ci in np.flatnonzero(src.hist >= 0):
+                a, q = int(src.changes[ci]["actor"]), int(src.changes[ci]["seq"])
+                past = [int(x) for x in causal_past(src, ad, S, int(ci))]
+                assert closure(src.changes, src.hist, ad, S, [(a, q)]) == past, (profile, d, ci)
+                ents = [(r, past[r]) for r in rng.permutation(S) if past[r]]
+                assert closure(src.changes, src.hist, ad, S, ents) == past, (profile, d, ci)
+                assert int(applied_at(src, ad, S, past).sum()) == int(selected_at(src, past).sum())
+                n += 1
+    assert n > 1000
+
+
+def query_requests(b, o, d, rng):
+    """six requests for document d: test_fields_gpu.rand_have entries, the sixth one past the clock"""
+    S = b.a_stride
+    clock = o.clock[d * S:(d + 1) * S]
+    return [rand_have(rng, clock, len(b.doc_actors[d]), late=j == 5) for j in range(6)]
+
+
+def query_census(profile):
+    """What the withheld documents and their requests hold, from the oracle and the references alone."""
+    b, o = withheld_merge(profile)
+    S = b.a_stride
+    rng = np.random.default_rng(1)
+    c = dict(docs=b.n_docs, status0=int((o.docs["status"] == 0).sum()), blocked=int((o.docs["n_queued"] > 0).sum()),
+             rows2=0, longest=int(o.docs["n_queued"].max()), dup=0, requests=0, late=0, order=0, rows=0, uncovered=0,
+             multi=0, partial=0, proposals=0, ready=0, assign=0, unknown=0)
+    for d in range(b.n_docs):
+        c0, nc = int(b.docs["change_off"][d]), int(b.docs["n_changes"][d])
+        changes, hist, ad = b.changes[c0:c0 + nc], o.hist[c0:c0 + nc], o.all_deps[c0 * S:(c0 + nc) * S]
+        c["rows2"] += int(np.count_nonzero(waiting_doc_ref(b, o, d)[0])) >= 2
+        c["dup"] += bool((hist == -2).any())
+        H = int((hist >= 0).sum())
+        regs = list(range(int(b.docs["n_regs"][d])))
+        for ents in query_requests(b, o, d, rng):
+            ready, _, fl = fields_doc_ref(b, o, d, ents, regs)
+            c["requests"] += 1
+            c["late"] += not ready
+            c["order"] += closure(changes, hist, ad, S, ents) != closure(changes, hist, ad, S, ents[::-1])
+            c["rows"] += sum(len(f) for f in fl)
+            c["uncovered"] += sum(1 for f in fl for r in f if not r[7])
+            c["multi"] += sum(1 for f in fl if len(f) > 1)
+            c["partial"] += 0 < len(changes_doc_ref(b, o, d, ents)[0]) < H
+        rank = {a: i for i, a in enumerate(b.doc_actors[d])}
+        for ch_ in query_docs(profile)[d][2]:
+            p = proposal(b, d, ch_)
+            ents, unknown = base_entries(rank, p["actor"], p["seq"], p["deps"])
+            c["proposals"] += 1
+            c["ready"] += fields_doc_ref(b, o, d, ents, p["regs"])[0] and not unknown
+            c["assign"] += bool(p["fields"])
+            c["unknown"] += unknown
+    return c
+
+
+@pytest.mark.parametrize("profile,order", [("default", 10), ("wide", 5), ("long", 1)])
+def test_census_of_the_withheld_documents(profile, order):
+    c = query_census(profile)
+    print(profile, c)
+    assert c["status0"] == c["docs"], c
+    assert 2 * c["blocked"] >= c["docs"] and 4 * c["rows2"] >= c["docs"] and c["dup"] >= 1, c
+    if profile == "long":
+        assert c["longest"] > 64, c
+    assert 1 <= c["late"] and 4 * c["late"] <= c["requests"], c
+    assert c["order"] >= order, c
+    assert 0 < c["uncovered"] < c["rows"], c
+    assert 4 * c["partial"] >= c["requests"], c
+    if profile == "default":
+        assert c["multi"] >= 100, c
+    assert c["unknown"] == 0, c                          # no withheld change names an actor its document never saw
+    assert 4 * c["ready"] >= c["proposals"] and 4 * (c["proposals"] - c["ready"]) >= c["proposals"], c
+    assert 4 * c["assign"] >= (2 if profile == "long" else 3) * c["proposals"], c     # (long: nine proposals in all)
+
+
+def blocked_docs():
+    """the 20 withheld default documents that go through test_fuzz_gpu's materialize and diff legs"""
+    return [kept for _, kept, _ in query_docs("default")[:20]]
+
+
+def test_prefix_replay_holds_on_blocked_documents():
+    b = encode(blocked_docs(), 8)
+    o = O.merge(b)
+    assert (o.docs["status"] == 0).all() and 2 * int((o.docs["n_queued"] > 0).sum()) >= b.n_docs and (o.hist == -2).any()
+    prefix_replay_property(b, o, every=3)
+
+
+@needs_node
+def test_python_diff_references_match_js_on_blocked_documents():
+    docs = blocked_docs()
+    kinds = element_diffs_against_js(docs)
+    assert kinds["insert"] >= 20 and kinds["set"] >= 20 and kinds["remove"] >= 5, kinds
+    assert map_diffs_against_js(docs) >= 50

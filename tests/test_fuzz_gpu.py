@@ -19,12 +19,15 @@ from hypermerge_amd.render import canonical_json
 from hypermerge_amd.store import DocStore
 import oracle.oracle as O
 
+from clock_diffs_ref import census as clock_census
+from clock_diffs_ref import clocks_of
 from fuzz_docs import gen_docs
 from list_diffs_ref import pack as pack_lists
 from op_diffs_ref import pack as pack_maps
 from past_ref import clock_at, hist_len
+from test_clock_diffs_gpu import check as check_diffs_at
 from test_docset_gpu import _blocks, _chunks, _oracle
-from test_fuzz_docs import default_docs, fault_docs
+from test_fuzz_docs import blocked_docs, default_docs, fault_docs
 from test_gpu_parity import assert_same
 from test_list_diffs_gpu import check as check_element_diffs
 from test_materialize_gpu import check as check_materialize
@@ -230,7 +233,7 @@ def test_materialize_at_past_points(fed):
     materialize_leg(*fed)
 
 
-def materialize_leg(store, hs, marks):
+def materialize_leg(store, hs, marks, min_hist=30):
     """History lengths 0, 1, a random middle, H and H + 5 of every document, then the clocks
     (past_ref.clock_at) of the same points."""
     srcs = {h: past_source(store, h) for h in hs}
@@ -242,7 +245,7 @@ def materialize_leg(store, hs, marks):
             req.append(h)
             hist.append(k)
     want, o = check_materialize(store, srcs, req, history=hist)
-    assert int(o.docs["hist_len"].max()) > 30 and (want.docs["flags"] & 1).any()
+    assert int(o.docs["hist_len"].max()) > min_hist and (want.docs["flags"] & 1).any()
     rows = np.stack([clock_at(srcs[h], store.S, k) for h, k in zip(req, hist)])
     check_materialize(store, srcs, req, clocks=rows)
 
@@ -313,3 +316,70 @@ def docset_leg(engine, docs):
             for ds in (pair.device, pair.replay):
                 assert render_objects(view_objects(ds.view(d))) == state, (i, r)
     pair.check_counters()
+
+
+# ---- documents that end blocked (fuzz_docs.withheld) through the same legs --------------------------
+@pytest.fixture(scope="module")
+def fed_blocked(engine):
+    """20 default documents, each with one to three changes withheld, fed in three rounds"""
+    store, hs, marks = feed_store(engine, blocked_docs())
+    nq = store.waiting(hs)[2]
+    assert 2 * int((nq > 0).sum()) >= len(hs), nq
+    return store, hs, marks
+
+
+def queued_clocks(store, hs, srcs):
+    """per blocked document the clock of its whole history, and the same clock naming a queued
+    change's (actor, seq): queued changes are never selected, so both select the same changes"""
+    req, plain, named = [], [], []
+    for h in hs:
+        src = srcs[h]
+        queued = np.flatnonzero(src.hist == -1)
+        if not len(queued):
+            continue
+        k = clock_at(src, store.S, hist_len(src))
+        up = k.copy()
+        for i in queued:
+            a = int(src.changes[i]["actor"])
+            up[a] = max(int(up[a]), int(src.changes[i]["seq"]))
+        assert (up != k).any()
+        req.append(h); plain.append(k); named.append(up)
+    return req, plain, named
+
+
+def test_blocked_documents_materialize(fed_blocked):
+    """History lengths and clocks come from hist_len of the blocked state.  Wall under 0.1 s."""
+    store, hs, marks = fed_blocked
+    materialize_leg(store, hs, marks, min_hist=20)
+    srcs = {h: past_source(store, h) for h in hs}
+    req, plain, named = queued_clocks(store, hs, srcs)
+    assert 2 * len(req) >= len(hs)
+    a, _ = check_materialize(store, srcs, req, clocks=np.stack(named))
+    b, _ = check_materialize(store, srcs, req, clocks=np.stack(plain))
+    for f in ("docs", "changes", "deps", "ops"):
+        assert getattr(a, f).tobytes() == getattr(b, f).tobytes(), f
+
+
+def test_blocked_documents_op_and_element_diffs(fed_blocked):
+    """Wall 0.1 s."""
+    diffs_leg(*fed_blocked)
+
+
+def test_blocked_documents_diffs_at_clocks(fed_blocked):
+    """hm_store_op_diffs_at at prefix, causal-past and cut clocks, and at the clocks that name queued
+    changes.  Wall 0.1 s."""
+    store, hs, _ = fed_blocked
+    srcs = {h: diff_source(store, h) for h in hs}
+    rng = np.random.default_rng(24)
+    req, ks = [], []
+    for h in hs:
+        for _, k in clocks_of(*srcs[h], store.S, rng):
+            req.append(h); ks.append(k)
+    n, closed, queued = clock_census([(*srcs[h], store.S, k) for h, k in zip(req, ks)])
+    assert 8 * closed >= n and 8 * queued >= n, (n, closed, queued)
+    memo = {}
+    check_diffs_at(store, srcs, req, ks, memo=memo)
+    qreq, plain, named = queued_clocks(store, hs, {h: srcs[h][0] for h in hs})
+    a = check_diffs_at(store, srcs, qreq, named, memo=memo)
+    b = check_diffs_at(store, srcs, qreq, plain, memo=memo)
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(a, b))

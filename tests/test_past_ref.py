@@ -23,16 +23,23 @@ def shuffled_docs():
 
 def test_prefix_replays_in_order_and_whole_history_is_the_full_merge():
     b = shuffled_docs()
-    S = b.a_stride
     full = O.merge(b)
     assert (full.docs["status"] == 0).all()
     assert (full.hist == -2).any() and (full.hist == -1).any()
     assert int(full.docs["n_queued"][b.n_docs - 1]) == 1
+    prefix_replay_property(b, full)
+
+
+def prefix_replay_property(b, full, every=1):
+    """Every document of b (full = the oracle's merge of it): replaying the gathered prefix k from
+    Backend.init() applies every change at once and in order, for k = 0, every, 2 * every, ..,
+    hist_len and hist_len + 5; the whole history gives the full merge's state."""
+    S = b.a_stride
     for d in range(b.n_docs):
         src = source_of(b, full.hist, d)
         H = hist_len(src)
         assert H == int(full.docs["hist_len"][d])
-        for k in list(range(H + 1)) + [H + 5]:
+        for k in list(range(0, H, every)) + [H, H + 5]:
             g, clog, olog = gather([(src, k, None)], S)
             o = O.merge(g)
             kk = min(k, H)

@@ -14,7 +14,7 @@ import oracle.oracle as O
 
 from kat_cases import ch, s
 from test_store_gpu import split
-from test_waiting_host import HAND, A, B, Cc
+from test_waiting_host import HAND, OWN_DEP_ABOVE_SEQ, A, B, Cc
 from waiting_ref import doc_ref, unmet_min
 
 pytestmark = pytest.mark.gpu
@@ -51,12 +51,13 @@ def named(store, h, row):
 
 def test_known_answers(engine):
     store = DocStore(engine, a_stride=8)
-    hs = [store.open() for _ in HAND]
+    cases = HAND + [OWN_DEP_ABOVE_SEQ]
+    hs = [store.open() for _ in cases]
     empty = store.open()
-    store.apply([(h, c[1]) for h, c in zip(hs, HAND)])
+    store.apply([(h, c[1]) for h, c in zip(hs, cases)])
     miss, unmet, nq = store.waiting(hs + [empty])
     want_blocked = []
-    for j, (h, (name, _, _, want, queue)) in enumerate(zip(hs, HAND)):
+    for j, (h, (name, _, _, want, queue)) in enumerate(zip(hs, cases)):
         assert named(store, h, miss[j]) == want, name
         assert store.queue(h) == queue, name
         assert int(nq[j]) == len(queue), name

@@ -37,6 +37,7 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 #include "../../include/hypermerge_amd.h"
 #include "engine_internal.h"
@@ -1893,6 +1894,8 @@ struct Call {
     }
 };
 
+int finish(Call &c, hm_text *out);
+
 // One call = one applyChanges round for every document of the call.  A phase that returns a
 // status fails the call: fail() undoes it on every store and rolls every document back.
 int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t *doc_block, const uint32_t *docs, uint32_t n,
@@ -1906,6 +1909,13 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
     for (uint32_t k = 0; k < N_CLASS; k++)
         if (!c.by_cls[k].empty() && (rc = c.merge_class(k))) return c.fail(rc);
     c.mark("merge");
+    return finish(c, out);
+}
+
+// the phases behind the merge: what every round's patch reads, the commit, the rendering
+int finish(Call &c, hm_text *out) {
+    hm_docset *ds = c.ds;
+    int rc;
     c.settle();
     // (the injected read failure: after the requests are built, before any read)
     if (c.inj_read) return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "injected failure (HM_DOCSET_INJECT_FAIL)"));
@@ -1930,6 +1940,167 @@ int apply(hm_docset *ds, const uint8_t *data, const uint64_t *bo, const uint32_t
     c.assemble(out);
     c.mark("render");
     return HM_OK;
+}
+
+// ---------------- fork ----------------
+uint32_t seq_u32(double v);
+// The new document d as its parent p names things: the interners and rank tables (the gathered rows
+// keep the parent's ranks, object and register ids), an empty log.
+void clone_names(DocSt &d, const DocSt &p) {
+    if (!d.ready) d.setup();
+    d.actors = p.actors; d.objs = p.objs; d.regs = p.regs; d.strs = p.strs;
+    d.rank_of = p.rank_of; d.by_rank = p.by_rank;
+}
+
+// hm_docset_fork: the new documents first + i are rounds of one Call whose rows come from the stores'
+// fork batches instead of a decode — a parent not placed yet gives a round without blocks — and whose
+// later phases (what each patch reads, commit, rendering, the replay check) are hm_docset_apply's.
+int fork_docs(hm_docset *ds, uint32_t n, const uint32_t *parents, const uint32_t *hist_len, const uint32_t *entry_off,
+              const char *actor_ids, const uint32_t *actor_off, const double *seqs, uint32_t first, hm_text *out) {
+    std::vector<uint32_t> nd(n), no_blocks(n + 1, 0);
+    for (uint32_t i = 0; i < n; i++) nd[i] = first + i;
+    Call c{ds, nullptr, nullptr, no_blocks.data(), nd.data(), n};
+    c.t0 = std::chrono::steady_clock::now();
+    c.R.resize(n);
+    std::vector<uint32_t> forks[N_CLASS];
+    ClsOut plain;                                            // the batch of the rounds without blocks
+    int rc;
+    // the new documents' host state on host threads, as a decode's (a call lists a new document once;
+    // parents are only read)
+    c.T = std::min<uint32_t>(ds->threads, std::max<uint32_t>(1, n / 64));
+    try {
+    par_for(n, c.T, [&](uint32_t lo, uint32_t hi, uint32_t) {
+        Scratch X;
+        for (uint32_t i = lo; i < hi; i++) {
+            Round &x = c.R[i];
+            DocSt &d = ds->doc(nd[i]);
+            const DocSt &p = ds->doc(parents[i]);
+            x.doc = nd[i];
+            if (p.cls == NO_CLASS) {                         // Backend.init(): an empty round of a fresh document
+                decode_round(d, x, nullptr, nullptr, X);
+                x.cls = class_for(0); x.placed = true;
+                continue;
+            }
+            clone_names(d, p);
+            x.started = true;
+            x.s_objs = 1;                                    // (the rollback leaves Backend.init(): ROOT alone)
+            x.n_actors = (uint16_t)p.actors.size(); x.n_regs = p.regs.size(); x.n_objs = p.objs.size(); x.flags = p.flags;
+            x.cls = p.cls; x.placed = true;
+        }
+    });
+    } catch (...) {
+        return c.fail(hm_engine_fail(ds->e, HM_ERR_NOMEM, "out of memory in hm_docset_fork"));
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        if (ds->doc(parents[i]).cls == NO_CLASS) c.by_cls[c.R[i].cls].push_back(i);
+        else forks[c.R[i].cls].push_back(i);
+    }
+    for (uint32_t k = 0; k < N_CLASS; k++) {
+        if (c.by_cls[k].empty()) continue;
+        if ((rc = c.merge_class(k))) return c.fail(rc);
+        // (nothing of this batch needs an undo: its documents are fresh and empty, fail() releases their handles)
+        plain = std::move(c.co[k]);
+        c.co[k] = ClsOut();
+        c.by_cls[k].clear();
+    }
+    for (uint32_t k = 0; k < N_CLASS; k++) {
+        if (forks[k].empty()) continue;
+        c.by_cls[k] = forks[k];
+        const auto &rows = c.by_cls[k];
+        const uint32_t S = STRIDES[k], m = (uint32_t)rows.size();
+        hm_store *st = ds->stores[k];
+        std::vector<uint32_t> fh, src(m), sel, ord;
+        if ((rc = c.take_handles(k, st, m, fh))) return c.fail(rc);
+        if (hist_len) sel.resize(m); else { sel.assign((size_t)m * S, 0u); ord.assign((size_t)m * S, HM_NONE); }
+        for (uint32_t j = 0; j < m; j++) {
+            const uint32_t i = rows[j];
+            Round &x = c.R[i];
+            const DocSt &p = ds->doc(parents[i]);
+            x.handle = fh[j]; x.fresh = true; x.row = j;
+            src[j] = p.handle;
+            if (hist_len) { sel[j] = hist_len[i]; continue; }
+            uint32_t *row = sel.data() + (size_t)j * S, *orow = ord.data() + (size_t)j * S, listed = 0;
+            for (uint32_t e = entry_off[i]; e < entry_off[i + 1]; e++) {
+                if (actor_off[e + 1] < actor_off[e]) return c.fail(hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease"));
+                const uint32_t a = p.actors.find(actor_ids + actor_off[e], actor_off[e + 1] - actor_off[e], 0);
+                if (a == HM_NONE || a >= p.rank_of.size() || p.rank_of[a] >= S) continue;   // (an actor the parent has never seen)
+                const uint32_t r = p.rank_of[a];
+                bool again = false;
+                for (uint32_t q = 0; q < listed && !again; q++) again = orow[q] == r;
+                if (!again) orow[listed++] = r;
+                row[r] = seq_u32(seqs[e]);
+            }
+        }
+        ClsOut &O = c.co[k];
+        if ((rc = hm_store_fork_submit(st, m, src.data(), hist_len ? sel.data() : nullptr, hist_len ? nullptr : sel.data(),
+                                       hist_len ? nullptr : ord.data(), fh.data(), 0u, &O.id)))
+            return c.fail(rc);
+        O.sub = true;
+        // what a decode would have handed this round: the gathered change rows and the op map come
+        // back; the op rows through the map from the parent's own copy of its log where the docset
+        // keeps one (the per-op patch modes), and from the device otherwise.  Dep rows are not needed.
+        const bool host_ops = ds->patches && ds->op_diffs;
+        std::vector<hm_doc_row> gd;
+        std::vector<hm_change_row> gc;
+        std::vector<hm_op_row> go;
+        std::vector<uint32_t> gl;
+        if ((rc = hm_store_fork_rows(st, O.id, gd, gc, host_ops ? nullptr : &go, gl))) return c.fail(rc);
+        O.res.resize(m); O.clock.resize((size_t)m * S); O.back.resize((size_t)m * S); O.heads.resize((size_t)m * S);
+        if ((rc = hm_batch_wait(st, O.id, O.res.data(), O.clock.data(), O.back.data(), O.heads.data()))) return c.fail(rc);
+        O.sub = false;
+        O.done = true;
+        uint32_t r3[3] = {0, 0, 0};
+        if (hm_store_last_routing(st, r3) == HM_OK)
+            for (int q = 0; q < 3; q++) c.call_routing[q] += r3[q];
+        std::atomic<bool> outside{false};
+        try {
+        par_for(m, c.T, [&](uint32_t j_lo, uint32_t j_hi, uint32_t) {
+        for (uint32_t j = j_lo; j < j_hi; j++) {
+            const uint32_t i = rows[j];
+            Round &x = c.R[i];
+            DocSt &d = ds->doc(nd[i]);
+            const DocSt &p = ds->doc(parents[i]);
+            const hm_doc_row &r = gd[j];
+            if ((uint64_t)r.change_off + r.n_changes > gc.size() || (uint64_t)r.op_off + r.n_ops > gl.size()) { outside = true; continue; }
+            x.ch.assign(gc.begin() + r.change_off, gc.begin() + r.change_off + r.n_changes);
+            for (hm_change_row &cr : x.ch) { cr.dep_off -= r.dep_off; cr.op_first -= r.op_off; }
+            if (!host_ops) x.op.assign(go.begin() + r.op_off, go.begin() + r.op_off + r.n_ops);
+            else {
+                x.op.resize(r.n_ops);
+                for (uint32_t q = 0; q < r.n_ops; q++) {
+                    const uint32_t lo = gl[r.op_off + q];
+                    if (lo >= p.oplog.size()) { outside = true; break; }
+                    x.op[q] = p.oplog[lo];
+                }
+            }
+            // the per-op tables through the op map, the content table of the selected (actor, seq)
+            d.op_actor.reserve(r.n_ops); d.op_dt.reserve(r.n_ops);
+            for (uint32_t q = 0; q < r.n_ops; q++) {
+                const uint32_t lo = gl[r.op_off + q];
+                if (lo >= p.op_actor.size() || lo >= p.op_dt.size()) { outside = true; break; }
+                d.op_actor.push_back(p.op_actor[lo]);
+                d.op_dt.push_back(p.op_dt[lo]);
+            }
+            std::unordered_set<uint64_t> keys;
+            for (const hm_change_row &cr : x.ch)
+                if (cr.actor < p.by_rank.size()) keys.insert(((uint64_t)p.by_rank[cr.actor] << 32) | cr.seq);
+            for (const DocSt::CE &e : p.cents)
+                if (keys.count(e.key)) d.cents.push_back({e.key, e.h, e.cid, HM_NONE});
+            d.n_content = p.n_content;
+            size_t cap = 64;
+            while ((d.cents.size() + 1) * 2 > cap) cap *= 2;
+            d.crehash(cap);
+            x.res = O.res[j];
+            x.clock = O.clock.data() + (size_t)j * S; x.back = O.back.data() + (size_t)j * S; x.heads = O.heads.data() + (size_t)j * S;
+        }
+        });
+        } catch (...) {
+            return c.fail(hm_engine_fail(ds->e, HM_ERR_NOMEM, "out of memory in hm_docset_fork"));
+        }
+        if (outside) return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a fork's rows outside the gathered tables or its parent's log"));
+    }
+    c.mark("fork");
+    return finish(c, out);
 }
 
 // ---------------- what the host queries over many documents share ----------------
@@ -2460,6 +2631,32 @@ int hm_docset_materialize(hm_docset *ds, uint32_t n, const uint32_t *docs, const
         return HM_OK;
     } catch (...) {
         return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_materialize");
+    }
+}
+
+int hm_docset_fork(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, const uint32_t *entry_off,
+                   const char *actor_ids, const uint32_t *actor_off, const double *seqs, uint32_t *out_first, hm_text **out) {
+    if (!ds || !out || !out_first || (n && !docs)) return HM_ERR_INVALID;
+    *out = nullptr;
+    if ((hist_len != nullptr) == (entry_off != nullptr))
+        return hm_engine_fail(ds->e, HM_ERR_INVALID, "exactly one of hist_len and the clock entries");
+    Busy b(ds);
+    if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "hm_docset_fork: another call on this docset is running");
+    if (ds->broken)
+        return hm_engine_fail(ds->e, HM_ERR_DEVICE, "hm_docset_fork: an earlier failed call could not be undone on its store");
+    try {
+        int rc = check_request(ds, n, docs, entry_off);
+        if (rc) return rc;
+        if (entry_off && n && entry_off[n] - entry_off[0] && (!actor_ids || !actor_off || !seqs)) return HM_ERR_INVALID;
+        uint32_t first = 0;
+        if ((rc = hm_docset_open(ds, n, &first))) return rc;
+        std::unique_ptr<hm_text> t(new hm_text());
+        if ((rc = fork_docs(ds, n, docs, hist_len, entry_off, actor_ids, actor_off, seqs, first, t.get()))) return rc;
+        *out_first = first;
+        *out = t.release();
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_fork");
     }
 }
 

@@ -21,3 +21,11 @@ typedef const hm_past_out *(*hm_past_alloc)(void *ctx, const uint64_t *totals);
 struct hm_store;
 int hm_store_materialize_sized(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *hist_len,
                                const uint32_t *clock_rows, hm_past_alloc alloc, void *ctx, uint64_t *out_totals);
+
+// the tables a fork batch in flight (hm_store_fork_submit) gathered, read back for a host that
+// mirrors the forks' logs: request i's rows are docs[i]'s ranges, op_log[k] = the parent's log op
+// index of gathered op k; ops may be NULL (the caller holds the parents' op rows and takes the forks'
+// through op_log).  Only between the fork's submit and its wait.
+#include <vector>
+int hm_store_fork_rows(hm_store *s, uint64_t batch_id, std::vector<hm_doc_row> &docs, std::vector<hm_change_row> &changes,
+                       std::vector<hm_op_row> *ops, std::vector<uint32_t> &op_log);

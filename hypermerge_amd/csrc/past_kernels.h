@@ -33,14 +33,26 @@ inline uint32_t hm_past_scan_chunks(uint32_t n) { return (uint32_t)(((unsigned l
 // outside the source sets HM_PAST_BAD_HANDLE in sum->bad and gets empty ranges; a change row whose
 // dep / op range leaves its document's segment sets HM_PAST_BAD_ROWS and is gathered without those
 // rows.
+//
+// order (optional, with clock_rows only): request i's row order[i * S ..] lists actor ranks in
+// hand-over order, HM_NONE ends it.  The selection is then laid out actor after actor, each actor's
+// changes by ascending seq (loadDocument's / syncReadyActors' order) instead of history order: a
+// change's output position is base[actor] + seq - 1, base = the running sum over the row of
+// min(clock[actor], opSet.clock[actor]) (src.clock is read; an actor's applied changes are exactly
+// its seqs 1 .. opSet.clock[actor], so the positions are dense as history positions are).  The count
+// pass checks the row — ranks below n_actors, none twice, every rank with a selected change listed —
+// and sets HM_PAST_BAD_ORDER; the caller does not launch the fill then.  NULL: history order, the
+// kernels' output as without the table, byte for byte.
 #define HM_PAST_BAD_HANDLE 1u
 #define HM_PAST_BAD_ROWS 2u
+#define HM_PAST_BAD_ORDER 4u
 
 struct PastArgs {
     uint32_t n;
     DocSource src;
     const uint32_t *hist_len;                  // [n] or NULL
     const uint32_t *clock_rows;                // [n * S] or NULL
+    const uint32_t *order;                     // [n * S] or NULL: actor-major order (clock_rows only)
     uint32_t *cnt, *aux, *off;                 // [4n], [2n], [4n]
     unsigned long long *part;                  // [hm_past_scan_chunks(n) * HM_PAST_PART]
     hm_past_summary *sum;

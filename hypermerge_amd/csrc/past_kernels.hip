@@ -40,6 +40,7 @@ static_assert(sizeof(hm_op_row) == 32 && sizeof(hm_change_row) == 24 && sizeof(h
 struct Src : DocRef {
     uint32_t npre;                             // prefix selector (clock selector: unused)
     const uint32_t *clk;                       // clock selector's row, or NULL
+    const uint32_t *ord;                       // actor-major order row, or NULL (history order)
 };
 
 __device__ __forceinline__ Src source_of(const PastArgs &A, unsigned long long q) {
@@ -47,18 +48,54 @@ __device__ __forceinline__ Src source_of(const PastArgs &A, unsigned long long q
     static_cast<DocRef &>(s) = doc_of(A.src, q);
     s.npre = A.hist_len ? A.hist_len[q] : 0u;
     s.clk = A.clock_rows ? A.clock_rows + q * A.src.S : nullptr;
+    s.ord = A.order ? A.order + q * A.src.S : nullptr;
     return s;
 }
 
-// is log row i selected?  p = its history position
-__device__ __forceinline__ bool selected(const Src &s, const PastArgs &A, uint32_t i, uint32_t &p) {
+// is log row i selected?  p = its output position: its history position, or with ab (the request's
+// per-rank bases of the actor-major order, in LDS) ab[actor] + seq - 1
+__device__ __forceinline__ bool selected(const Src &s, const PastArgs &A, uint32_t i, uint32_t &p, const uint32_t *ab = nullptr) {
     const int32_t hp = A.src.hist[s.c_off + i];
     if (hp < 0 || (uint32_t)hp >= s.n_c) return false;
     p = (uint32_t)hp;
     if (!s.clk) return p < s.npre;
     const hm_change_row *c = A.src.changes + s.c_off + i;
-    const uint32_t a = c->actor;
-    return a < A.src.S && c->seq <= s.clk[a];
+    const uint32_t a = c->actor, q = c->seq;
+    if (a >= A.src.S || q > s.clk[a]) return false;
+    if (!ab) return true;
+    if (ab[a] == HM_NONE || !q) return false;                // (an unlisted rank: the count pass refused the row)
+    p = ab[a] + q - 1u;
+    return p < s.n_c;
+}
+
+// The request's actor-major order row, checked by the whole wave: HM_NONE ends it, every rank lies
+// below n_actors and appears once.  m[k] = the listed ranks 64 k .. 64 k + 63 as a bitmap.
+__device__ __forceinline__ bool order_row(const Src &s, const PastArgs &A, uint32_t lane, unsigned long long m[4]) {
+    const uint32_t S = A.src.S;
+    uint32_t len = S;
+    for (uint32_t j = lane; j < S; j += 64u)
+        if (s.ord[j] == HM_NONE) { len = j; break; }
+    for (uint32_t d = 32; d; d >>= 1) len = min(len, (uint32_t)__shfl_xor(len, d));
+    bool ok = s.clk != nullptr && A.src.clock != nullptr && !s.bad;
+    uint32_t mine = 0;
+    m[0] = m[1] = m[2] = m[3] = 0ull;
+    for (uint32_t j = lane; j < len; j += 64u) {
+        const uint32_t r = s.ord[j];
+        if (r >= s.n_actors || r >= S || r >= 256u) { ok = false; continue; }
+        const unsigned long long b = 1ull << (r & 63u);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++)
+            if (k == (r >> 6)) { ok &= !(m[k] & b); m[k] |= b; }
+        mine++;
+    }
+    mine = wave_sum(mine);
+    uint32_t listed = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        for (uint32_t d = 32; d; d >>= 1) m[k] |= (unsigned long long)__shfl_xor((long long)m[k], d);
+        listed += (uint32_t)__popcll(m[k]);
+    }
+    return __ballot(!ok) == 0ull && listed == mine;           // (a rank on two lanes: fewer bits than entries)
 }
 
 // the change's dep / op rows, none where the range leaves the document's segment
@@ -77,20 +114,29 @@ __global__ __launch_bounds__(PCWG) void past_count_kernel(PastArgs A) {
     for (unsigned long long q = (unsigned long long)blockIdx.x * (PCWG / 64) + wv; q < A.n; q += step) {
         const Src s = source_of(A, q);
         uint32_t nc = 0, nd = 0, no = 0;
-        bool ok = true;
+        bool ok = true, listed = true;
+        unsigned long long m[4] = {0ull, 0ull, 0ull, 0ull};
+        const bool row_ok = s.ord ? order_row(s, A, lane, m) : true;
         for (uint32_t i = lane; i < s.n_c; i += 64u) {
             uint32_t p;
             if (!selected(s, A, i, p)) continue;
+            if (s.ord) {                                       // every rank with a selected change is listed
+                const uint32_t a = A.src.changes[s.c_off + i].actor, k = a >> 6;
+                const unsigned long long w = k == 0 ? m[0] : (k == 1 ? m[1] : (k == 2 ? m[2] : m[3]));
+                listed &= ((w >> (a & 63u)) & 1ull) != 0ull;
+            }
             uint32_t d, o;
             ok &= rows_of(s, A.src.changes[s.c_off + i], d, o);
             nc++; nd += d; no += o;
         }
         nc = wave_sum(nc); nd = wave_sum(nd); no = wave_sum(no);
         const bool any_bad = __ballot(!ok) != 0ull;
+        const bool bad_order = !row_ok || __ballot(!listed) != 0ull;
         if (lane == 0) {
             *(uint4 *)(A.cnt + 4 * q) = make_uint4(nc, nd, no, s.n_r);
             *(uint2 *)(A.aux + 2 * q) = make_uint2(s.n_objs, s.flags);
-            const uint32_t b = (s.bad ? HM_PAST_BAD_HANDLE : 0u) | (any_bad ? HM_PAST_BAD_ROWS : 0u);
+            const uint32_t b = (s.bad ? HM_PAST_BAD_HANDLE : 0u) | (any_bad ? HM_PAST_BAD_ROWS : 0u) |
+                               (bad_order ? HM_PAST_BAD_ORDER : 0u);
             if (b) atomicOr(&A.sum->bad, b);
         }
     }
@@ -185,6 +231,7 @@ struct Lds {
     uint32_t src[PTILE];                      // per slot: the change's log row (document-local)
     uint32_t dp[PTILE], op[PTILE];             // per slot: dep / op rows, then their offsets within the tile
     uint32_t of[PTILE];                        // per slot: the change's first source op row
+    uint32_t ab[HM_MAX_STRIDE];                // actor-major order: per rank the position of its seq 1 (HM_NONE: unlisted)
 };
 
 __global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
@@ -207,6 +254,30 @@ __global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
             A.out_docs[q] = r;
         }
         if (!cn.x) continue;
+        const uint32_t *ab = nullptr;
+        if (s.ord) {
+            // the ranks' bases: the running sum, over the order row, of min(clock row, opSet.clock) —
+            // an actor's applied changes are exactly its seqs 1 .. opSet.clock[actor]
+            __syncthreads();                                   // (the previous request's reads of L.ab)
+            for (uint32_t a = lane; a < HM_MAX_STRIDE; a += 64u) L.ab[a] = HM_NONE;
+            __syncthreads();
+            const uint32_t *have = D.clock + (unsigned long long)s.index * D.S;
+            uint32_t run = 0;
+            bool open = true;                                  // (HM_NONE not met yet)
+            for (uint32_t j0 = 0; j0 < D.S && open; j0 += 64u) {
+                const uint32_t j = j0 + lane;
+                const uint32_t r = j < D.S ? s.ord[j] : HM_NONE;
+                const unsigned long long ends = __ballot(r == HM_NONE || r >= D.S);
+                const bool live = ends == 0ull || lane < (uint32_t)__ffsll((long long)ends) - 1u;
+                const uint32_t k = live ? min(s.clk[r], have[r]) : 0u;
+                const uint32_t incl = wave_incl_scan(k, lane);
+                if (live) L.ab[r] = run + incl - k;
+                run += __shfl(incl, 63);
+                open = ends == 0ull;
+            }
+            __syncthreads();
+            ab = L.ab;
+        }
         const uint32_t n_tiles = (s.n_c + PTILE - 1u) / PTILE;
         uint32_t base = 0, dbase = 0, obase = 0;               // changes / deps / ops gathered by the earlier tiles
         for (uint32_t t = 0; t < n_tiles && base < cn.x; t++) {
@@ -214,17 +285,22 @@ __global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
             __syncthreads();
             for (uint32_t i = lane; i < s.n_c; i += 64u) {     // mark
                 uint32_t p;
-                if (selected(s, A, i, p) && p / PTILE == t) L.tile.mark(p);
+                if (selected(s, A, i, p, ab) && p / PTILE == t) L.tile.mark(p);
             }
             __syncthreads();
             const uint32_t tile_n = L.tile.rank(lane);         // rank
             __syncthreads();
             if (!tile_n) continue;
             for (uint32_t i = lane; i < s.n_c; i += 64u) {     // scatter
-                const int32_t hp = D.hist[s.c_off + i];
-                if (hp < 0 || (uint32_t)hp >= s.n_c || (uint32_t)hp / PTILE != t) continue;
-                uint32_t k;
-                if (!L.tile.slot((uint32_t)hp, k)) continue;
+                uint32_t p, k;
+                if (ab) {                                      // (another rank's unselected change may name a marked position)
+                    if (!selected(s, A, i, p, ab)) continue;
+                } else {
+                    const int32_t hp = D.hist[s.c_off + i];
+                    if (hp < 0 || (uint32_t)hp >= s.n_c) continue;
+                    p = (uint32_t)hp;
+                }
+                if (p / PTILE != t || !L.tile.slot(p, k)) continue;
                 const hm_change_row c = D.changes[s.c_off + i];
                 uint32_t nd, no;
                 rows_of(s, c, nd, no);

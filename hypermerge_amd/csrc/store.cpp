@@ -101,6 +101,10 @@ struct hm_store {
     // staging (device)
     DBuf<uint8_t> stage;
     DBuf<uint8_t> past;                           // hm_store_materialize: the gathered batch and its merge
+    // the fork batch in flight: its gathered tables in `past` (hm_store_fork_rows reads them until the wait)
+    uint64_t fork_id = 0;
+    uint32_t fork_n = 0;
+    size_t fork_rows[3] = {0, 0, 0}, fork_off[6] = {0, 0, 0, 0, 0, 0};
     // in-flight batch
     std::atomic<bool> pending{false};             // a submitted batch not yet waited for (other threads may read it)
     uint64_t next_id = 1, pending_id = 0;
@@ -1248,31 +1252,48 @@ static_assert(sizeof(PlanStats) >= sizeof(hm_past_summary), "the summary is read
 
 // The count pass of n staged requests: handles and the selector go to the stage buffer, the counts,
 // offsets and summary stay there (P.cnt / P.off / P.sum); *sum = the summary, read back.
+// order: the actor-major order rows (staged too); dst: a fork's destination handles, staged
+// (*dst_dev) and checked on the device before the one read-back.
 static int past_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *hist_len,
-                      const uint32_t *clock_rows, PastArgs &P, hm_past_summary *sum) {
+                      const uint32_t *clock_rows, PastArgs &P, hm_past_summary *sum, const uint32_t *order = nullptr,
+                      const uint32_t *dst = nullptr, const uint32_t **dst_dev = nullptr) {
     const uint32_t S = s->S;
     hipStream_t st = hm_engine_stream(s->e);
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t sel_b = hist_len ? 4 * (size_t)n : 4 * (size_t)n * S;
     const size_t o_sum = 0, o_h = 256, o_sel = o_h + al(4 * (size_t)n), o_cnt = o_sel + al(sel_b), o_off = o_cnt + al(16 * (size_t)n),
                  o_aux = o_off + al(16 * (size_t)n), o_part = o_aux + al(8 * (size_t)n),
-                 total = o_part + al((size_t)hm_past_scan_chunks(n) * HM_PAST_PART * 8);
+                 o_ord = o_part + al((size_t)hm_past_scan_chunks(n) * HM_PAST_PART * 8),
+                 o_dst = o_ord + (order ? al(4 * (size_t)n * S) : 0), total = o_dst + (dst ? al(4 * (size_t)n) : 0);
     int rc = ensure_stage(s, total);
     if (rc) return rc;
     uint8_t *sp = s->stage.p;
     SCHK(s, hipMemcpyAsync(sp + o_h, doc_handles, 4 * (size_t)n, hipMemcpyHostToDevice, st));
     SCHK(s, hipMemcpyAsync(sp + o_sel, hist_len ? hist_len : clock_rows, sel_b, hipMemcpyHostToDevice, st));
+    if (order) SCHK(s, hipMemcpyAsync(sp + o_ord, order, 4 * (size_t)n * S, hipMemcpyHostToDevice, st));
+    if (dst) SCHK(s, hipMemcpyAsync(sp + o_dst, dst, 4 * (size_t)n, hipMemcpyHostToDevice, st));
     P = PastArgs{};
     P.n = n; P.src = store_source(s); P.src.handles = (const uint32_t *)(sp + o_h);
     if (hist_len) P.hist_len = (const uint32_t *)(sp + o_sel); else P.clock_rows = (const uint32_t *)(sp + o_sel);
+    if (order) P.order = (const uint32_t *)(sp + o_ord);
     P.cnt = (uint32_t *)(sp + o_cnt); P.off = (uint32_t *)(sp + o_off); P.aux = (uint32_t *)(sp + o_aux);
     P.part = (unsigned long long *)(sp + o_part);
     P.sum = (hm_past_summary *)(sp + o_sum);
     SCHK(s, hm_launch_past_count(P, st));
+    if (dst) {
+        const uint32_t stamp_src = ++s->stamp ? s->stamp : ++s->stamp, stamp_dst = ++s->stamp ? s->stamp : ++s->stamp;
+        SCHK(s, hm_launch_fork_check(P.src.handles, (const uint32_t *)(sp + o_dst), n, s->n_handles, s->dm, s->seen, stamp_src,
+                                     stamp_dst, &P.sum->bad, st));
+        *dst_dev = (const uint32_t *)(sp + o_dst);
+    }
     SCHK(s, hipMemcpyAsync(s->h_st, P.sum, sizeof(hm_past_summary), hipMemcpyDeviceToHost, st));
     SCHK(s, hipStreamSynchronize(st));
     memcpy(sum, s->h_st, sizeof *sum);
     if (sum->bad & HM_PAST_BAD_HANDLE) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad handle");
+    if (sum->bad & HM_FORK_BAD_DST)
+        return hm_engine_fail(s->e, HM_ERR_INVALID, "a fork's destination is outside the store, repeated, a source or not empty");
+    if (sum->bad & HM_PAST_BAD_ORDER)
+        return hm_engine_fail(s->e, HM_ERR_INVALID, "actor order row: a rank outside the document, repeated, or an actor of the clock not listed");
     if (sum->bad) return hm_engine_fail(s->e, HM_ERR_INVALID, "a change row outside its document's segments");
     return HM_OK;
 }
@@ -1308,7 +1329,95 @@ int hm_store_materialize(hm_store *s, uint32_t n, const uint32_t *doc_handles, c
                                       [](void *ctx, const uint64_t *) { return (const hm_past_out *)ctx; }, (void *)out, out_totals);
 }
 
+// Fork: count, scan and fill into the store's own buffer, then the device-table submit of those
+// tables to the destinations.  The gathered rows (and the staged destination handles, copied behind
+// them) stay untouched until the wait: every call that would reuse the buffer is refused while the
+// batch is in flight.
+int hm_store_fork_submit(hm_store *s, uint32_t n, const uint32_t *src_handles, const uint32_t *hist_len,
+                         const uint32_t *clock_rows, const uint32_t *actor_order, const uint32_t *dst_handles, uint32_t flags,
+                         uint64_t *out_batch_id) {
+    if (!s || !n || !src_handles || !dst_handles) return HM_ERR_INVALID;
+    if ((hist_len != nullptr) == (clock_rows != nullptr))
+        return hm_engine_fail(s->e, HM_ERR_INVALID, "exactly one of hist_len and clock_rows");
+    if (actor_order && !clock_rows) return hm_engine_fail(s->e, HM_ERR_INVALID, "an actor order goes with a clock, not a history length");
+    if (flags & ~HM_FORK_MIN_CLOCK) return hm_engine_fail(s->e, HM_ERR_INVALID, "unknown fork flags");
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "a batch is already in flight (call hm_batch_wait)");
+    try {
+        const uint32_t S = s->S;
+        SCHK(s, hipSetDevice(hm_engine_device(s->e)));
+        hipStream_t st = hm_engine_stream(s->e);
+        PastArgs P;
+        hm_past_summary sum;
+        const uint32_t *dst_staged = nullptr;
+        int rc = past_count(s, n, src_handles, hist_len, clock_rows, P, &sum, actor_order, dst_handles, &dst_staged);
+        if (rc) return rc;
+        const uint64_t tc = sum.totals[0], td = sum.totals[1], to = sum.totals[2], tr = sum.totals[3];
+        if (std::max(std::max(tc, td), std::max(to, tr)) > 0xFFFFFFFFull)
+            return hm_engine_fail(s->e, HM_ERR_NOMEM, "a call's rows stay below 2^32");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        // [docs][changes][deps][ops][change_log][op_log][destination handles]
+        const size_t sz[7] = {n * sizeof(hm_doc_row), tc * sizeof(hm_change_row), td * sizeof(hm_dep_row), to * sizeof(hm_op_row),
+                              tc * 4, to * 4, (size_t)n * 4};
+        size_t o[7], total = 0;
+        for (int i = 0; i < 7; i++) { o[i] = total; total += al(sz[i] + 1); }
+        if ((rc = ensure_buf(s, s->past, total))) return rc;
+        uint8_t *bp = s->past.p;
+        P.cap[0] = (uint32_t)tc; P.cap[1] = (uint32_t)td; P.cap[2] = (uint32_t)to; P.cap[3] = (uint32_t)tr;
+        P.out_docs = (hm_doc_row *)(bp + o[0]); P.out_changes = (hm_change_row *)(bp + o[1]); P.out_deps = (hm_dep_row *)(bp + o[2]);
+        P.out_ops = (hm_op_row *)(bp + o[3]); P.out_change_log = (uint32_t *)(bp + o[4]); P.out_op_log = (uint32_t *)(bp + o[5]);
+        // (the fill, the copy and the min-clock kernel below still read the stage buffer — handles, counts,
+        // offsets, order rows — when the submit stages its own rows there: they are enqueued first on the
+        // same stream, and a stage buffer that has to grow is freed only after ensure_buf has synchronised
+        // that stream)
+        SCHK(s, hm_launch_past_fill(P, st));
+        uint32_t *dst_dev = (uint32_t *)(bp + o[6]);
+        SCHK(s, hipMemcpyAsync(dst_dev, dst_staged, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        // (the destinations passed the check: empty documents, whose minimumClock row no result shows)
+        SCHK(s, hm_launch_fork_min_clock(P.src.handles, dst_dev, n, S, s->dm, s->min_clock, flags & HM_FORK_MIN_CLOCK ? 1u : 0u, st));
+        hm_batch b = {};
+        b.a_stride = S; b.n_docs = n;
+        b.n_changes = (uint32_t)tc; b.n_deps = (uint32_t)td; b.n_ops = (uint32_t)to; b.n_regs = (uint32_t)tr;
+        b.docs = P.out_docs; b.changes = P.out_changes; b.deps = P.out_deps; b.ops = P.out_ops;
+        uint64_t id = 0;
+        if ((rc = hm_batch_submit_device(s, &b, dst_dev, nullptr, &id))) return rc;
+        s->fork_id = id; s->fork_n = n;
+        s->fork_rows[0] = (size_t)tc; s->fork_rows[1] = (size_t)td; s->fork_rows[2] = (size_t)to;
+        for (int i = 0; i < 6; i++) s->fork_off[i] = o[i];
+        if (out_batch_id) *out_batch_id = id;
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_fork_submit");
+    }
+}
+
 }  // extern "C"
+
+// (engine_internal.h) the tables a fork batch in flight gathered, for a host that mirrors the forks'
+// logs (the docset): request i's rows are out_docs[i]'s ranges, op_log[k] = the parent's log op index
+// of gathered op k.  ops may be NULL (a host that holds the parents' op rows takes them through
+// op_log).  Only between the fork's submit and its wait.
+int hm_store_fork_rows(hm_store *s, uint64_t batch_id, std::vector<hm_doc_row> &docs, std::vector<hm_change_row> &changes,
+                       std::vector<hm_op_row> *ops, std::vector<uint32_t> &op_log) {
+    if (!s) return HM_ERR_INVALID;
+    if (!s->pending || !batch_id || batch_id != s->pending_id || batch_id != s->fork_id)
+        return hm_engine_fail(s->e, HM_ERR_INVALID, "hm_store_fork_rows: not the fork batch in flight");
+    try {
+        hipStream_t st = hm_engine_stream(s->e);
+        docs.resize(s->fork_n); changes.resize(s->fork_rows[0]); op_log.resize(s->fork_rows[2]);
+        if (ops) ops->resize(s->fork_rows[2]);
+        const uint8_t *bp = s->past.p;
+        void *dst[4] = {docs.data(), changes.data(), ops ? ops->data() : nullptr, op_log.data()};
+        const size_t sz[4] = {docs.size() * sizeof(hm_doc_row), changes.size() * sizeof(hm_change_row),
+                              ops ? ops->size() * sizeof(hm_op_row) : 0, op_log.size() * 4};
+        const size_t at[4] = {s->fork_off[0], s->fork_off[1], s->fork_off[3], s->fork_off[5]};
+        for (int i = 0; i < 4; i++)
+            if (sz[i]) SCHK(s, hipMemcpyAsync(dst[i], bp + at[i], sz[i], hipMemcpyDeviceToHost, st));
+        SCHK(s, hipStreamSynchronize(st));
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_fork_rows");
+    }
+}
 
 // (engine_internal.h) the outputs are asked for once the count pass has sized them: one count pass
 // for a caller that allocates by the totals

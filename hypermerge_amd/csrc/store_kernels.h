@@ -218,6 +218,14 @@ hipError_t hm_launch_init_docs(DevDoc *dm, uint32_t h0, uint32_t n, hipStream_t 
 hipError_t hm_launch_reset_docs(const uint32_t *handles, uint32_t n, DevDoc *dm, hm_doc_result *res, IncState *ist,
                                 uint32_t *clock, uint32_t *back, uint32_t *heads, uint32_t *minc, uint32_t *stored,
                                 uint32_t S, uint32_t *n_valid, hipStream_t s);
+// hm_store_fork_submit: the destinations checked against the store and the sources (*bad |=
+// HM_FORK_BAD_DST; `bad` is the past kernels' summary word, whose low bits are HM_PAST_BAD_*), two
+// stamps of the submit's `seen` table; then the forks' minimumClock rows
+#define HM_FORK_BAD_DST 8u
+hipError_t hm_launch_fork_check(const uint32_t *src, const uint32_t *dst, uint32_t n, uint32_t n_handles, const DevDoc *dm,
+                                uint32_t *seen, uint32_t stamp_src, uint32_t stamp_dst, uint32_t *bad, hipStream_t s);
+hipError_t hm_launch_fork_min_clock(const uint32_t *src, const uint32_t *dst, uint32_t n, uint32_t S, DevDoc *dm,
+                                    uint32_t *minc, uint32_t on, hipStream_t s);
 // chosen registers of resident documents by (handle, register): validated on the device
 hipError_t hm_launch_read_hist(uint32_t n, const uint32_t *handles, const uint32_t *from, const uint32_t *to,
                                const uint32_t *out_off, const DevDoc *dm, uint32_t n_handles, const int32_t *hist,

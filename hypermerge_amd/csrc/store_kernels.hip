@@ -664,6 +664,44 @@ __global__ void reset_docs_kernel(const uint32_t *handles, uint32_t n, DevDoc *d
     }
 }
 
+// hm_store_fork_submit's destination check, two launches over the n requests.  mark: seen[source] =
+// stamp_src.  check: destination i lies inside the store, is named once (seen exchanged for
+// stamp_dst), is no source, holds no change, and its totals (an emptied document keeps them) lie
+// within its parent's, so the submit's plan cannot refuse it.  Nothing is read through a handle
+// outside the store.
+__global__ void fork_mark_kernel(const uint32_t *src, uint32_t n, uint32_t n_handles, uint32_t *seen, uint32_t stamp_src) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && src[i] < n_handles) seen[src[i]] = stamp_src;
+}
+__global__ void fork_check_kernel(const uint32_t *src, const uint32_t *dst, uint32_t n, uint32_t n_handles, const DevDoc *dm,
+                                  uint32_t *seen, uint32_t stamp_src, uint32_t stamp_dst, uint32_t *bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t h = dst[i], p = src[i];
+    bool ok = h < n_handles;
+    if (ok) {
+        const uint32_t was = atomicExch(&seen[h], stamp_dst);
+        const DevDoc m = dm[h];
+        ok = was != stamp_dst && was != stamp_src && m.n_c == 0u;
+        if (ok && p < n_handles) {
+            const DevDoc pm = dm[p];
+            ok = m.n_actors <= pm.n_actors && m.n_r <= pm.n_r && m.n_objs <= pm.n_objs;
+        }
+    }
+    if (!ok) atomicOr(bad, HM_FORK_BAD_DST);
+}
+
+// the forks' minimumClock rows: the parent's row and its HM_DDOC_MINC bit (on), or none
+__global__ void fork_min_clock_kernel(const uint32_t *src, const uint32_t *dst, uint32_t n, uint32_t S, DevDoc *dm,
+                                      uint32_t *minc, uint32_t on) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t h = dst[i], p = src[i];
+    const bool has = on && (dm[p].pad[0] & HM_DDOC_MINC);
+    for (uint32_t a = 0; a < S; a++) minc[(size_t)h * S + a] = has ? minc[(size_t)p * S + a] : 0u;
+    if (has) dm[h].pad[0] |= HM_DDOC_MINC; else dm[h].pad[0] &= ~HM_DDOC_MINC;
+}
+
 __global__ void read_regs_h_kernel(uint32_t n, const uint32_t *handles, const uint32_t *regs, const DevDoc *dm,
                                    uint32_t n_handles, const hm_reg_result *rr, const hm_surv_result *surv,
                                    hm_reg_result *out_regs, hm_surv_result *out_surv, uint32_t cap, uint32_t *counter,
@@ -742,6 +780,22 @@ hipError_t hm_launch_reset_docs(const uint32_t *handles, uint32_t n, DevDoc *dm,
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(hms::reset_docs_kernel, dim3((n + 255) / 256), dim3(256), 0, s, handles, n, dm, res, ist, clock, back,
                        heads, minc, stored, S, n_valid);
+    return hipGetLastError();
+}
+hipError_t hm_launch_fork_check(const uint32_t *src, const uint32_t *dst, uint32_t n, uint32_t n_handles, const DevDoc *dm,
+                                uint32_t *seen, uint32_t stamp_src, uint32_t stamp_dst, uint32_t *bad, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(hms::fork_mark_kernel, dim3((n + 255) / 256), dim3(256), 0, s, src, n, n_handles, seen, stamp_src);
+    hipError_t r = hipGetLastError();
+    if (r != hipSuccess) return r;
+    hipLaunchKernelGGL(hms::fork_check_kernel, dim3((n + 255) / 256), dim3(256), 0, s, src, dst, n, n_handles, dm, seen,
+                       stamp_src, stamp_dst, bad);
+    return hipGetLastError();
+}
+hipError_t hm_launch_fork_min_clock(const uint32_t *src, const uint32_t *dst, uint32_t n, uint32_t S, DevDoc *dm,
+                                    uint32_t *minc, uint32_t on, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(hms::fork_min_clock_kernel, dim3((n + 255) / 256), dim3(256), 0, s, src, dst, n, S, dm, minc, on);
     return hipGetLastError();
 }
 hipError_t hm_launch_read_regs_h(uint32_t n, const uint32_t *handles, const uint32_t *regs, const DevDoc *dm,

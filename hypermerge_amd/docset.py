@@ -285,6 +285,40 @@ class DocSet:
         s, _ = _text(self._L, t)
         return json.loads(s)
 
+    def _fork(self, docs, clocks, history):
+        ids = np.ascontiguousarray(docs, np.uint32)
+        if (history is None) == (clocks is None):
+            raise ValueError("fork takes exactly one of history and clocks")
+        hl = eoff = data = aoff = sq = None
+        if history is not None:
+            hl = np.ascontiguousarray(np.minimum(np.asarray(history, np.int64), 0xFFFFFFFF), np.uint32)
+            assert len(hl) == len(ids)
+        else:
+            eoff, data, aoff, sq = self._clock_entries(len(ids), clocks)
+        p = lambda a: None if a is None else a.ctypes.data
+        first, t = ctypes.c_uint32(), ctypes.c_void_p()
+        self.engine._check(self._L.hm_docset_fork(self._h, len(ids), ids.ctypes.data if len(ids) else None, p(hl), p(eoff),
+                                                  p(data), p(aoff), p(sq), ctypes.byref(first), ctypes.byref(t)), "hm_docset_fork")
+        return list(range(first.value, first.value + len(ids))), t
+
+    def fork(self, docs: Sequence[int], clocks: Optional[Sequence[Dict[str, float]]] = None,
+             history: Optional[Sequence[int]] = None) -> Tuple[List[int], np.ndarray, Dict[str, Any]]:
+        """Repo.fork / Repo.merge into a fresh document, many per call (hm_docset_fork): new documents
+        that are docs[i] (may repeat) at the clock clocks[i] ({actorId: seq}: the changes are handed
+        over actor after actor in the clock's key order, an id the parent never saw is dropped) or at
+        history length history[i] (in the parent's history order).  Returns (the new documents' ids,
+        and what `apply` returns for a first round handing them those changes: the result rows and
+        {"p", "b", "c"})."""
+        new, t = self._fork(docs, clocks, history)
+        s, res = _text(self._L, t)
+        return new, res, json.loads(s)
+
+    def fork_raw(self, docs, clocks=None, history=None) -> Tuple[List[int], np.ndarray, bytes]:
+        """`fork` with the call's text as it came (the HMP1 words of a binary docset)."""
+        new, t = self._fork(docs, clocks, history)
+        s, res = _text(self._L, t, raw=True)
+        return new, res, s
+
     def handles(self, a_stride: int) -> Dict[str, int]:
         """hm_docset_handles: handles opened in the a_stride store and released ones awaiting reuse."""
         o, f = ctypes.c_uint32(), ctypes.c_uint32()

@@ -462,14 +462,16 @@ class KeyTable {
 }
 
 class GpuBackendState {
-  constructor(engine, docId) {
+  // at: {shard, id} of a document the docset has opened itself (a fork lives in its parent's docset,
+  // whatever shard its own docId hashes to)
+  constructor(engine, docId, at) {
     this.engine = engine
     this.docId = docId
-    this.shard = docId === undefined ? 0 : engine.shardOf(docId)
+    this.shard = at ? at.shard : docId === undefined ? 0 : engine.shardOf(docId)
     this.ds = engine.docsets[this.shard]
-    this.id = addon.docsetOpen(this.ds, 1)
+    this.id = at ? at.id : addon.docsetOpen(this.ds, 1)
     engine.states[this.shard].set(this.id, this)    // (docset id -> state: GpuEngine.blocked names documents)
-    if (docId !== undefined) engine.byDocId[this.shard].set(docId, this)   // (docId -> state: GpuEngine.materialize by id)
+    if (docId !== undefined) engine.byDocId[engine.shardOf(docId)].set(docId, this)   // (docId -> state: GpuEngine.materialize by id)
     this.log = []
     this.histLen = 0
     this.nQueued = 0
@@ -655,6 +657,87 @@ class GpuEngine {
         const ids = Uint32Array.from(byClock.map((i) => states[i].id))
         const got = JSON.parse(addon.docsetMaterializePatchAt(ds, ids, ...clockEntries(byClock.map((i) => reqs[i].clock)), lists ? 1 : 0))
         byClock.forEach((i, j) => { out[i] = { history: got[j].history, queued: got[j].queued, patch: got[j].patch } })
+      }
+    })
+    return out
+  }
+
+  // Repo.fork / Repo.merge into a fresh document, many at once: reqs[i] = {from: state | docId, clock:
+  // {actorId: seq} | history: n, id: the new document's docId} -> per request {state, patch, history,
+  // roundClock, changes}: a new resident document holding the parent's changes at that clock, handed
+  // over actor after actor in the clock's key order (what syncReadyActors hands a new document; an id
+  // the parent never saw is dropped), or its history prefix in history order.  The rows are selected
+  // and copied on the device (hm_docset_fork); patch is the one a fresh document's first applyChanges
+  // of those changes returns.  Reflects the rounds already applied: in 'async' mode the call waits
+  // for idle() and returns a Promise.
+  fork(reqs) {
+    if (this.mode === 'async') return this.idle().then(() => this.forkNow(reqs))
+    return this.forkNow(reqs)
+  }
+
+  // the changes a fork is handed, as the entries of its parent's log, in hand-over order
+  handedOver(parent, req) {
+    if (req.clock === undefined || req.clock === null) {
+      const n = Math.min(Math.max(Math.floor(Number(req.history) || 0), 0), 0xffffffff)
+      const b = addon.docsetHistoryPrefix(parent.ds, parent.id, n)
+      const idx = new Uint32Array(b.buffer, b.byteOffset, b.length / 4)
+      return Array.from(idx, (i) => parent.log[i])
+    }
+    // actor -> seq -> the first copy's log index, kept on the parent and extended by the entries
+    // that arrived since the last fork of it (a document's log only grows)
+    if (!parent.firstCopy) { parent.firstCopy = new Map(); parent.firstCopyLen = 0 }
+    const at = parent.firstCopy
+    for (let i = parent.firstCopyLen; i < parent.log.length; i++) {
+      const c = parent.change(i)
+      let m = at.get(c.actor)
+      if (!m) { m = new Map(); at.set(c.actor, m) }
+      if (!m.has(c.seq)) m.set(c.seq, i)
+    }
+    parent.firstCopyLen = parent.log.length
+    const clock = plainClock(req.clock), out = [], seen = new Set()
+    for (const a of Object.keys(clock)) {
+      if (seen.has(a)) continue
+      seen.add(a)
+      const top = Math.min(Math.floor(Number(clock[a]) || 0), parent.clock[a] || 0)
+      for (let q = 1; q <= top; q++) out.push(parent.log[at.get(a).get(q)])
+    }
+    return out
+  }
+
+  forkNow(reqs) {
+    if (this.flushing) throw new Error('GpuEngine.fork while a round is in flight')
+    const parents = reqs.map((r) => (r.from instanceof GpuBackendState ? r.from : this.stateOf(r.from)))
+    const out = new Array(reqs.length)
+    this.docsets.forEach((ds, k) => {
+      const mine = []
+      parents.forEach((p, i) => { if (p.shard === k) mine.push(i) })
+      const byClock = mine.filter((i) => !(reqs[i].clock === undefined || reqs[i].clock === null))
+      const byHist = mine.filter((i) => reqs[i].clock === undefined || reqs[i].clock === null)
+      for (const sel of [byHist, byClock]) {
+        if (!sel.length) continue
+        const ids = Uint32Array.from(sel.map((i) => parents[i].id))
+        const handed = sel.map((i) => this.handedOver(parents[i], reqs[i]))
+        const r = sel === byHist
+          ? addon.docsetFork(ds, ids, Uint32Array.from(sel.map((i) => Math.min(Math.max(Math.floor(Number(reqs[i].history) || 0), 0), 0xffffffff))),
+            null, null, null, null)
+          : addon.docsetFork(ds, ids, null, ...clockEntries(sel.map((i) => reqs[i].clock)))
+        this.submits++
+        const res = new Uint32Array(r.results.buffer, r.results.byteOffset, r.results.length / 4)
+        const j = decodeRound(r.data, sel.length)
+        const states = sel.map((i, x) => {
+          const status = res[RESULT_U32 * x] | 0
+          if (status !== 0) throw this.errorFor(parents[i], handed[x], status, res[RESULT_U32 * x + 1], res[RESULT_U32 * x + 2])
+          const st = new GpuBackendState(this, reqs[i].id, { shard: k, id: r.first + x })
+          st.log = handed[x]
+          st.histLen = res[RESULT_U32 * x + 3]
+          st.nQueued = res[RESULT_U32 * x + 4]
+          j.advance(x, st)
+          return st
+        })
+        sel.forEach((i, x) => {
+          const m = j.message(x, states[x])
+          out[i] = { state: states[x], patch: m.patch, history: states[x].histLen, roundClock: m.c, changes: handed[x].length }
+        })
       }
     })
     return out
@@ -1249,6 +1332,59 @@ class DocBackend {
           actorId: this.actorId, patch, history: this.back.histLen })
       } })
     } })
+  }
+
+  // init(changes, actorId) with the changes Repo.merge hands a new document for `clock` out of
+  // parentBackend's document (src/RepoBackend.ts:213-217): each actor's changes 1 .. clock[actor] in the
+  // clock's key order.  Message for message what init does with those changes — the same ReadyMsg,
+  // minimumClockSatisfied = changes.length > 0, the same clock — but the rows are copied on the
+  // device (GpuEngine.fork) instead of being decoded and uploaded again.
+  initFrom(parentBackend, clock, actorId) {
+    const run = () => {
+      const f = this.engine.forkNow([{ from: parentBackend.back, clock, id: this.id }])[0]
+      const state = f.state
+      this.actorId = this.actorId || actorId
+      this.back = state
+      this.updateClock(f.roundClock)
+      this.minimumClockSatisfied = f.changes > 0
+      const patch = f.patch
+      this.ready.subscribe((g) => g())
+      this.subscribeToLocalChanges()
+      this.subscribeToRemoteChanges()
+      // ReadyMsg after the buffered remote changes drained above (per-document FIFO)
+      this.engine.enqueue(state, { entries: null, done: () => {
+        this.notify({ type: 'ReadyMsg', id: this.id, minimumClockSatisfied: this.minimumClockSatisfied,
+          actorId: this.actorId, patch, history: this.back.histLen })
+      } })
+    }
+    this.afterIdle(run)
+  }
+
+  // Repo.merge(this, parent) into a document that is still empty (Repo.fork = create() + merge(fork,
+  // parent), src/RepoFrontend.ts:95-99): the RemotePatchMsg that applyRemoteChanges of the handed-over
+  // changes would give, with the rows copied on the device (GpuEngine.fork).  The document's state
+  // object is replaced by the fork's.  Throws when the document already holds changes: merging into
+  // those needs the two documents' ids remapped, which the engine does not do.
+  mergeFrom(parentBackend, clock) {
+    this.afterIdle(() => {
+      if (!this.back || this.back.log.length) throw new Error('DocBackend.mergeFrom: the document already holds changes')
+      const f = this.engine.forkNow([{ from: parentBackend.back, clock, id: this.id }])[0]
+      this.engine.states[this.back.shard].delete(this.back.id)    // (the empty document it replaces)
+      this.back = f.state
+      this.updateClock(f.roundClock)
+      this.notify({ type: 'RemotePatchMsg', id: this.id, minimumClockSatisfied: this.minimumClockSatisfied,
+        patch: f.patch, history: this.back.histLen })
+    })
+  }
+
+  // run now, or in 'async' mode once the engine is idle; what run throws there goes to the engine's
+  // onError, or is thrown from a fresh turn of the event loop (not swallowed by the promise)
+  afterIdle(run) {
+    if (this.engine.mode !== 'async') return run()
+    this.engine.idle().then(run).catch((e) => {
+      if (this.engine.onError) this.engine.onError(e)
+      else setImmediate(() => { throw e })
+    })
   }
 
   subscribeToRemoteChanges() {

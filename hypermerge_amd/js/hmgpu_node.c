@@ -1078,6 +1078,43 @@ static napi_value DocsetMaterialize(napi_env env, napi_callback_info info) {
     return js;
 }
 
+/* docsetFork(docset, parents Uint32Array, histLen Uint32Array | null, entryOff Uint32Array [n + 1] | null,
+ * actorIds Buffer, actorOff Uint32Array [entries + 1], seqs Float64Array) -> {first, results, data}: n new
+ * documents first .. first + n - 1, request i the parent parents[i] at a history length (in its history
+ * order) or at a clock given as docsetMaterialize takes one (handed over actor after actor in entry
+ * order); results / data are what docsetApply returns for a first round handing them those changes
+ * (hm_docset_fork; refused while a call on the docset is in flight) */
+static napi_value DocsetFork(napi_env env, napi_callback_info info) {
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return NULL;
+    Docset *d = get_docset(env, argv[0]);
+    if (!d) return NULL;
+    void *p[6]; size_t len[6];
+    for (int i = 0; i < 6; i++)
+        if (!get_bytes(env, argv[1 + i], &p[i], &len[i])) return NULL;
+    const uint32_t n = (uint32_t)(len[0] / 4);
+    const uint32_t *hl = (const uint32_t *)p[1], *eoff = (const uint32_t *)p[2], *aoff = (const uint32_t *)p[4];
+    const uint32_t zero[1] = {0};
+    int ok = (hl != NULL) != (eoff != NULL);
+    uint32_t ne = 0;
+    if (ok && hl) ok = len[1] / 4 == n;
+    if (ok && eoff) {
+        ok = len[2] / 4 == (size_t)n + 1 && eoff[0] == 0;
+        ne = ok ? eoff[n] : 0;
+        ok = ok && len[5] / 8 >= ne && (ne == 0 || (len[4] / 4 >= (size_t)ne + 1 && aoff[ne] <= len[3]));
+    }
+    if (!ok) { napi_throw_type_error(env, NULL, "docsetFork: one selector, and table lengths that agree"); return NULL; }
+    hm_text *t = NULL;
+    uint32_t first = 0;
+    int st = hm_docset_fork(d->ds, n, (const uint32_t *)p[0], hl, eoff, p[3] ? (const char *)p[3] : "",
+                            ne ? aoff : zero, ne ? (const double *)p[5] : NULL, &first, &t);
+    if (st) return throw_status(env, d->engine, st, "hm_docset_fork");
+    napi_value o = text_object(env, &t);
+    set(env, o, "first", u32v(env, first));
+    if (t) hm_text_free(t);
+    return o;
+}
+
 /* docsetMaterializePatch(docset, ids Uint32Array, histLen Uint32Array) -> JSON text, per request
  * {"doc", "history", "patch"}: the patch of the document as it was at that history length (clock, deps,
  * per-op diffs from the device), or "patch": null with "host": true when the prefix assigns list /
@@ -1407,7 +1444,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"docsetCreate", DocsetCreate}, {"docsetOpen", DocsetOpen}, {"docsetApply", DocsetApply}, {"docsetApplyPacked", DocsetApplyPacked},
         {"docsetHistoryPrefix", DocsetHistoryPrefix}, {"docsetClockUpdate", DocsetClockUpdate},
         {"docsetView", DocsetView}, {"docsetBlocked", DocsetBlocked}, {"docsetWaiting", DocsetWaiting},
-        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetFields", DocsetFields}, {"docsetMaterialize", DocsetMaterialize}, {"docsetMaterializePatch", DocsetMaterializePatch}, {"docsetMaterializePatchEx", DocsetMaterializePatchEx}, {"docsetMaterializePatchAt", DocsetMaterializePatchAt}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
+        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetFields", DocsetFields}, {"docsetMaterialize", DocsetMaterialize}, {"docsetFork", DocsetFork}, {"docsetMaterializePatch", DocsetMaterializePatch}, {"docsetMaterializePatchEx", DocsetMaterializePatchEx}, {"docsetMaterializePatchAt", DocsetMaterializePatchAt}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
         {"cursorsCreate", CursorsCreate}, {"cursorsReserve", CursorsReserve}, {"cursorsUpdate", CursorsUpdate},
         {"cursorsGet", CursorsGet}, {"cursorsEntry", CursorsEntry}, {"cursorsDocsWithActors", CursorsDocsWithActors},
         {"syncRanges", SyncRanges}, {"decodeBlocks", DecodeBlocks}, {"commCreateLocalDocsets", CommCreateLocalDocsets},

@@ -341,6 +341,9 @@ class DocStore:
         for i, h in enumerate(handles):          # rolled-back documents: the interner rolls back too
             if r.docs[i]["status"] != 0:
                 self.enc[h].restore(snaps[i])
+        src, self._forked = getattr(self, "_forked", None), None
+        if src is not None:                      # a fork batch: the forks' encoders are their parents', cloned
+            self._clone_encoders(src, handles, r.docs["status"])
         return r
 
     def apply(self, items, extra_actors=None) -> BatchResult:
@@ -592,6 +595,82 @@ class DocStore:
                     "hm_store_materialize")
         return b, r, clog, olog
 
+    # -- a document as it was, kept: Repo.fork / Repo.merge into a fresh document ----------------------
+    def _open_forks(self, n: int) -> List[int]:
+        return [self.open() for _ in range(n)]
+
+    def _order_rows(self, hs: np.ndarray, clocks, order) -> Optional[np.ndarray]:
+        """[n, S] rank rows (NONE ends a row) of fork()'s `order`."""
+        if order is None:
+            return None
+        n, S = len(hs), self.S
+        if isinstance(order, np.ndarray):
+            rows = np.ascontiguousarray(order, np.uint32)
+            assert rows.shape == (n, S), rows.shape
+            return rows
+        if isinstance(order, str):
+            assert order == "clock", order
+            if clocks is None or isinstance(clocks, np.ndarray):
+                raise EngineError("order='clock' reads the key order of {actorId: seq} clocks")
+            order = [list(c.keys()) for c in clocks]
+        rows = np.full((n, S), NONE, np.uint32)
+        for i, (h, row) in enumerate(zip(hs, order)):
+            rank = {a: r for r, a in enumerate(self.enc[h].actors)} if h < len(self.enc) else {}
+            k = 0
+            for a in row:
+                if isinstance(a, str):
+                    if a not in rank:                  # (an id the parent never saw names no change)
+                        continue
+                    a = rank[a]
+                if k >= S:
+                    raise EngineError(f"request {i}: more than a_stride {S} actors in the order")
+                rows[i, k] = int(a)
+                k += 1
+        return rows
+
+    def fork_submit(self, handles, history=None, clocks=None, order=None, min_clock=False, into=None) -> Tuple[List[int], int]:
+        """hm_store_fork_submit: (the forks' handles, the batch id); wait() returns one row per fork.
+        into: empty documents to fork into (default: newly opened ones)."""
+        hs = np.ascontiguousarray(handles, np.uint32)
+        n = len(hs)
+        hl, rows = self._selector(hs, history, clocks)
+        orow = self._order_rows(hs, clocks, order)
+        new = self._open_forks(n) if into is None else [int(h) for h in into]
+        dst = np.array(new, np.uint32)
+        assert len(dst) == n
+        bid = ctypes.c_uint64()
+        self._check(self._L.hm_store_fork_submit(self._h, n, _p(hs), _p(hl), _p(rows), _p(orow), _p(dst),
+                                                 1 if min_clock else 0, ctypes.byref(bid)), "hm_store_fork_submit")
+        snaps = [self.enc[h].snapshot() if h < len(self.enc) else None for h in new]
+        self._pending = (bid.value, new, snaps, (hs, hl, rows, orow, dst))
+        self._forked = [int(h) for h in hs]
+        return new, bid.value
+
+    def fork(self, handles, history=None, clocks=None, order=None, min_clock=False) -> List[int]:
+        """New resident documents: document handles[i] (a handle may repeat) as it was at history
+        length history[i] or at the clock clocks[i] (materialize's selectors), indistinguishable from
+        a fresh document that received the selected changes in one applyChanges round — in the
+        parent's history order (order=None), or actor after actor, each actor's seqs ascending
+        (a clock only): order = 'clock' (the {actorId: seq} clocks' own key order, what Repo.merge
+        hands over), per request a sequence of actor ids or ranks, or [n, S] rank rows ending in NONE.
+        min_clock: the forks get their parent's minimumClock.  The forks keep the parent's id spaces;
+        their host encoders are the parents', cloned, so they take later submits.  Returns the new
+        handles; the batch's result rows are left in self.fork_result."""
+        new, _ = self.fork_submit(handles, history, clocks, order, min_clock)
+        self.fork_result = self.wait()
+        return new
+
+    def _clone_encoders(self, src: List[int], dst: List[int], status) -> None:
+        for p, h, st in zip(src, dst, status):
+            if st != 0 or p >= len(self.enc) or h >= len(self.enc):
+                continue
+            e, f = self.enc[p], DocEncoder(self.pool, self.enc[p].keep_log)
+            f.actors, f.objs, f.obj_list = list(e.actors), dict(e.objs), list(e.obj_list)
+            f.regs, f.reg_list, f.content, f.flags = dict(e.regs), list(e.reg_list), dict(e.content), e.flags
+            if f.keep_log:                             # (the host mirror of the log, for rendering and the oracle)
+                f.log_changes, f.log_deps, f.log_ops = self.log(h)
+            self.enc[h] = f
+
     def op_diff_sizes(self, handles, frm, to, lists=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """hm_store_op_diff_sizes: ([n, 2] diff rows / survivor rows per request, flags [n], their [2] totals).
         lists=True: the sizes of op_diffs(..., lists=True)."""
@@ -736,6 +815,17 @@ class RowStore(DocStore):
         first = ctypes.c_uint32()
         self._check(self._L.hm_doc_open_n(self._h, n, ctypes.byref(first)), "hm_doc_open_n")
         return first.value
+
+    def _open_forks(self, n: int) -> List[int]:
+        h0 = self.open_n(n)
+        return list(range(h0, h0 + n))
+
+    def fork_submit(self, handles, history=None, clocks=None, order=None, min_clock=False, into=None) -> Tuple[List[int], int]:
+        """DocStore.fork_submit over rank rows (clocks [n, S]; order [n, S] or sequences of ranks)."""
+        new, bid = super().fork_submit(handles, history, clocks, order, min_clock, into)
+        self._pending = (bid, len(new), None, self._pending[3])
+        self._forked = None
+        return new, bid
 
     def submit_batch(self, b: Batch, handles: np.ndarray) -> int:
         hs = np.ascontiguousarray(handles, np.uint32)

@@ -512,7 +512,8 @@ int hm_missing_changes_host(hm_engine *e, const hm_batch *b, const hm_results *r
 typedef struct {          /* 64 B */
     uint64_t totals[4];   /* changes, deps, ops, registers of all requests */
     uint32_t max_changes, max_ops, max_regs, max_objs, max_deps, doc_flags;  /* hm_batch launch hints */
-    uint32_t bad;         /* _device form: 1 a handle outside the source, 2 a change row outside its document */
+    uint32_t bad;         /* _device form: 1 a handle outside the source, 2 a change row outside its document
+                           * (store forms also: 4 a bad actor order row, 8 a bad fork destination) */
     uint32_t pad;
 } hm_past_summary;
 typedef struct {
@@ -541,6 +542,37 @@ int hm_store_past_sizes(hm_store *s, uint32_t n, const uint32_t *doc_handles, co
  * once more at its end. */
 int hm_store_materialize(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *hist_len,
                          const uint32_t *clock_rows, const hm_past_out *out, uint64_t *out_totals);
+/* Fork: resident documents as they were, kept as new resident documents (src/RepoFrontend.ts:95-99
+ * Repo.fork = create() + merge(fork, parent); src/RepoBackend.ts:213-217 the merge = cursors.update +
+ * syncReadyActors, which hands the new document each listed actor's changes 1 .. clock[actor], actor
+ * after actor).  Request i = document src_handles[i] (only read; a handle may repeat) with
+ * hm_store_materialize's selectors, into the empty document dst_handles[i]: afterwards that document
+ * is indistinguishable from a fresh one that received the selected changes, in the stated order, in
+ * one applyChanges round.  It keeps the parent's id spaces (ranks, object and register ids; n_actors /
+ * n_regs / n_objs / flags are the parent's totals).
+ *   actor_order == NULL   history order (the parent's own), the only order a history length allows
+ *   actor_order           with clock_rows only: row i ([a_stride], HM_NONE ends it) lists actor ranks in
+ *                         hand-over order (the clock's key order); each contributes its seqs
+ *                         1 .. min(clock[a], opSet.clock[a]) ascending.  Every rank whose clock entry
+ *                         selects a change must be listed, none twice, all below the document's n_actors.
+ *   HM_FORK_MIN_CLOCK     the fork gets the parent's minimumClock row (hm_doc_set_min_clock); without it
+ *                         the fork has none (a row an earlier, undone fork left is cleared)
+ * The selection is gathered on the device into a buffer of the store and handed to the device-table
+ * submit: no row passes through the host, the one read-back is the count pass's totals.  The call is
+ * the store's batch in flight: hm_batch_wait / hm_batch_wait_device return one row per request, a
+ * merge that throws rolls its destination back, hm_batch_undo empties every destination again.  A
+ * selection of no changes leaves the destination an empty document (with the parent's totals).
+ * HM_ERR_INVALID, nothing changed: n == 0, both or neither selector, an order with hist_len, a bad
+ * order row, a source outside the store, a destination that is outside the store, repeated, also a
+ * source, or holds changes (or totals above its parent's), a batch in flight.  A call's rows stay below
+ * 2^32 (HM_ERR_NOMEM).  The destinations' minimumClock rows are written once the checks have passed,
+ * before the submit: a call that fails later (HM_ERR_NOMEM / HM_ERR_DEVICE from the submit) leaves them
+ * replaced — the parent's row, or none — on otherwise unchanged, empty destinations; a row the caller
+ * had set on an empty destination with hm_doc_set_min_clock does not survive a fork into it either way. */
+#define HM_FORK_MIN_CLOCK 1u
+int hm_store_fork_submit(hm_store *s, uint32_t n, const uint32_t *src_handles, const uint32_t *hist_len,
+                         const uint32_t *clock_rows, const uint32_t *actor_order, const uint32_t *dst_handles, uint32_t flags,
+                         uint64_t *out_batch_id);
 /* The gather alone over the tables of a merged cold batch (b's docs / changes / deps / ops, r's docs /
  * hist), everything in device memory, enqueued on `stream` (NULL = the engine's) without
  * synchronising.  Request i = document doc_index[i] of b (NULL: document i); hist_len / clock_rows
@@ -1045,6 +1077,19 @@ int hm_docset_materialize_patch_ex(hm_docset *ds, uint32_t n, const uint32_t *do
  * refusals are those of hm_docset_materialize_patch_ex. */
 int hm_docset_materialize_patch_at(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off, const char *actor_ids,
                                    const uint32_t *actor_off, const double *seqs, uint32_t opts, hm_text **out);
+/* Fork (Repo.fork / Repo.merge into a fresh document; hm_store_fork_submit per stride class): n new
+ * documents are opened (*out_first = the first one's id, request i gets *out_first + i); request i is
+ * parent docs[i] (may repeat) at history length hist_len[i], in the parent's history order, or at the
+ * clock given as hm_docset_materialize takes one, handed over actor after actor in entry order (an id
+ * the parent never saw is dropped, a repeated id counts once with its last seq); exactly one of
+ * hist_len and entry_off is not NULL.  The fork lives in its parent's stride class with the parent's
+ * interners and rank tables, the content table of the selected (actor, seq) and the per-op tables of
+ * the gathered ops.  *out = what a first hm_docset_apply round handing the fork those changes returns
+ * (result rows, the one combined patch, DocBackend.clock), in the docset's format, whatever its flags;
+ * actors the fork does not hold appear nowhere in it.  A parent not placed yet gives an empty fork.
+ * All-or-nothing as hm_docset_apply is (a failed call leaves the new documents empty). */
+int hm_docset_fork(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, const uint32_t *entry_off,
+                   const char *actor_ids, const uint32_t *actor_off, const double *seqs, uint32_t *out_first, hm_text **out);
 /* the merged document: {uuid: {"type", "keys": [[key, entry]], "elems": [[elemId, entry]]}} */
 int hm_docset_view(hm_docset *ds, uint32_t doc, hm_text **out);
 /* counters: calls, documents, class moves, net patches from the hit registers, net patches from every

@@ -1236,6 +1236,7 @@ struct hm_docset {
     uint64_t routing[3] = {0, 0, 0};                         // document rounds: incremental, re-merged, handed back
     uint64_t stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};           // rounds, docs, restrides, hit-register patches, full patches,
                                                              // per-op patches, replay mismatches, replay checks skipped
+    uint64_t mstat[2] = {0, 0};                              // merge requests: device route, host route
     DocSt &doc(uint32_t i) { return chunks[i / CHUNK][i % CHUNK]; }
 };
 
@@ -2103,6 +2104,339 @@ int fork_docs(hm_docset *ds, uint32_t n, const uint32_t *parents, const uint32_t
     return finish(c, out);
 }
 
+// ---------------- merge into a live document ----------------
+// One request's maps from its source's id spaces into its destination's (hm_merge_maps' slices), the
+// selector rows in the source's ranks, and what the destination's interners looked like before.
+struct MergeReq {
+    std::vector<uint32_t> amap;                              // source actor id -> destination actor id
+    std::vector<uint32_t> rank, omap, rmap, smap, cmap;      // rank: [source ranks]
+    std::vector<uint32_t> clock, have, order;                // [source ranks]; order: listed ranks
+    bool device = false, empty = false;                      // route; empty: the source holds nothing
+};
+
+// a new actor re-ranks the document (JS string order): decode_round's step, for actors interned since
+// `before`; the round keeps the old tables for the rollback and the remap for the store
+void rerank(DocSt &d, Round &R, uint32_t before) {
+    const uint32_t na = d.actors.size();
+    R.s_rank_of = d.rank_of; R.s_by_rank = d.by_rank;
+    std::vector<uint16_t> order(na);
+    for (uint32_t i = 0; i < na; i++) order[i] = (uint16_t)i;
+    std::sort(order.begin(), order.end(), [&](uint16_t x, uint16_t y) {
+        return js_less(d.actors.ptr(x), d.actors.len(x), d.actors.ptr(y), d.actors.len(y)); });
+    std::vector<uint16_t> rank_of(na);
+    for (uint32_t r = 0; r < na; r++) rank_of[order[r]] = (uint16_t)r;
+    bool ident = true;
+    std::vector<uint8_t> remap(before);
+    for (uint32_t r = 0; r < before; r++) {
+        remap[r] = (uint8_t)rank_of[d.by_rank[r]];
+        ident &= remap[r] == r;
+    }
+    if (!ident) R.remap = std::move(remap);
+    d.rank_of = std::move(rank_of);
+    d.by_rank = std::move(order);
+}
+
+// rows of the source's id spaces into the destination's, on the host (the host route; the device
+// route's rename pass does the same through the same maps); false: an id outside its map
+bool rename_rows(const MergeReq &q, std::vector<hm_change_row> &ch, std::vector<hm_dep_row> &dp, std::vector<hm_op_row> &op) {
+    bool ok = true;
+    auto thru = [&](const std::vector<uint32_t> &m, uint32_t id) -> uint32_t {
+        if (id >= m.size() || m[id] == HM_NONE) { ok = false; return id; }
+        return m[id];
+    };
+    for (hm_change_row &c : ch) { c.actor = (uint16_t)thru(q.rank, c.actor); c.content_id = thru(q.cmap, c.content_id); }
+    for (hm_dep_row &d : dp) d.actor = (uint16_t)thru(q.rank, d.actor);
+    for (hm_op_row &o : op) {
+        o.obj = thru(q.omap, o.obj);
+        if (o.reg != HM_NONE) o.reg = thru(q.rmap, o.reg);
+        if (o.parent != HM_HEAD) o.parent = thru(q.rmap, o.parent);
+        if (o.action >= HM_SET) o.key = thru(q.smap, o.key);
+        if (o.vtag == HM_V_STR) o.value = thru(q.smap, (uint32_t)o.value);
+        else if (o.vtag == HM_V_OBJ) o.value = thru(q.omap, (uint32_t)o.value);
+    }
+    return ok;
+}
+
+// hm_docset_merge_from: destination dst[i] is handed source src[i]'s applied changes above what it was
+// handed before (its DocBackend.clock) up to the request's clock, actor after actor in the clock's key
+// order.  The destinations are rounds of one Call whose rows come from the stores' merge batches (the
+// device route: both documents in one stride class, the destination staying in it) or from the
+// source's log read back and renamed here (the host route: every other request), and whose later phases
+// are hm_docset_apply's.
+int merge_docs(hm_docset *ds, uint32_t n, const uint32_t *dst, const uint32_t *src, const uint32_t *entry_off,
+               const char *actor_ids, const uint32_t *actor_off, const double *seqs, hm_text *out) {
+    std::vector<uint32_t> no_blocks(n + 1, 0);
+    Call c{ds, nullptr, nullptr, no_blocks.data(), dst, n};
+    int rc = c.validate();
+    if (rc) return rc;
+    {
+        const uint32_t nd = ds->n_docs.load();
+        std::vector<uint8_t> is_dst(nd, 0);
+        for (uint32_t i = 0; i < n; i++) is_dst[dst[i]] = 1;
+        for (uint32_t i = 0; i < n; i++)
+            if (src[i] >= nd || is_dst[src[i]]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "a merge's source is no document, or a destination of the same call");
+    }
+    c.R.resize(n);
+    std::vector<MergeReq> Q(n);
+    // the maps: every actor, object, register and string of the source is interned into the destination
+    // (deps and links may name any); content ids of the (actor, seq) entries the selector covers
+    for (uint32_t i = 0; i < n; i++) {                       // (every round's snapshot first: fail() rolls all of them back)
+        Round &x = c.R[i];
+        DocSt &d = ds->doc(dst[i]);
+        x.doc = dst[i];
+        if (!d.ready) d.setup();
+        x.s_actors = d.actors.size(); x.s_objs = d.objs.size(); x.s_regs = d.regs.size(); x.s_strs = d.strs.size();
+        x.s_cents = (uint32_t)d.cents.size(); x.s_content = d.n_content; x.s_ops = (uint32_t)d.op_actor.size();
+        x.started = true;
+    }
+    try {
+    // the destinations' DocBackend.clock rows, one read per stride class
+    std::vector<std::vector<uint32_t>> backs(n);
+    for (uint32_t k = 0; k < N_CLASS; k++) {
+        std::vector<uint32_t> idx, hh;
+        for (uint32_t i = 0; i < n; i++)
+            if (ds->doc(dst[i]).cls == k) { idx.push_back(i); hh.push_back(ds->doc(dst[i]).handle); }
+        if (idx.empty()) continue;
+        const uint32_t Sd = STRIDES[k];
+        std::vector<uint32_t> rows(idx.size() * (size_t)Sd);
+        if ((rc = hm_store_back_clocks(ds->stores[k], (uint32_t)idx.size(), hh.data(), rows.data()))) return c.fail(rc);
+        for (size_t j = 0; j < idx.size(); j++) backs[idx[j]].assign(rows.begin() + j * Sd, rows.begin() + (j + 1) * Sd);
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        Round &x = c.R[i];
+        MergeReq &q = Q[i];
+        DocSt &d = ds->doc(dst[i]);
+        const DocSt &p = ds->doc(src[i]);
+        q.empty = p.cls == NO_CLASS || !p.ready;
+        bool f, fresh_any = false;
+        if (!q.empty) {
+            q.amap.resize(p.actors.size());
+            for (uint32_t a = 0; a < p.actors.size(); a++) { q.amap[a] = d.actors.get(p.actors.ptr(a), p.actors.len(a), 0, f); fresh_any |= f; }
+        }
+        if (d.actors.size() > MAX_ACTORS) { x.status = HM_ERR_UNSUPPORTED; rollback(d, x); x.started = false; continue; }
+        if (fresh_any) rerank(d, x, x.s_actors);
+        x.n_actors = (uint16_t)d.actors.size();
+        if (!q.empty) {
+            const uint32_t ns = (uint32_t)p.by_rank.size();
+            q.rank.resize(ns); q.clock.assign(ns, 0); q.have.assign(ns, 0);
+            for (uint32_t r = 0; r < ns; r++) q.rank[r] = d.rank_of[q.amap[p.by_rank[r]]];
+            q.omap.resize(p.objs.size());
+            for (uint32_t o = 0; o < p.objs.size(); o++) q.omap[o] = d.objs.get(p.objs.ptr(o), p.objs.len(o), 0, f);
+            q.rmap.resize(p.regs.size());
+            for (uint32_t g = 0; g < p.regs.size(); g++) {
+                const uint32_t o = p.regs.tag(g);
+                q.rmap[g] = o < q.omap.size() ? d.regs.get(p.regs.ptr(g), p.regs.len(g), q.omap[o], f) : HM_NONE;
+            }
+            q.smap.resize(p.strs.size());
+            for (uint32_t s = 0; s < p.strs.size(); s++) q.smap[s] = d.strs.get(p.strs.ptr(s), p.strs.len(s), 0, f);
+            // the clock, by actor id in key order (the hand-over order); an id the source never saw is dropped
+            for (uint32_t e = entry_off[i]; e < entry_off[i + 1]; e++) {
+                if (actor_off[e + 1] < actor_off[e]) return c.fail(hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease"));
+                const uint32_t a = p.actors.find(actor_ids + actor_off[e], actor_off[e + 1] - actor_off[e], 0);
+                if (a == HM_NONE || a >= p.rank_of.size()) continue;
+                const uint32_t r = p.rank_of[a];
+                if (std::find(q.order.begin(), q.order.end(), r) == q.order.end()) q.order.push_back(r);
+                q.clock[r] = seq_u32(seqs[e]);
+            }
+            // have: the destination's DocBackend.clock, in the source's ranks
+            if (d.cls != NO_CLASS) {
+                const std::vector<uint32_t> &back = backs[i];
+                const uint32_t Sd = (uint32_t)back.size();
+                for (uint32_t r = 0; r < ns; r++) {
+                    const uint32_t da = q.amap[p.by_rank[r]];
+                    if (da < x.s_actors) {
+                        const uint32_t old = x.s_rank_of.empty() ? d.rank_of[da] : x.s_rank_of[da];
+                        if (old < Sd) q.have[r] = back[old];
+                    }
+                }
+            }
+            q.cmap.assign(p.n_content, HM_NONE);
+            for (const DocSt::CE &ce : p.cents) {
+                const uint32_t a = (uint32_t)(ce.key >> 32), sq = (uint32_t)ce.key;
+                if (a >= p.rank_of.size() || ce.cid >= q.cmap.size()) continue;
+                const uint32_t r = p.rank_of[a];
+                if (sq <= q.have[r] || sq > q.clock[r]) continue;
+                q.cmap[ce.cid] = d.content_id(((uint64_t)q.amap[a] << 32) | sq, ce.h);
+            }
+        }
+        x.n_regs = d.regs.size(); x.n_objs = d.objs.size(); x.flags = q.empty ? 0 : p.flags;
+    }
+    // routes: the device route where both documents live in one class and the destination stays in it —
+    // unless the class also takes host-route rounds in this call (a store has one batch in flight, and
+    // only its last batch can be undone: such a class's rounds all go through merge_class)
+    bool host_cls[N_CLASS] = {};
+    for (uint32_t i = 0; i < n; i++) {
+        const DocSt &d = ds->doc(dst[i]), &p = ds->doc(src[i]);
+        if (c.R[i].status != HM_OK) continue;
+        const uint8_t want = std::max<uint8_t>(class_for(c.R[i].n_actors), d.cls == NO_CLASS ? 0 : d.cls);
+        Q[i].device = !Q[i].empty && d.cls != NO_CLASS && p.cls == d.cls && want == d.cls;
+        if (!Q[i].device) host_cls[want] = true;
+    }
+    for (uint32_t i = 0; i < n; i++)
+        if (Q[i].device && host_cls[ds->doc(dst[i]).cls]) Q[i].device = false;
+    // the host route: the source's log and hist read back, the selection laid out actor after actor,
+    // renamed, then placed and merged as decoded rows are
+    for (uint32_t i = 0; i < n; i++) {
+        Round &x = c.R[i];
+        MergeReq &q = Q[i];
+        if (x.status != HM_OK || q.device) continue;
+        ds->mstat[1]++;
+        if (q.empty) continue;
+        const DocSt &p = ds->doc(src[i]);
+        hm_store *ps = ds->stores[p.cls];
+        hm_doc_info_t inf;
+        if ((rc = hm_doc_info(ps, p.handle, &inf))) return c.fail(rc);
+        std::vector<hm_change_row> lc(inf.n_changes);
+        std::vector<hm_dep_row> ld(inf.n_deps);
+        std::vector<hm_op_row> lo(inf.n_ops);
+        std::vector<int32_t> hist(inf.n_changes);
+        if ((rc = hm_doc_log(ps, p.handle, lc.data(), ld.data(), lo.data())) ||
+            (rc = hm_doc_read(ps, p.handle, hist.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)))
+            return c.fail(rc);
+        std::unordered_map<uint64_t, uint32_t> at;            // (rank, seq) of an applied change -> its log row
+        for (uint32_t k = 0; k < lc.size(); k++)
+            if (hist[k] >= 0) at[((uint64_t)lc[k].actor << 32) | lc[k].seq] = k;
+        std::vector<uint32_t> oplog_at;                        // the gathered ops' source log indices
+        for (uint32_t r : q.order) {
+            for (uint64_t sq = (uint64_t)q.have[r] + 1; sq <= q.clock[r]; sq++) {
+                auto it = at.find(((uint64_t)r << 32) | sq);
+                if (it == at.end()) break;                     // (an actor's applied changes are its seqs 1 .. opSet.clock)
+                hm_change_row cr = lc[it->second];
+                if ((uint64_t)cr.dep_off + cr.n_deps > ld.size() || (uint64_t)cr.op_first + cr.n_ops > lo.size())
+                    return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a merge source's change rows outside its log"));
+                const uint32_t d0 = cr.dep_off, o0 = cr.op_first;
+                cr.dep_off = (uint32_t)x.dp.size(); cr.op_first = (uint32_t)x.op.size();
+                x.ch.push_back(cr);
+                x.dp.insert(x.dp.end(), ld.begin() + d0, ld.begin() + d0 + cr.n_deps);
+                x.op.insert(x.op.end(), lo.begin() + o0, lo.begin() + o0 + cr.n_ops);
+                for (uint32_t k = 0; k < cr.n_ops; k++) oplog_at.push_back(o0 + k);
+            }
+        }
+        if (!rename_rows(q, x.ch, x.dp, x.op)) return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a merge's rows name an id its source's tables do not hold"));
+        DocSt &d = ds->doc(dst[i]);
+        for (uint32_t lo_i : oplog_at) {
+            if (lo_i >= p.op_actor.size() || p.op_actor[lo_i] >= q.amap.size()) return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a merge's ops outside its source's log"));
+            d.op_actor.push_back((uint16_t)q.amap[p.op_actor[lo_i]]);
+            d.op_dt.push_back(p.op_dt[lo_i]);
+        }
+    }
+    // place the host-route rounds (Call::place, for them alone)
+    for (uint32_t i = 0; i < n; i++) {
+        Round &x = c.R[i];
+        if (x.status != HM_OK || Q[i].device) continue;
+        DocSt &d = ds->doc(x.doc);
+        uint8_t k = class_for(x.n_actors);
+        if (d.cls != NO_CLASS && d.cls > k) k = d.cls;
+        x.cls = k;
+        x.placed = d.cls == NO_CLASS;
+        x.moved = !x.placed && k != d.cls;
+        x.handle = d.handle;
+        c.by_cls[k].push_back(i);
+    }
+    for (uint32_t k = 0; k < N_CLASS; k++)
+        if (!c.by_cls[k].empty() && (rc = c.merge_class(k))) return c.fail(rc);
+    // the device route, a merge batch per class
+    std::vector<uint32_t> dev[N_CLASS];
+    for (uint32_t i = 0; i < n; i++)
+        if (c.R[i].status == HM_OK && Q[i].device) dev[ds->doc(dst[i]).cls].push_back(i);
+    for (uint32_t k = 0; k < N_CLASS; k++) {
+        if (dev[k].empty()) continue;
+        c.by_cls[k] = dev[k];
+        const auto &rows = c.by_cls[k];
+        const uint32_t S = STRIDES[k], m = (uint32_t)rows.size();
+        hm_store *st = ds->stores[k];
+        ds->mstat[0] += m;
+        std::vector<uint32_t> sh(m), dh(m), clk((size_t)m * S, 0u), hav((size_t)m * S, 0u), ord((size_t)m * S, HM_NONE), tot((size_t)m * 4),
+            rank((size_t)m * S, HM_NONE), off[4], tab[4];
+        std::vector<uint8_t> remap;
+        bool any_remap = false;
+        for (uint32_t j = 0; j < m; j++) any_remap |= !c.R[rows[j]].remap.empty();
+        if (any_remap) {
+            remap.resize((size_t)m * S);
+            for (uint32_t j = 0; j < m; j++) for (uint32_t a = 0; a < S; a++) remap[(size_t)j * S + a] = (uint8_t)a;
+        }
+        for (auto &o : off) o.assign(1, 0u);
+        for (uint32_t j = 0; j < m; j++) {
+            const uint32_t i = rows[j];
+            Round &x = c.R[i];
+            const MergeReq &q = Q[i];
+            const DocSt &d = ds->doc(dst[i]), &p = ds->doc(src[i]);
+            x.cls = (uint8_t)k; x.handle = d.handle; x.row = j;
+            sh[j] = p.handle; dh[j] = d.handle;
+            for (uint32_t r = 0; r < q.rank.size() && r < S; r++) { clk[(size_t)j * S + r] = q.clock[r]; hav[(size_t)j * S + r] = q.have[r]; rank[(size_t)j * S + r] = q.rank[r]; }
+            for (uint32_t r = 0; r < q.order.size() && r < S; r++) ord[(size_t)j * S + r] = q.order[r];
+            for (size_t a = 0; a < x.remap.size() && a < S; a++) remap[(size_t)j * S + a] = x.remap[a];
+            tot[4 * (size_t)j] = x.n_actors; tot[4 * (size_t)j + 1] = x.n_regs; tot[4 * (size_t)j + 2] = x.n_objs; tot[4 * (size_t)j + 3] = x.flags;
+            const std::vector<uint32_t> *mp[4] = {&q.omap, &q.rmap, &q.smap, &q.cmap};
+            for (int t = 0; t < 4; t++) { tab[t].insert(tab[t].end(), mp[t]->begin(), mp[t]->end()); off[t].push_back((uint32_t)tab[t].size()); }
+        }
+        for (auto &t : tab) if (t.empty()) t.push_back(HM_NONE);
+        hm_merge_maps mm = {tot.data(), rank.data(), off[0].data(), tab[0].data(), off[1].data(), tab[1].data(), off[2].data(), tab[2].data(),
+                            off[3].data(), tab[3].data()};
+        ClsOut &O = c.co[k];
+        if ((rc = hm_store_merge_from_submit(st, m, sh.data(), hav.data(), clk.data(), ord.data(), dh.data(), &mm,
+                                             any_remap ? remap.data() : nullptr, &O.id)))
+            return c.fail(rc);
+        O.sub = true;
+        // what a decode would have handed each round: the renamed change rows and the op map come back;
+        // the op rows through the map from the source's own host copy of its log, renamed here, where
+        // the docset keeps one (the per-op patch modes), and renamed from the device otherwise
+        const bool host_ops = ds->patches && ds->op_diffs;
+        std::vector<hm_doc_row> gd;
+        std::vector<hm_change_row> gc;
+        std::vector<hm_op_row> go;
+        std::vector<uint32_t> gl;
+        if ((rc = hm_store_fork_rows(st, O.id, gd, gc, host_ops ? nullptr : &go, gl))) return c.fail(rc);
+        O.res.resize(m); O.clock.resize((size_t)m * S); O.back.resize((size_t)m * S); O.heads.resize((size_t)m * S);
+        if ((rc = hm_batch_wait(st, O.id, O.res.data(), O.clock.data(), O.back.data(), O.heads.data()))) return c.fail(rc);
+        O.sub = false;
+        O.done = true;
+        uint32_t r3[3] = {0, 0, 0};
+        if (hm_store_last_routing(st, r3) == HM_OK)
+            for (int t = 0; t < 3; t++) c.call_routing[t] += r3[t];
+        for (uint32_t j = 0; j < m; j++) {
+            const uint32_t i = rows[j];
+            Round &x = c.R[i];
+            const MergeReq &q = Q[i];
+            DocSt &d = ds->doc(dst[i]);
+            const DocSt &p = ds->doc(src[i]);
+            const hm_doc_row &r = gd[j];
+            if ((uint64_t)r.change_off + r.n_changes > gc.size() || (uint64_t)r.op_off + r.n_ops > gl.size() ||
+                (!host_ops && (uint64_t)r.op_off + r.n_ops > go.size()))
+                return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a merge's rows outside the gathered tables"));
+            x.ch.assign(gc.begin() + r.change_off, gc.begin() + r.change_off + r.n_changes);
+            for (hm_change_row &cr : x.ch) { cr.dep_off -= r.dep_off; cr.op_first -= r.op_off; }
+            if (!host_ops) x.op.assign(go.begin() + r.op_off, go.begin() + r.op_off + r.n_ops);
+            else {
+                x.op.resize(r.n_ops);
+                for (uint32_t t = 0; t < r.n_ops; t++) {
+                    const uint32_t lo = gl[r.op_off + t];
+                    if (lo >= p.oplog.size()) return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a merge's ops outside its source's log"));
+                    x.op[t] = p.oplog[lo];
+                }
+                std::vector<hm_change_row> no_ch;
+                std::vector<hm_dep_row> no_dp;
+                if (!rename_rows(q, no_ch, no_dp, x.op))
+                    return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a merge's ops name an id its source's tables do not hold"));
+            }
+            for (uint32_t t = 0; t < r.n_ops; t++) {
+                const uint32_t lo = gl[r.op_off + t];
+                if (lo >= p.op_actor.size() || p.op_actor[lo] >= q.amap.size())
+                    return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a merge's ops outside its source's log"));
+                d.op_actor.push_back((uint16_t)q.amap[p.op_actor[lo]]);
+                d.op_dt.push_back(p.op_dt[lo]);
+            }
+            x.res = O.res[j];
+            x.clock = O.clock.data() + (size_t)j * S; x.back = O.back.data() + (size_t)j * S; x.heads = O.heads.data() + (size_t)j * S;
+        }
+    }
+    } catch (...) {
+        return c.fail(hm_engine_fail(ds->e, HM_ERR_NOMEM, "out of memory in hm_docset_merge_from"));
+    }
+    c.mark("merge_from");
+    return finish(c, out);
+}
+
 // ---------------- what the host queries over many documents share ----------------
 // the request's documents exist (and, with entry_off, its entry ranges do not decrease)
 int check_request(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off = nullptr) {
@@ -2658,6 +2992,37 @@ int hm_docset_fork(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32
     } catch (...) {
         return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_fork");
     }
+}
+
+int hm_docset_merge_from(hm_docset *ds, uint32_t n, const uint32_t *dst_docs, const uint32_t *src_docs, const uint32_t *entry_off,
+                         const char *actor_ids, const uint32_t *actor_off, const double *seqs, hm_text **out) {
+    if (!ds || !out || !n || !dst_docs || !src_docs || !entry_off) return HM_ERR_INVALID;
+    *out = nullptr;
+    Busy b(ds);
+    if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "hm_docset_merge_from: another call on this docset is running");
+    if (ds->broken)
+        return hm_engine_fail(ds->e, HM_ERR_DEVICE, "hm_docset_merge_from: an earlier failed call could not be undone on its store");
+    try {
+        int rc = check_request(ds, n, src_docs, entry_off);
+        if (rc) return rc;
+        if (entry_off[n] - entry_off[0] && (!actor_ids || !actor_off || !seqs)) return HM_ERR_INVALID;
+        std::unique_ptr<hm_text> t(new hm_text());
+        const uint64_t before[2] = {ds->mstat[0], ds->mstat[1]};
+        if ((rc = merge_docs(ds, n, dst_docs, src_docs, entry_off, actor_ids, actor_off, seqs, t.get()))) {
+            ds->mstat[0] = before[0]; ds->mstat[1] = before[1];
+            return rc;
+        }
+        *out = t.release();
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_merge_from");
+    }
+}
+
+int hm_docset_merge_stats(const hm_docset *ds, uint64_t *out2) {
+    if (!ds || !out2) return HM_ERR_INVALID;
+    out2[0] = ds->mstat[0]; out2[1] = ds->mstat[1];
+    return HM_OK;
 }
 
 int hm_docset_materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, hm_text **out) {

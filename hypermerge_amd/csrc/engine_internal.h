@@ -25,7 +25,12 @@ int hm_store_materialize_sized(hm_store *s, uint32_t n, const uint32_t *doc_hand
 // the tables a fork batch in flight (hm_store_fork_submit) gathered, read back for a host that
 // mirrors the forks' logs: request i's rows are docs[i]'s ranges, op_log[k] = the parent's log op
 // index of gathered op k; ops may be NULL (the caller holds the parents' op rows and takes the forks'
-// through op_log).  Only between the fork's submit and its wait.
+// through op_log).  Only between the fork's submit and its wait.  A merge batch in flight
+// (hm_store_merge_from_submit) answers the same way: its change and op rows are the renamed ones, the
+// destinations' ids; op_log still indexes the source's log.
 #include <vector>
+// the DocBackend.clock rows of n resident documents (out[i * a_stride ..]) with one synchronise: the
+// docset's merge reads its destinations' rows per stride class, not per request
+int hm_store_back_clocks(hm_store *s, uint32_t n, const uint32_t *doc_handles, uint32_t *out);
 int hm_store_fork_rows(hm_store *s, uint64_t batch_id, std::vector<hm_doc_row> &docs, std::vector<hm_change_row> &changes,
                        std::vector<hm_op_row> *ops, std::vector<uint32_t> &op_log);

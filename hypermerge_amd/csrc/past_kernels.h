@@ -45,7 +45,18 @@ inline uint32_t hm_past_scan_chunks(uint32_t n) { return (uint32_t)(((unsigned l
 // kernels' output as without the table, byte for byte.
 #define HM_PAST_BAD_HANDLE 1u
 #define HM_PAST_BAD_ROWS 2u
+//
+// have_rows (optional, with clock_rows only): request i's row have_rows[i * S ..], in the source's rank
+// space, is a lower bound: a change is selected when it is applied and have[a] < seq <= clock[a] (what
+// syncReadyActors hands a document that was handed each actor's first have[a] changes before).  With an
+// order table actor a then contributes max(0, min(clock[a], opSet.clock[a]) - have[a]) changes and a
+// change's position is base[a] + seq - have[a] - 1, dense again; history order ranks the selection as
+// before.  The count pass's order check sees the narrowed selection.  NULL: as without the table.
+// With a history-length selector (clock_rows == NULL) the table is not read: the kernels ignore it,
+// and the store's calls refuse it before any launch.
 #define HM_PAST_BAD_ORDER 4u
+// (8: HM_FORK_BAD_DST, store_kernels.h)
+#define HM_PAST_BAD_MAP 16u
 
 struct PastArgs {
     uint32_t n;
@@ -53,6 +64,7 @@ struct PastArgs {
     const uint32_t *hist_len;                  // [n] or NULL
     const uint32_t *clock_rows;                // [n * S] or NULL
     const uint32_t *order;                     // [n * S] or NULL: actor-major order (clock_rows only)
+    const uint32_t *have_rows;                 // [n * S] or NULL: the clock selector's lower bound (clock_rows only)
     uint32_t *cnt, *aux, *off;                 // [4n], [2n], [4n]
     unsigned long long *part;                  // [hm_past_scan_chunks(n) * HM_PAST_PART]
     hm_past_summary *sum;
@@ -71,3 +83,31 @@ hipError_t hm_launch_past_fill(const PastArgs &a, hipStream_t s);
 // the scan alone over cnt / aux already written (n, cnt, aux, off, part and sum are read): the op-diff
 // kernels reserve their requests' row and survivor blocks with it (op_diff_kernels.hip)
 hipError_t hm_launch_past_scan(const PastArgs &a, hipStream_t s);
+
+// The rename pass over a filled batch (cnt / off: the count pass's; one wave per request): the rows of
+// request i enter another document's id spaces through the caller's maps.
+//   change rows  actor through the rank row, content_id through the content map
+//   dep rows     actor through the rank row
+//   op rows      obj through the object map; reg (unless HM_NONE: make*) and parent (unless HM_HEAD)
+//                through the register map; key (set / del / link / inc only: the others carry none)
+//                through the string map; value through the string map (HM_V_STR) or the object map
+//                (HM_V_OBJ); everything else, elem included, stays
+//   doc row      n_actors / n_regs / n_objs = totals[4i ..], flags |= totals[4i + 3]
+// rank is an [n * S] table; the other maps are CSR slices per request (off [n + 1]), the string and the
+// content map optional (NULL: identity).  An id at or beyond its slice, an entry of HM_NONE, a source
+// rank >= S, or an image at or beyond the stated totals sets HM_PAST_BAD_MAP in *bad (nothing is read
+// through such an id; the request's rows are then garbage and the caller drops the batch).
+struct RenameArgs {
+    uint32_t n, S;
+    const uint32_t *cnt, *off;                 // [4n] each
+    hm_doc_row *docs;
+    hm_change_row *changes;
+    hm_dep_row *deps;
+    hm_op_row *ops;
+    const uint32_t *totals;                    // [4n] n_actors, n_regs, n_objs, flags after the merge
+    const uint32_t *rank;                      // [n * S] source rank -> destination rank
+    const uint32_t *obj_off, *obj_map, *reg_off, *reg_map;
+    const uint32_t *str_off, *str_map, *cid_off, *cid_map;   // (maps may be NULL: identity)
+    uint32_t *bad;
+};
+hipError_t hm_launch_past_rename(const RenameArgs &a, hipStream_t s);

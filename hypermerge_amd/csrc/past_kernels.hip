@@ -22,8 +22,12 @@
 //             change by binary search over the slots' op offsets and moves the 32-byte row as two
 //             16-byte words, so the stores are contiguous and the loads contiguous within a change
 //
-// Nothing inside a row is remapped: register, object and rank ids are the document's own.  The
-// request's document comes from doc_source.h; the bitmap tile and the wave scans are wave.h's.
+// Nothing inside a row is remapped by these passes: register, object and rank ids are the document's
+// own.  The request's document comes from doc_source.h; the bitmap tile and the wave scans are wave.h's.
+//
+//  past_rename_kernel a pass of its own over the gathered tables (a merge into a document that already
+//                     holds changes: the rows enter another document's id spaces): one wavefront per
+//                     request strides its change, dep and op rows, every id through the caller's maps
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/hypermerge_amd.h"
@@ -41,6 +45,7 @@ struct Src : DocRef {
     uint32_t npre;                             // prefix selector (clock selector: unused)
     const uint32_t *clk;                       // clock selector's row, or NULL
     const uint32_t *ord;                       // actor-major order row, or NULL (history order)
+    const uint32_t *hav;                       // clock selector's lower bound row (source ranks), or NULL
 };
 
 __device__ __forceinline__ Src source_of(const PastArgs &A, unsigned long long q) {
@@ -49,11 +54,13 @@ __device__ __forceinline__ Src source_of(const PastArgs &A, unsigned long long q
     s.npre = A.hist_len ? A.hist_len[q] : 0u;
     s.clk = A.clock_rows ? A.clock_rows + q * A.src.S : nullptr;
     s.ord = A.order ? A.order + q * A.src.S : nullptr;
+    s.hav = A.have_rows && s.clk ? A.have_rows + q * A.src.S : nullptr;
     return s;
 }
 
 // is log row i selected?  p = its output position: its history position, or with ab (the request's
-// per-rank bases of the actor-major order, in LDS) ab[actor] + seq - 1
+// per-rank bases of the actor-major order, in LDS) ab[actor] + seq - 1, or with a lower bound row
+// ab[actor] + seq - have[actor] - 1
 __device__ __forceinline__ bool selected(const Src &s, const PastArgs &A, uint32_t i, uint32_t &p, const uint32_t *ab = nullptr) {
     const int32_t hp = A.src.hist[s.c_off + i];
     if (hp < 0 || (uint32_t)hp >= s.n_c) return false;
@@ -62,9 +69,11 @@ __device__ __forceinline__ bool selected(const Src &s, const PastArgs &A, uint32
     const hm_change_row *c = A.src.changes + s.c_off + i;
     const uint32_t a = c->actor, q = c->seq;
     if (a >= A.src.S || q > s.clk[a]) return false;
+    const uint32_t lo = s.hav ? s.hav[a] : 0u;
+    if (q <= lo && s.hav) return false;                      // (the destination was handed it already)
     if (!ab) return true;
     if (ab[a] == HM_NONE || !q) return false;                // (an unlisted rank: the count pass refused the row)
-    p = ab[a] + q - 1u;
+    p = ab[a] + q - lo - 1u;
     return p < s.n_c;
 }
 
@@ -257,7 +266,8 @@ __global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
         const uint32_t *ab = nullptr;
         if (s.ord) {
             // the ranks' bases: the running sum, over the order row, of min(clock row, opSet.clock) —
-            // an actor's applied changes are exactly its seqs 1 .. opSet.clock[actor]
+            // an actor's applied changes are exactly its seqs 1 .. opSet.clock[actor] — less the lower
+            // bound row where there is one
             __syncthreads();                                   // (the previous request's reads of L.ab)
             for (uint32_t a = lane; a < HM_MAX_STRIDE; a += 64u) L.ab[a] = HM_NONE;
             __syncthreads();
@@ -269,7 +279,8 @@ __global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
                 const uint32_t r = j < D.S ? s.ord[j] : HM_NONE;
                 const unsigned long long ends = __ballot(r == HM_NONE || r >= D.S);
                 const bool live = ends == 0ull || lane < (uint32_t)__ffsll((long long)ends) - 1u;
-                const uint32_t k = live ? min(s.clk[r], have[r]) : 0u;
+                uint32_t k = live ? min(s.clk[r], have[r]) : 0u;
+                if (s.hav && live) k -= min(k, s.hav[r]);
                 const uint32_t incl = wave_incl_scan(k, lane);
                 if (live) L.ab[r] = run + incl - k;
                 run += __shfl(incl, 63);
@@ -353,7 +364,78 @@ __global__ __launch_bounds__(PWG) void past_fill_kernel(PastArgs A) {
     }
 }
 
+// id through request q's slice of a CSR map (map == NULL: identity); an id at or beyond the slice, or
+// an entry of HM_NONE, is not read through and marks the request bad
+__device__ __forceinline__ uint32_t mapped(const uint32_t *off, const uint32_t *map, unsigned long long q, uint32_t id, bool &bad) {
+    if (!map) return id;
+    const uint32_t lo = off[q], hi = off[q + 1];
+    if (hi < lo || id >= hi - lo) { bad = true; return id; }
+    const uint32_t v = map[lo + id];
+    bad |= v == HM_NONE;
+    return v;
+}
+
+#define PRWG 256
+__global__ __launch_bounds__(PRWG) void past_rename_kernel(RenameArgs R) {
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const unsigned long long step = (unsigned long long)gridDim.x * (PRWG / 64);
+    for (unsigned long long q = (unsigned long long)blockIdx.x * (PRWG / 64) + wv; q < R.n; q += step) {
+        const uint4 cn = *(const uint4 *)(R.cnt + 4 * q), of = *(const uint4 *)(R.off + 4 * q);
+        const uint4 tot = *(const uint4 *)(R.totals + 4 * q);       // n_actors, n_regs, n_objs, flags
+        const uint32_t *rk = R.rank + q * R.S;
+        bool bad = false;
+        auto ranked = [&](uint32_t a) -> uint32_t {
+            if (a >= R.S) { bad = true; return a; }
+            const uint32_t v = rk[a];
+            bad |= v >= tot.x;                                 // (HM_NONE too)
+            return v;
+        };
+        auto obj_of = [&](uint32_t o) -> uint32_t {
+            const uint32_t v = mapped(R.obj_off, R.obj_map, q, o, bad);
+            bad |= v >= tot.z;
+            return v;
+        };
+        auto reg_of = [&](uint32_t r) -> uint32_t {
+            const uint32_t v = mapped(R.reg_off, R.reg_map, q, r, bad);
+            bad |= v >= tot.y;
+            return v;
+        };
+        for (uint32_t i = lane; i < cn.x; i += 64u) {
+            hm_change_row *c = R.changes + of.x + i;
+            c->actor = (uint16_t)ranked(c->actor);
+            c->content_id = mapped(R.cid_off, R.cid_map, q, c->content_id, bad);
+        }
+        for (uint32_t i = lane; i < cn.y; i += 64u) {
+            hm_dep_row *d = R.deps + of.y + i;
+            d->actor = (uint16_t)ranked(d->actor);
+        }
+        for (uint32_t i = lane; i < cn.z; i += 64u) {
+            hm_op_row *p = R.ops + of.z + i;
+            hm_op_row o = *p;
+            o.obj = obj_of(o.obj);
+            if (o.reg != HM_NONE) o.reg = reg_of(o.reg);       // (make*: no register)
+            if (o.parent != HM_HEAD) o.parent = reg_of(o.parent);
+            if (o.action >= HM_SET) o.key = mapped(R.str_off, R.str_map, q, o.key, bad);   // (the keyed actions)
+            if (o.vtag == HM_V_STR) o.value = mapped(R.str_off, R.str_map, q, (uint32_t)o.value, bad);
+            else if (o.vtag == HM_V_OBJ) o.value = obj_of((uint32_t)o.value);
+            *p = o;
+        }
+        if (lane == 0) {
+            hm_doc_row *r = R.docs + q;
+            r->n_actors = (uint16_t)tot.x; r->n_regs = tot.y; r->n_objs = tot.z; r->flags |= (uint16_t)tot.w;
+        }
+        if (__ballot(bad) != 0ull && lane == 0) atomicOr(R.bad, HM_PAST_BAD_MAP);
+    }
+}
+
 }  // namespace hmp
+
+hipError_t hm_launch_past_rename(const RenameArgs &a, hipStream_t s) {
+    if (!a.n) return hipSuccess;
+    const unsigned long long wgs = ((unsigned long long)a.n + PRWG / 64 - 1) / (PRWG / 64);
+    hipLaunchKernelGGL(hmp::past_rename_kernel, dim3((uint32_t)(wgs < 65535ull ? wgs : 65535ull)), dim3(PRWG), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t hm_launch_past_count(const PastArgs &a, hipStream_t s) {
     hipError_t r = hipMemsetAsync(a.sum, 0, sizeof(hm_past_summary), s);

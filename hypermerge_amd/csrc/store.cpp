@@ -1253,10 +1253,13 @@ static_assert(sizeof(PlanStats) >= sizeof(hm_past_summary), "the summary is read
 // The count pass of n staged requests: handles and the selector go to the stage buffer, the counts,
 // offsets and summary stay there (P.cnt / P.off / P.sum); *sum = the summary, read back.
 // order: the actor-major order rows (staged too); dst: a fork's destination handles, staged
-// (*dst_dev) and checked on the device before the one read-back.
+// (*dst_dev) and checked on the device before the one read-back.  have: the clock selector's lower
+// bound rows (staged); merge_totals: the destinations are a merge's, checked against their stated
+// totals ([4n], staged, *tot_dev) instead of for emptiness.
 static int past_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, const uint32_t *hist_len,
                       const uint32_t *clock_rows, PastArgs &P, hm_past_summary *sum, const uint32_t *order = nullptr,
-                      const uint32_t *dst = nullptr, const uint32_t **dst_dev = nullptr) {
+                      const uint32_t *dst = nullptr, const uint32_t **dst_dev = nullptr, const uint32_t *have = nullptr,
+                      const uint32_t *merge_totals = nullptr, const uint32_t **tot_dev = nullptr) {
     const uint32_t S = s->S;
     hipStream_t st = hm_engine_stream(s->e);
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -1264,7 +1267,8 @@ static int past_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, cons
     const size_t o_sum = 0, o_h = 256, o_sel = o_h + al(4 * (size_t)n), o_cnt = o_sel + al(sel_b), o_off = o_cnt + al(16 * (size_t)n),
                  o_aux = o_off + al(16 * (size_t)n), o_part = o_aux + al(8 * (size_t)n),
                  o_ord = o_part + al((size_t)hm_past_scan_chunks(n) * HM_PAST_PART * 8),
-                 o_dst = o_ord + (order ? al(4 * (size_t)n * S) : 0), total = o_dst + (dst ? al(4 * (size_t)n) : 0);
+                 o_dst = o_ord + (order ? al(4 * (size_t)n * S) : 0), o_have = o_dst + (dst ? al(4 * (size_t)n) : 0),
+                 o_tot = o_have + (have ? al(4 * (size_t)n * S) : 0), total = o_tot + (merge_totals ? al(16 * (size_t)n) : 0);
     int rc = ensure_stage(s, total);
     if (rc) return rc;
     uint8_t *sp = s->stage.p;
@@ -1272,24 +1276,35 @@ static int past_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, cons
     SCHK(s, hipMemcpyAsync(sp + o_sel, hist_len ? hist_len : clock_rows, sel_b, hipMemcpyHostToDevice, st));
     if (order) SCHK(s, hipMemcpyAsync(sp + o_ord, order, 4 * (size_t)n * S, hipMemcpyHostToDevice, st));
     if (dst) SCHK(s, hipMemcpyAsync(sp + o_dst, dst, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    if (have) SCHK(s, hipMemcpyAsync(sp + o_have, have, 4 * (size_t)n * S, hipMemcpyHostToDevice, st));
+    if (merge_totals) SCHK(s, hipMemcpyAsync(sp + o_tot, merge_totals, 16 * (size_t)n, hipMemcpyHostToDevice, st));
     P = PastArgs{};
     P.n = n; P.src = store_source(s); P.src.handles = (const uint32_t *)(sp + o_h);
     if (hist_len) P.hist_len = (const uint32_t *)(sp + o_sel); else P.clock_rows = (const uint32_t *)(sp + o_sel);
     if (order) P.order = (const uint32_t *)(sp + o_ord);
+    if (have) P.have_rows = (const uint32_t *)(sp + o_have);
     P.cnt = (uint32_t *)(sp + o_cnt); P.off = (uint32_t *)(sp + o_off); P.aux = (uint32_t *)(sp + o_aux);
     P.part = (unsigned long long *)(sp + o_part);
     P.sum = (hm_past_summary *)(sp + o_sum);
     SCHK(s, hm_launch_past_count(P, st));
     if (dst) {
         const uint32_t stamp_src = ++s->stamp ? s->stamp : ++s->stamp, stamp_dst = ++s->stamp ? s->stamp : ++s->stamp;
-        SCHK(s, hm_launch_fork_check(P.src.handles, (const uint32_t *)(sp + o_dst), n, s->n_handles, s->dm, s->seen, stamp_src,
-                                     stamp_dst, &P.sum->bad, st));
+        if (merge_totals) {
+            SCHK(s, hm_launch_merge_check(P.src.handles, (const uint32_t *)(sp + o_dst), (const uint32_t *)(sp + o_tot), n,
+                                          s->n_handles, S, s->dm, s->seen, stamp_src, stamp_dst, &P.sum->bad, st));
+            *tot_dev = (const uint32_t *)(sp + o_tot);
+        } else {
+            SCHK(s, hm_launch_fork_check(P.src.handles, (const uint32_t *)(sp + o_dst), n, s->n_handles, s->dm, s->seen, stamp_src,
+                                         stamp_dst, &P.sum->bad, st));
+        }
         *dst_dev = (const uint32_t *)(sp + o_dst);
     }
     SCHK(s, hipMemcpyAsync(s->h_st, P.sum, sizeof(hm_past_summary), hipMemcpyDeviceToHost, st));
     SCHK(s, hipStreamSynchronize(st));
     memcpy(sum, s->h_st, sizeof *sum);
     if (sum->bad & HM_PAST_BAD_HANDLE) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad handle");
+    if ((sum->bad & HM_FORK_BAD_DST) && merge_totals)
+        return hm_engine_fail(s->e, HM_ERR_INVALID, "a merge's destination is outside the store, repeated, a source, or its stated totals are below its current ones or above a_stride");
     if (sum->bad & HM_FORK_BAD_DST)
         return hm_engine_fail(s->e, HM_ERR_INVALID, "a fork's destination is outside the store, repeated, a source or not empty");
     if (sum->bad & HM_PAST_BAD_ORDER)
@@ -1390,6 +1405,98 @@ int hm_store_fork_submit(hm_store *s, uint32_t n, const uint32_t *src_handles, c
     }
 }
 
+// Merge into documents that hold changes: count, scan and the destination check, fill into the
+// store's buffer, the rename pass over the filled tables (the maps staged behind them), then the
+// device-table submit to the destinations with their remap rows.  Two read-backs: the totals with
+// the count's verdicts, the rename's verdict.
+int hm_store_merge_from_submit(hm_store *s, uint32_t n, const uint32_t *src_handles, const uint32_t *have_rows,
+                               const uint32_t *clock_rows, const uint32_t *actor_order, const uint32_t *dst_handles,
+                               const hm_merge_maps *maps, const uint8_t *dst_actor_remap, uint64_t *out_batch_id) {
+    if (!s || !n || !src_handles || !dst_handles || !maps) return HM_ERR_INVALID;
+    if (!clock_rows) return hm_engine_fail(s->e, HM_ERR_INVALID, "a merge selects by a clock (clock_rows)");
+    if (!maps->totals || !maps->rank || !maps->obj_off || !maps->reg_off || (maps->str_map && !maps->str_off) ||
+        (maps->content_map && !maps->content_off))
+        return hm_engine_fail(s->e, HM_ERR_INVALID, "hm_merge_maps: totals, rank and the object and register maps are required");
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "a batch is already in flight (call hm_batch_wait)");
+    try {
+        const uint32_t S = s->S;
+        // the CSR offsets start at 0 and do not decrease; a map with entries has its table
+        const uint32_t *offs[4] = {maps->obj_off, maps->reg_off, maps->str_map ? maps->str_off : nullptr,
+                                   maps->content_map ? maps->content_off : nullptr};
+        const uint32_t *tabs[4] = {maps->obj_map, maps->reg_map, maps->str_map, maps->content_map};
+        for (int k = 0; k < 4; k++) {
+            if (!offs[k]) continue;
+            if (offs[k][0]) return hm_engine_fail(s->e, HM_ERR_INVALID, "hm_merge_maps: an offset table must start at 0");
+            for (uint32_t i = 0; i < n; i++)
+                if (offs[k][i + 1] < offs[k][i]) return hm_engine_fail(s->e, HM_ERR_INVALID, "hm_merge_maps: an offset table must not decrease");
+            if (offs[k][n] && !tabs[k]) return hm_engine_fail(s->e, HM_ERR_INVALID, "hm_merge_maps: a map table is missing");
+        }
+        SCHK(s, hipSetDevice(hm_engine_device(s->e)));
+        hipStream_t st = hm_engine_stream(s->e);
+        PastArgs P;
+        hm_past_summary sum;
+        const uint32_t *dst_staged = nullptr, *tot_staged = nullptr;
+        int rc = past_count(s, n, src_handles, nullptr, clock_rows, P, &sum, actor_order, dst_handles, &dst_staged, have_rows,
+                            maps->totals, &tot_staged);
+        if (rc) return rc;
+        const uint64_t tc = sum.totals[0], td = sum.totals[1], to = sum.totals[2], tr = sum.totals[3];
+        if (std::max(std::max(tc, td), std::max(to, tr)) > 0xFFFFFFFFull)
+            return hm_engine_fail(s->e, HM_ERR_NOMEM, "a call's rows stay below 2^32");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        // [docs][changes][deps][ops][change_log][op_log][destination handles][remap rows][rank rows]
+        // [obj_off][obj_map][reg_off][reg_map][str_off][str_map][content_off][content_map]
+        const size_t offb = ((size_t)n + 1) * 4;
+        const size_t sz[17] = {n * sizeof(hm_doc_row), tc * sizeof(hm_change_row), td * sizeof(hm_dep_row), to * sizeof(hm_op_row),
+                               tc * 4, to * 4, (size_t)n * 4, dst_actor_remap ? (size_t)n * S : 0, (size_t)n * S * 4,
+                               offb, (size_t)offs[0][n] * 4, offb, (size_t)offs[1][n] * 4,
+                               offs[2] ? offb : 0, offs[2] ? (size_t)offs[2][n] * 4 : 0,
+                               offs[3] ? offb : 0, offs[3] ? (size_t)offs[3][n] * 4 : 0};
+        size_t o[17], total = 0;
+        for (int i = 0; i < 17; i++) { o[i] = total; total += al(sz[i] + 1); }
+        if ((rc = ensure_buf(s, s->past, total))) return rc;
+        uint8_t *bp = s->past.p;
+        const void *host[17] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, dst_actor_remap, maps->rank,
+                                offs[0], tabs[0], offs[1], tabs[1], offs[2], tabs[2], offs[3], tabs[3]};
+        for (int i = 7; i < 17; i++)
+            if (host[i] && sz[i]) SCHK(s, hipMemcpyAsync(bp + o[i], host[i], sz[i], hipMemcpyHostToDevice, st));
+        P.cap[0] = (uint32_t)tc; P.cap[1] = (uint32_t)td; P.cap[2] = (uint32_t)to; P.cap[3] = (uint32_t)tr;
+        P.out_docs = (hm_doc_row *)(bp + o[0]); P.out_changes = (hm_change_row *)(bp + o[1]); P.out_deps = (hm_dep_row *)(bp + o[2]);
+        P.out_ops = (hm_op_row *)(bp + o[3]); P.out_change_log = (uint32_t *)(bp + o[4]); P.out_op_log = (uint32_t *)(bp + o[5]);
+        SCHK(s, hm_launch_past_fill(P, st));
+        uint32_t *dst_dev = (uint32_t *)(bp + o[6]);
+        SCHK(s, hipMemcpyAsync(dst_dev, dst_staged, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        RenameArgs R = {};
+        R.n = n; R.S = S; R.cnt = P.cnt; R.off = P.off;
+        R.docs = P.out_docs; R.changes = P.out_changes; R.deps = P.out_deps; R.ops = P.out_ops;
+        R.totals = tot_staged; R.rank = (const uint32_t *)(bp + o[8]);
+        R.obj_off = (const uint32_t *)(bp + o[9]); R.obj_map = (const uint32_t *)(bp + o[10]);
+        R.reg_off = (const uint32_t *)(bp + o[11]); R.reg_map = (const uint32_t *)(bp + o[12]);
+        if (offs[2]) { R.str_off = (const uint32_t *)(bp + o[13]); R.str_map = (const uint32_t *)(bp + o[14]); }
+        if (offs[3]) { R.cid_off = (const uint32_t *)(bp + o[15]); R.cid_map = (const uint32_t *)(bp + o[16]); }
+        R.bad = &P.sum->bad;
+        SCHK(s, hm_launch_past_rename(R, st));
+        // the rename's verdict: the second read-back (the stage buffer is free for the submit afterwards)
+        SCHK(s, hipMemcpyAsync(s->h_st, P.sum, sizeof(hm_past_summary), hipMemcpyDeviceToHost, st));
+        SCHK(s, hipStreamSynchronize(st));
+        memcpy(&sum, s->h_st, sizeof sum);
+        if (sum.bad & HM_PAST_BAD_MAP)
+            return hm_engine_fail(s->e, HM_ERR_INVALID, "a merge map: an id beyond its slice, an entry of HM_NONE, or an image beyond the stated totals");
+        hm_batch b = {};
+        b.a_stride = S; b.n_docs = n;
+        b.n_changes = (uint32_t)tc; b.n_deps = (uint32_t)td; b.n_ops = (uint32_t)to;
+        b.docs = P.out_docs; b.changes = P.out_changes; b.deps = P.out_deps; b.ops = P.out_ops;
+        uint64_t id = 0;
+        if ((rc = hm_batch_submit_device(s, &b, dst_dev, dst_actor_remap ? bp + o[7] : nullptr, &id))) return rc;
+        s->fork_id = id; s->fork_n = n;
+        s->fork_rows[0] = (size_t)tc; s->fork_rows[1] = (size_t)td; s->fork_rows[2] = (size_t)to;
+        for (int i = 0; i < 6; i++) s->fork_off[i] = o[i];
+        if (out_batch_id) *out_batch_id = id;
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_merge_from_submit");
+    }
+}
+
 }  // extern "C"
 
 // (engine_internal.h) the tables a fork batch in flight gathered, for a host that mirrors the forks'
@@ -1416,6 +1523,24 @@ int hm_store_fork_rows(hm_store *s, uint64_t batch_id, std::vector<hm_doc_row> &
         return HM_OK;
     } catch (...) {
         return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_fork_rows");
+    }
+}
+
+// (engine_internal.h) the DocBackend.clock rows of n documents, out[i * S ..], with one synchronise
+int hm_store_back_clocks(hm_store *s, uint32_t n, const uint32_t *doc_handles, uint32_t *out) {
+    if (!s || (n && (!doc_handles || !out))) return HM_ERR_INVALID;
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        const uint32_t S = s->S;
+        hipStream_t st = hm_engine_stream(s->e);
+        for (uint32_t i = 0; i < n; i++) {
+            if (doc_handles[i] >= s->n_handles) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad handle");
+            SCHK(s, hipMemcpyAsync(out + (size_t)i * S, s->back_clock + (size_t)doc_handles[i] * S, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+        }
+        SCHK(s, hipStreamSynchronize(st));
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_back_clocks");
     }
 }
 

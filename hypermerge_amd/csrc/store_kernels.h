@@ -224,6 +224,11 @@ hipError_t hm_launch_reset_docs(const uint32_t *handles, uint32_t n, DevDoc *dm,
 #define HM_FORK_BAD_DST 8u
 hipError_t hm_launch_fork_check(const uint32_t *src, const uint32_t *dst, uint32_t n, uint32_t n_handles, const DevDoc *dm,
                                 uint32_t *seen, uint32_t stamp_src, uint32_t stamp_dst, uint32_t *bad, hipStream_t s);
+// a merge's destinations (hm_store_merge_from_submit): inside the store, named once, no source, stated
+// totals (totals[4i ..] = n_actors, n_regs, n_objs, flags) covering the current ones, n_actors <= S
+hipError_t hm_launch_merge_check(const uint32_t *src, const uint32_t *dst, const uint32_t *totals, uint32_t n, uint32_t n_handles,
+                                 uint32_t S, const DevDoc *dm, uint32_t *seen, uint32_t stamp_src, uint32_t stamp_dst, uint32_t *bad,
+                                 hipStream_t s);
 hipError_t hm_launch_fork_min_clock(const uint32_t *src, const uint32_t *dst, uint32_t n, uint32_t S, DevDoc *dm,
                                     uint32_t *minc, uint32_t on, hipStream_t s);
 // chosen registers of resident documents by (handle, register): validated on the device

@@ -691,6 +691,25 @@ __global__ void fork_check_kernel(const uint32_t *src, const uint32_t *dst, uint
     if (!ok) atomicOr(bad, HM_FORK_BAD_DST);
 }
 
+// hm_store_merge_from_submit's destination check (after fork_mark_kernel over the sources): destination
+// i lies inside the store, is named once, is no source of the call, and its stated totals after the
+// merge (totals[4i ..] = n_actors, n_regs, n_objs, flags) cover its current ones with n_actors <= S.
+// It may hold anything, queued changes included.
+__global__ void merge_check_kernel(const uint32_t *dst, const uint32_t *totals, uint32_t n, uint32_t n_handles, uint32_t S,
+                                   const DevDoc *dm, uint32_t *seen, uint32_t stamp_src, uint32_t stamp_dst, uint32_t *bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t h = dst[i];
+    bool ok = h < n_handles;
+    if (ok) {
+        const uint32_t was = atomicExch(&seen[h], stamp_dst);
+        const DevDoc m = dm[h];
+        const uint32_t na = totals[4 * (size_t)i], nr = totals[4 * (size_t)i + 1], nob = totals[4 * (size_t)i + 2];
+        ok = was != stamp_dst && was != stamp_src && na <= S && na >= m.n_actors && nr >= m.n_r && nob >= m.n_objs;
+    }
+    if (!ok) atomicOr(bad, HM_FORK_BAD_DST);
+}
+
 // the forks' minimumClock rows: the parent's row and its HM_DDOC_MINC bit (on), or none
 __global__ void fork_min_clock_kernel(const uint32_t *src, const uint32_t *dst, uint32_t n, uint32_t S, DevDoc *dm,
                                       uint32_t *minc, uint32_t on) {
@@ -789,6 +808,17 @@ hipError_t hm_launch_fork_check(const uint32_t *src, const uint32_t *dst, uint32
     hipError_t r = hipGetLastError();
     if (r != hipSuccess) return r;
     hipLaunchKernelGGL(hms::fork_check_kernel, dim3((n + 255) / 256), dim3(256), 0, s, src, dst, n, n_handles, dm, seen,
+                       stamp_src, stamp_dst, bad);
+    return hipGetLastError();
+}
+hipError_t hm_launch_merge_check(const uint32_t *src, const uint32_t *dst, const uint32_t *totals, uint32_t n, uint32_t n_handles,
+                                 uint32_t S, const DevDoc *dm, uint32_t *seen, uint32_t stamp_src, uint32_t stamp_dst, uint32_t *bad,
+                                 hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(hms::fork_mark_kernel, dim3((n + 255) / 256), dim3(256), 0, s, src, n, n_handles, seen, stamp_src);
+    hipError_t r = hipGetLastError();
+    if (r != hipSuccess) return r;
+    hipLaunchKernelGGL(hms::merge_check_kernel, dim3((n + 255) / 256), dim3(256), 0, s, dst, totals, n, n_handles, S, dm, seen,
                        stamp_src, stamp_dst, bad);
     return hipGetLastError();
 }

@@ -63,7 +63,8 @@ class DocSet:
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.hm_docset_destroy(self._h)
+            if getattr(self.engine, "_h", None):               # (its stores live on the engine's stream)
+                self._L.hm_docset_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -318,6 +319,39 @@ class DocSet:
         new, t = self._fork(docs, clocks, history)
         s, res = _text(self._L, t, raw=True)
         return new, res, s
+
+    def _merge_from(self, dst_docs, src_docs, clocks):
+        dst, src = np.ascontiguousarray(dst_docs, np.uint32), np.ascontiguousarray(src_docs, np.uint32)
+        if len(dst) != len(src) or len(clocks) != len(dst):
+            raise ValueError("merge_from takes one source and one clock per destination")
+        eoff, data, aoff, sq = self._clock_entries(len(dst), clocks)
+        t = ctypes.c_void_p()
+        self.engine._check(self._L.hm_docset_merge_from(self._h, len(dst), dst.ctypes.data if len(dst) else None,
+                                                        src.ctypes.data if len(src) else None, eoff.ctypes.data, data.ctypes.data,
+                                                        aoff.ctypes.data, sq.ctypes.data, ctypes.byref(t)), "hm_docset_merge_from")
+        return t
+
+    def merge_from(self, dst_docs: Sequence[int], src_docs: Sequence[int],
+                   clocks: Sequence[Dict[str, float]]) -> Tuple[np.ndarray, Dict[str, Any]]:
+        """Repo.merge(target, source) into documents that may already hold changes, many per call
+        (hm_docset_merge_from): dst_docs[i] (each once, none a source of the call) is handed
+        src_docs[i]'s applied changes above what it was handed before (its DocBackend.clock) up to
+        clocks[i] ({actorId: seq}), actor after actor in the clock's key order.  Returns what `apply`
+        returns for a round handing the destinations those changes: the result rows and {"p", "b", "c"}
+        (one combined patch per destination)."""
+        s, res = _text(self._L, self._merge_from(dst_docs, src_docs, clocks))
+        return res, json.loads(s)
+
+    def merge_from_raw(self, dst_docs, src_docs, clocks) -> Tuple[np.ndarray, bytes]:
+        """`merge_from` with the call's text as it came (the HMP1 words of a binary docset)."""
+        s, res = _text(self._L, self._merge_from(dst_docs, src_docs, clocks), raw=True)
+        return res, s
+
+    def merge_stats(self) -> Dict[str, int]:
+        """hm_docset_merge_stats: merge requests that moved their rows on the device / through the host."""
+        out = np.zeros(2, np.uint64)
+        self.engine._check(self._L.hm_docset_merge_stats(self._h, out.ctypes.data), "hm_docset_merge_stats")
+        return {"device": int(out[0]), "host": int(out[1])}
 
     def handles(self, a_stride: int) -> Dict[str, int]:
         """hm_docset_handles: handles opened in the a_stride store and released ones awaiting reuse."""

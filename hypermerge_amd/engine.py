@@ -46,7 +46,8 @@ EXPORTS = ("hm_abi_version", "hm_status_message", "hm_engine_create", "hm_engine
            "hm_op_diffs_host_ex", "hm_docset_materialize_patch_ex", "hm_docset_diff_stats",
            "hm_store_fields", "hm_fields_device", "hm_fields_host", "hm_docset_fields",
            "hm_store_op_diff_sizes_at", "hm_store_op_diffs_at", "hm_op_diffs_at_work_bytes", "hm_op_diffs_at_device",
-           "hm_op_diffs_at_host", "hm_docset_materialize_patch_at", "hm_store_fork_submit", "hm_docset_fork")
+           "hm_op_diffs_at_host", "hm_docset_materialize_patch_at", "hm_store_fork_submit", "hm_docset_fork",
+           "hm_store_merge_from_submit", "hm_docset_merge_from", "hm_docset_merge_stats")
 
 _lib = None
 
@@ -135,6 +136,8 @@ def lib():
             "hm_store_materialize": [vp, u32, vp, vp, vp, vp, vp],
             "hm_store_fork_submit": [vp, u32, vp, vp, vp, vp, vp, u32, vp],
             "hm_docset_fork": [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp],
+            "hm_store_merge_from_submit": [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp],
+            "hm_docset_merge_from": [vp, u32, vp, vp, vp, vp, vp, vp, vp], "hm_docset_merge_stats": [vp, vp],
             "hm_materialize_work_bytes": [u32],
             "hm_docset_materialize": [vp, u32, vp, vp, vp, vp, vp, vp, vp],
             "hm_materialize_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, vp],

@@ -675,8 +675,9 @@ class GpuEngine {
     return this.forkNow(reqs)
   }
 
-  // the changes a fork is handed, as the entries of its parent's log, in hand-over order
-  handedOver(parent, req) {
+  // the changes a fork is handed, as the entries of its parent's log, in hand-over order; have
+  // ({actorId: seq}, a merge into a live document): only each actor's changes above have[actor]
+  handedOver(parent, req, have) {
     if (req.clock === undefined || req.clock === null) {
       const n = Math.min(Math.max(Math.floor(Number(req.history) || 0), 0), 0xffffffff)
       const b = addon.docsetHistoryPrefix(parent.ds, parent.id, n)
@@ -699,8 +700,58 @@ class GpuEngine {
       if (seen.has(a)) continue
       seen.add(a)
       const top = Math.min(Math.floor(Number(clock[a]) || 0), parent.clock[a] || 0)
-      for (let q = 1; q <= top; q++) out.push(parent.log[at.get(a).get(q)])
+      for (let q = ((have && have[a]) || 0) + 1; q <= top; q++) out.push(parent.log[at.get(a).get(q)])
     }
+    return out
+  }
+
+  // Repo.merge(target, source) into documents that may already hold changes, many at once: reqs[i] =
+  // {into: state | docId, from: state | docId, clock: {actorId: seq}} -> per request {patch, roundClock,
+  // history, changes} once the destination has been handed the source's changes above what it was handed
+  // before (its DocBackend.clock) up to the clock, actor after actor in the clock's key order.  Source
+  // and destination in one docset: the rows move on the device (hm_docset_merge_from) and the
+  // destination's state advances here.  On different shards: {entries}, the selected entries of the
+  // source's host log, for the caller to hand to applyRemoteChanges.  A destination whose merge throws
+  // gets {error} (the reference's Error) and stays as it was.  In 'async' mode after idle().
+  mergeFrom(reqs) {
+    if (this.mode === 'async') return this.idle().then(() => this.mergeFromNow(reqs))
+    return this.mergeFromNow(reqs)
+  }
+
+  mergeFromNow(reqs) {
+    if (this.flushing) throw new Error('GpuEngine.mergeFrom while a round is in flight')
+    const pick = (x) => (x instanceof GpuBackendState ? x : this.stateOf(x))
+    const dst = reqs.map((r) => pick(r.into)), src = reqs.map((r) => pick(r.from))
+    const handed = reqs.map((r, i) => this.handedOver(src[i], { clock: r.clock || {} }, dst[i].backClock))
+    const out = new Array(reqs.length)
+    reqs.forEach((r, i) => { if (dst[i].shard !== src[i].shard) out[i] = { entries: handed[i], changes: handed[i].length } })
+    this.docsets.forEach((ds, k) => {
+      const mine = []
+      reqs.forEach((r, i) => { if (!out[i] && dst[i].shard === k) mine.push(i) })
+      if (!mine.length) return
+      const r = addon.docsetMergeFrom(ds, Uint32Array.from(mine.map((i) => dst[i].id)), Uint32Array.from(mine.map((i) => src[i].id)),
+        ...clockEntries(mine.map((i) => reqs[i].clock || {})))
+      this.submits++
+      const res = new Uint32Array(r.results.buffer, r.results.byteOffset, r.results.length / 4)
+      const j = decodeRound(r.data, mine.length)
+      const ok = []
+      mine.forEach((i, x) => {
+        const status = res[RESULT_U32 * x] | 0
+        if (status !== 0) {
+          out[i] = { error: this.errorFor(dst[i], handed[i], status, res[RESULT_U32 * x + 1], res[RESULT_U32 * x + 2]) }
+          return
+        }
+        for (const c of handed[i]) dst[i].log.push(c)
+        dst[i].histLen = res[RESULT_U32 * x + 3]
+        dst[i].nQueued = res[RESULT_U32 * x + 4]
+        if (j.advance(x, dst[i])) ok.push([i, x])
+        else out[i] = { patch: null, roundClock: {}, history: dst[i].histLen, changes: handed[i].length }
+      })
+      for (const [i, x] of ok) {
+        const m = j.message(x, dst[i])
+        out[i] = { patch: m.patch, roundClock: m.c, history: dst[i].histLen, changes: handed[i].length }
+      }
+    })
     return out
   }
 
@@ -1363,11 +1414,25 @@ class DocBackend {
   // Repo.merge(this, parent) into a document that is still empty (Repo.fork = create() + merge(fork,
   // parent), src/RepoFrontend.ts:95-99): the RemotePatchMsg that applyRemoteChanges of the handed-over
   // changes would give, with the rows copied on the device (GpuEngine.fork).  The document's state
-  // object is replaced by the fork's.  Throws when the document already holds changes: merging into
-  // those needs the two documents' ids remapped, which the engine does not do.
+  // object is replaced by the fork's.
+  // Into a document that already holds changes (RepoBackend.merge, src/RepoBackend.ts:213-217): it is
+  // handed the parent's changes above what it was handed before, up to the clock (GpuEngine.mergeFrom:
+  // the rows renamed and appended on the device), and answers with the RemotePatchMsg that
+  // applyRemoteChanges of those changes sends; clock and history advance as there.  A parent on
+  // another shard: the selected changes of its host log go to applyRemoteChanges.
   mergeFrom(parentBackend, clock) {
     this.afterIdle(() => {
-      if (!this.back || this.back.log.length) throw new Error('DocBackend.mergeFrom: the document already holds changes')
+      if (!this.back) throw new Error('DocBackend.mergeFrom: the document is not initialised')
+      if (this.back.log.length) {
+        const r = this.engine.mergeFromNow([{ into: this.back, from: parentBackend.back, clock }])[0]
+        if (r.error) throw r.error
+        if (r.entries) { if (r.entries.length) this.applyRemoteChanges(r.entries); return }
+        if (!r.patch || r.changes === 0) return      // (nothing above what it was handed before: syncReadyActors hands nothing)
+        this.updateClock(r.roundClock)
+        this.notify({ type: 'RemotePatchMsg', id: this.id, minimumClockSatisfied: this.minimumClockSatisfied,
+          patch: r.patch, history: this.back.histLen })
+        return
+      }
       const f = this.engine.forkNow([{ from: parentBackend.back, clock, id: this.id }])[0]
       this.engine.states[this.back.shard].delete(this.back.id)    // (the empty document it replaces)
       this.back = f.state

@@ -1115,6 +1115,35 @@ static napi_value DocsetFork(napi_env env, napi_callback_info info) {
     return o;
 }
 
+/* docsetMergeFrom(docset, dst Uint32Array, src Uint32Array, entryOff Uint32Array [n + 1], actorIds Buffer,
+ * actorOff Uint32Array [entries + 1], seqs Float64Array) -> {results, data}: document dst[i] is handed
+ * document src[i]'s changes above what it was handed before, up to the clock given as docsetMaterialize
+ * takes one, actor after actor in entry order; results / data are what docsetApply returns for a round
+ * handing the destinations those changes (hm_docset_merge_from; refused while a call is in flight) */
+static napi_value DocsetMergeFrom(napi_env env, napi_callback_info info) {
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return NULL;
+    Docset *d = get_docset(env, argv[0]);
+    if (!d) return NULL;
+    void *p[6]; size_t len[6];
+    for (int i = 0; i < 6; i++)
+        if (!get_bytes(env, argv[1 + i], &p[i], &len[i])) return NULL;
+    const uint32_t n = (uint32_t)(len[0] / 4);
+    const uint32_t *eoff = (const uint32_t *)p[2], *aoff = (const uint32_t *)p[4];
+    const uint32_t zero[1] = {0};
+    int ok = n && p[1] && eoff && len[1] / 4 == n && len[2] / 4 == (size_t)n + 1 && eoff[0] == 0;
+    const uint32_t ne = ok ? eoff[n] : 0;
+    ok = ok && len[5] / 8 >= ne && (ne == 0 || (len[4] / 4 >= (size_t)ne + 1 && aoff[ne] <= len[3]));
+    if (!ok) { napi_throw_type_error(env, NULL, "docsetMergeFrom: a source and a clock per destination, and table lengths that agree"); return NULL; }
+    hm_text *t = NULL;
+    int st = hm_docset_merge_from(d->ds, n, (const uint32_t *)p[0], (const uint32_t *)p[1], eoff, p[3] ? (const char *)p[3] : "",
+                                  ne ? aoff : zero, ne ? (const double *)p[5] : NULL, &t);
+    if (st) return throw_status(env, d->engine, st, "hm_docset_merge_from");
+    napi_value o = text_object(env, &t);
+    if (t) hm_text_free(t);
+    return o;
+}
+
 /* docsetMaterializePatch(docset, ids Uint32Array, histLen Uint32Array) -> JSON text, per request
  * {"doc", "history", "patch"}: the patch of the document as it was at that history length (clock, deps,
  * per-op diffs from the device), or "patch": null with "host": true when the prefix assigns list /
@@ -1444,7 +1473,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"docsetCreate", DocsetCreate}, {"docsetOpen", DocsetOpen}, {"docsetApply", DocsetApply}, {"docsetApplyPacked", DocsetApplyPacked},
         {"docsetHistoryPrefix", DocsetHistoryPrefix}, {"docsetClockUpdate", DocsetClockUpdate},
         {"docsetView", DocsetView}, {"docsetBlocked", DocsetBlocked}, {"docsetWaiting", DocsetWaiting},
-        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetFields", DocsetFields}, {"docsetMaterialize", DocsetMaterialize}, {"docsetFork", DocsetFork}, {"docsetMaterializePatch", DocsetMaterializePatch}, {"docsetMaterializePatchEx", DocsetMaterializePatchEx}, {"docsetMaterializePatchAt", DocsetMaterializePatchAt}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
+        {"docsetMissingChanges", DocsetMissingChanges}, {"docsetFields", DocsetFields}, {"docsetMaterialize", DocsetMaterialize}, {"docsetFork", DocsetFork}, {"docsetMergeFrom", DocsetMergeFrom}, {"docsetMaterializePatch", DocsetMaterializePatch}, {"docsetMaterializePatchEx", DocsetMaterializePatchEx}, {"docsetMaterializePatchAt", DocsetMaterializePatchAt}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
         {"cursorsCreate", CursorsCreate}, {"cursorsReserve", CursorsReserve}, {"cursorsUpdate", CursorsUpdate},
         {"cursorsGet", CursorsGet}, {"cursorsEntry", CursorsEntry}, {"cursorsDocsWithActors", CursorsDocsWithActors},
         {"syncRanges", SyncRanges}, {"decodeBlocks", DecodeBlocks}, {"commCreateLocalDocsets", CommCreateLocalDocsets},

@@ -177,6 +177,43 @@ class DocEncoder:
                      self.pool.strings, [list(self.actors)], [list(self.obj_list)], [list(self.reg_list)])
 
 
+def merge_maps(es: DocEncoder, ed: DocEncoder, S: int):
+    """The maps that carry rows of the document encoded by `es` into the document encoded by `ed`
+    (hm_merge_maps), interning into `ed` every actor, object, register and content key `es` holds.
+    Returns (totals [4] = ed's n_actors, n_regs, n_objs afterwards and es's flags, the rank row [S]
+    (NONE beyond es's actors), the object, register and content maps, ed's old rank -> new rank as
+    bytes or None when no rank of ed moved).  ed's host log mirror is re-ranked with it."""
+    mp = None
+    if ed is not es:
+        new = set(es.actors) - set(ed.actors)
+        if new:
+            if len(ed.actors) + len(new) > S:
+                raise ValueError(f"{len(ed.actors) + len(new)} actors > a_stride {S}")
+            ranked = sorted(set(ed.actors) | new, key=js_key)
+            at = {a: r for r, a in enumerate(ranked)}
+            m = np.array([at[a] for a in ed.actors], np.uint8)
+            if len(m) and not np.array_equal(m, np.arange(len(m), dtype=np.uint8)):
+                mp = m
+                if ed.keep_log:
+                    ed.log_changes, ed.log_deps = ed.log_changes.copy(), ed.log_deps.copy()
+                    ed.log_changes["actor"] = mp[ed.log_changes["actor"]]
+                    ed.log_deps["actor"] = mp[ed.log_deps["actor"]]
+            ed.actors = ranked
+    at = {a: r for r, a in enumerate(ed.actors)}
+    rank = np.full(S, NONE, np.uint32)
+    rank[:len(es.actors)] = [at[a] for a in es.actors]
+    om = np.array([ed._obj(u) for u in es.obj_list], np.uint32)
+    rm = np.array([ed._reg(int(om[o]), k) for o, k in es.reg_list], np.uint32).reshape(-1)
+    cm = np.full(len(es.content), NONE, np.uint32)
+    for ck, c in es.content.items():
+        j = ed.content.get(ck)
+        if j is None:
+            j = ed.content[ck] = len(ed.content)
+        cm[c] = j
+    ed.flags |= es.flags
+    return np.array([len(ed.actors), len(ed.reg_list), len(ed.obj_list), es.flags], np.uint32), rank, om, rm, cm, mp
+
+
 class _StoreConfig(ctypes.Structure):
     _fields_ = [("a_stride", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
@@ -196,6 +233,46 @@ class BatchResult:
     clock: np.ndarray           # [n, S] opSet.clock
     back_clock: np.ndarray      # [n, S] DocBackend.clock
     heads: np.ndarray           # [n, S] opSet.deps
+
+
+class _MergeMaps(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in ("totals", "rank", "obj_off", "obj_map", "reg_off", "reg_map",
+                                                "str_off", "str_map", "content_off", "content_map")]
+
+
+@dataclass
+class MergeMaps:
+    """hm_merge_maps: per request the destination's totals after the merge and the maps from the
+    source's id spaces into the destination's."""
+    totals: np.ndarray                         # [n, 4] n_actors, n_regs, n_objs, flags
+    rank: np.ndarray                           # [n, S] source rank -> destination rank
+    objs: Sequence[np.ndarray]                 # per request: source object id -> destination object id
+    regs: Sequence[np.ndarray]
+    strs: Optional[Sequence[np.ndarray]] = None      # None: identity
+    content: Optional[Sequence[np.ndarray]] = None
+
+    def c_struct(self, n: int, S: int):
+        """(the ctypes struct, the arrays it points into); built once per (n, S): a caller that merges with the
+        same maps again pays no second flattening"""
+        made = getattr(self, "_made", None)
+        if made is not None and made[0] == (n, S):
+            return made[1], made[2]
+
+        def csr(parts):
+            if parts is None:
+                return None, None
+            assert len(parts) == n
+            off = np.zeros(n + 1, np.uint32)
+            np.cumsum([len(p) for p in parts], out=off[1:])
+            flat = np.concatenate([np.asarray(p, np.uint32) for p in parts]) if n else np.zeros(0, np.uint32)
+            return off, np.ascontiguousarray(flat if len(flat) else np.zeros(1, np.uint32), np.uint32)
+        tot = np.ascontiguousarray(self.totals, np.uint32).reshape(n, 4)
+        rank = np.ascontiguousarray(self.rank, np.uint32).reshape(n, S)
+        keep = [tot, rank]
+        for parts in (self.objs, self.regs, self.strs, self.content):
+            keep.extend(csr(parts))
+        self._made = ((n, S), _MergeMaps(*[None if a is None else a.ctypes.data for a in keep]), keep)
+        return self._made[1], self._made[2]
 
 
 class DocStore:
@@ -344,6 +421,9 @@ class DocStore:
         src, self._forked = getattr(self, "_forked", None), None
         if src is not None:                      # a fork batch: the forks' encoders are their parents', cloned
             self._clone_encoders(src, handles, r.docs["status"])
+        if getattr(self, "_merged", False):      # a merge batch: the destinations' host logs follow the device's
+            self._merged = False
+            self._refresh_logs(handles, r.docs["status"])
         return r
 
     def apply(self, items, extra_actors=None) -> BatchResult:
@@ -671,6 +751,92 @@ class DocStore:
                 f.log_changes, f.log_deps, f.log_ops = self.log(h)
             self.enc[h] = f
 
+    # -- Repo.merge into a document that already holds changes -----------------------------------------
+    def _merge_rows(self, dst, src, rows, have, orow, maps: "MergeMaps", remap) -> int:
+        """hm_store_merge_from_submit over rank rows and explicit maps; returns the batch id."""
+        hs, ds = np.ascontiguousarray(src, np.uint32), np.ascontiguousarray(dst, np.uint32)
+        n, S = len(hs), self.S
+        assert len(ds) == n
+        u32 = lambda a, shape: None if a is None else np.ascontiguousarray(a, np.uint32).reshape(shape)
+        rows, have, orow = u32(rows, (n, S)), u32(have, (n, S)), u32(orow, (n, S))
+        remap = None if remap is None else np.ascontiguousarray(remap, np.uint8).reshape(n, S)
+        cm, keep = maps.c_struct(n, S)
+        bid = ctypes.c_uint64()
+        self._check(self._L.hm_store_merge_from_submit(self._h, n, _p(hs), _p(have), _p(rows), _p(orow), _p(ds),
+                                                       ctypes.byref(cm), _p(remap), ctypes.byref(bid)),
+                    "hm_store_merge_from_submit")
+        self._merge_keep = (hs, ds, rows, have, orow, remap, cm, keep)
+        return bid.value
+
+    def merge_from_submit(self, dst, src, clocks, have=None, order="clock") -> int:
+        """merge_from without the wait (wait() returns one row per request); returns the batch id."""
+        hs, ds = np.ascontiguousarray(src, np.uint32), [int(h) for h in dst]
+        n, S = len(hs), self.S
+        _, rows = self._selector(hs, None, clocks)
+        orow = self._order_rows(hs, clocks, order)
+        snaps, done = [], []
+        try:
+            totals, rank = np.zeros((n, 4), np.uint32), np.full((n, S), NONE, np.uint32)
+            objs, regs, cids, hv = [], [], [], np.zeros((n, S), np.uint32)
+            remap = None
+            for i, (p, h) in enumerate(zip(hs, ds)):
+                if h >= len(self.enc) or p >= len(self.enc):
+                    raise EngineError(f"request {i}: merge_from needs both documents' host encoders")
+                es, ed = self.enc[p], self.enc[h]
+                snaps.append(ed.snapshot())
+                done.append(h)
+                if have is None:                                   # DocBackend.clock of the destination, in source ranks
+                    back = np.zeros(S, np.uint32)
+                    self._check(self._L.hm_doc_read(self._h, h, None, None, None, None, None, _p(back), None), "hm_doc_read")
+                    was = {a: r for r, a in enumerate(ed.actors)}
+                    for r, a in enumerate(es.actors):
+                        if a in was:
+                            hv[i, r] = back[was[a]]
+                else:
+                    hv[i] = have[i]
+                try:
+                    totals[i], rank[i], om, rm, cm, mp = merge_maps(es, ed, S)
+                except ValueError as e:
+                    raise EngineError(f"document {h}: {e}")
+                if mp is not None:
+                    if remap is None:
+                        remap = np.tile(np.arange(S, dtype=np.uint8), (n, 1))
+                    remap[i, :len(mp)] = mp
+                objs.append(om); regs.append(rm); cids.append(cm)
+            bid = self._merge_rows(ds, hs, rows, hv, orow, MergeMaps(totals, rank, objs, regs, None, cids), remap)
+        except Exception:
+            for h, sn in zip(reversed(done), reversed(snaps)):
+                self.enc[h].restore(sn)
+            raise
+        self._pending = (bid, ds, snaps, self._merge_keep)
+        self._merged = True
+        return bid
+
+    def merge_from(self, dst, src, clocks, have=None, order="clock") -> BatchResult:
+        """Repo.merge(target, source) for resident documents, many per call: document dst[i] is handed
+        the changes of document src[i] (only read; may repeat) that are applied there with
+        have[a] < seq <= clocks[i][a] — in the clock's key order, actor after actor (order='clock', what
+        syncReadyActors does), in another actor order (see fork), or in the source's history order
+        (order=None).  clocks: {actorId: seq} per request or [n, S] rows in the source's ranks.  have
+        ([n, S], source ranks) defaults to the destination's DocBackend.clock row: what it was handed
+        before.  The rows go from the source's resident log to the destination's on the device, renamed
+        through maps built here from the two host encoders; the destination is re-ranked when a new actor
+        sorts before one of its own; content ids are mapped by the change's canonical content key (actor
+        and seq included), so a change the destination already holds keeps its id.
+
+        Deviation: every actor, object, register and content key of the SOURCE is interned into the
+        destination's encoder, not only those of the selected rows (deps and links may name any), so
+        the destination's totals can grow past what the handed changes mention.  A merge that throws
+        rolls the destination and its encoder back.  Returns wait()'s rows: the destinations' whole logs."""
+        self.merge_from_submit(dst, src, clocks, have, order)
+        return self.wait()
+
+    def _refresh_logs(self, handles, status) -> None:
+        for h, st in zip(handles, status):
+            if st == 0 and h < len(self.enc) and self.enc[h].keep_log:
+                e = self.enc[h]
+                e.log_changes, e.log_deps, e.log_ops = self.log(h)
+
     def op_diff_sizes(self, handles, frm, to, lists=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """hm_store_op_diff_sizes: ([n, 2] diff rows / survivor rows per request, flags [n], their [2] totals).
         lists=True: the sizes of op_diffs(..., lists=True)."""
@@ -826,6 +992,19 @@ class RowStore(DocStore):
         self._pending = (bid, len(new), None, self._pending[3])
         self._forked = None
         return new, bid
+
+    def merge_from_submit(self, dst, src, clocks, maps: MergeMaps, have=None, order=None, remap=None) -> int:
+        """hm_store_merge_from_submit with explicit maps: clocks / have [n, S] rows in the sources' ranks,
+        order [n, S] rank rows or None (history order), remap [n, S] bytes (the destinations' old rank
+        -> new rank) or None.  wait() returns one row per request."""
+        bid = self._merge_rows(dst, src, clocks, have, self._order_rows(np.ascontiguousarray(src, np.uint32), None, order),
+                               maps, remap)
+        self._pending = (bid, len(dst), None, self._merge_keep)
+        return bid
+
+    def merge_from(self, dst, src, clocks, maps: MergeMaps, have=None, order=None, remap=None) -> BatchResult:
+        self.merge_from_submit(dst, src, clocks, maps, have, order, remap)
+        return self.wait()
 
     def submit_batch(self, b: Batch, handles: np.ndarray) -> int:
         hs = np.ascontiguousarray(handles, np.uint32)

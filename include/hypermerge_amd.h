@@ -513,7 +513,8 @@ typedef struct {          /* 64 B */
     uint64_t totals[4];   /* changes, deps, ops, registers of all requests */
     uint32_t max_changes, max_ops, max_regs, max_objs, max_deps, doc_flags;  /* hm_batch launch hints */
     uint32_t bad;         /* _device form: 1 a handle outside the source, 2 a change row outside its document
-                           * (store forms also: 4 a bad actor order row, 8 a bad fork destination) */
+                           * (store forms also: 4 a bad actor order row, 8 a bad fork / merge destination,
+                           * 16 a bad merge map) */
     uint32_t pad;
 } hm_past_summary;
 typedef struct {
@@ -573,6 +574,51 @@ int hm_store_materialize(hm_store *s, uint32_t n, const uint32_t *doc_handles, c
 int hm_store_fork_submit(hm_store *s, uint32_t n, const uint32_t *src_handles, const uint32_t *hist_len,
                          const uint32_t *clock_rows, const uint32_t *actor_order, const uint32_t *dst_handles, uint32_t flags,
                          uint64_t *out_batch_id);
+/* Merge into a live document: resident documents' changes handed to other resident documents that may
+ * already hold changes (src/RepoBackend.ts:213-217 RepoBackend.merge = cursors.update + syncReadyActors,
+ * which hands the target each listed actor's changes above what it was handed before, up to
+ * clock[actor], actor after actor).  Request i = the changes of document src_handles[i] (only read; a
+ * handle may repeat) that are applied there with have[a] < seq <= clock[a], into document
+ * dst_handles[i]:
+ *   clock_rows   [n * a_stride], required; have_rows [n * a_stride] or NULL (no lower bound); both in
+ *                the SOURCE's rank space
+ *   actor_order  as hm_store_fork_submit's (source ranks; NULL = the source's history order); with it
+ *                actor a contributes max(0, min(clock[a], opSet.clock[a]) - have[a]) changes
+ * The two documents' id spaces differ, so the selected rows are renamed on the device through maps the
+ * caller builds (it holds both documents' interners):
+ *   totals       [4n] the destination's n_actors, n_regs, n_objs after the merge and flags to OR in
+ *   rank         [n * a_stride] source rank -> destination rank (after the merge)
+ *   obj / reg    CSR per request (off [n + 1], starting at 0): source object / register id ->
+ *                destination id; str / content: the same for string-pool and content ids, optional
+ *                (NULL map: identity, its off is not read)
+ * A change row's actor goes through rank, its content_id through content; a dep row's actor through
+ * rank; an op row's obj through obj, reg (unless HM_NONE) and parent (unless HM_HEAD) through reg, key
+ * (set / del / link / inc ops) through str, value through str (HM_V_STR) or obj (HM_V_OBJ); elem and
+ * everything else stay.  An id at or beyond its slice, a map entry of HM_NONE, or an image at or beyond
+ * the stated totals is never read through and refuses the call.
+ * dst_actor_remap is hm_batch_submit's actor_remap for the destinations ([n * a_stride] bytes, old rank
+ * -> new rank; NULL = no destination's ranks moved).
+ * No row passes through the host.  The call reads back twice before the submit: the totals with the
+ * verdicts on handles, order rows and destinations after the count pass, and the maps' verdict after
+ * the rename pass.  It is then the store's batch in flight: hm_batch_wait returns one row per request,
+ * the result of the destination's WHOLE log; a merge that throws rolls only that destination back;
+ * hm_batch_undo restores every destination (ranks mapped back).  An empty selection leaves the
+ * destination's log as it was (it takes the stated totals) and returns its current result row.  The
+ * destinations' minimumClock rows are not touched.
+ * HM_ERR_INVALID, nothing changed: n == 0, no clock_rows, a bad order row, a handle outside the store, a
+ * destination outside the store, named twice, also a source of the call, with stated totals below its
+ * current ones or n_actors > a_stride, a bad map, offsets that decrease, a batch in flight. */
+typedef struct {
+    const uint32_t *totals;                    /* [4n] n_actors, n_regs, n_objs, flags */
+    const uint32_t *rank;                      /* [n * a_stride] */
+    const uint32_t *obj_off, *obj_map;         /* [n + 1], [obj_off[n]] */
+    const uint32_t *reg_off, *reg_map;
+    const uint32_t *str_off, *str_map;         /* str_map NULL: identity */
+    const uint32_t *content_off, *content_map; /* content_map NULL: identity */
+} hm_merge_maps;
+int hm_store_merge_from_submit(hm_store *s, uint32_t n, const uint32_t *src_handles, const uint32_t *have_rows,
+                               const uint32_t *clock_rows, const uint32_t *actor_order, const uint32_t *dst_handles,
+                               const hm_merge_maps *maps, const uint8_t *dst_actor_remap, uint64_t *out_batch_id);
 /* The gather alone over the tables of a merged cold batch (b's docs / changes / deps / ops, r's docs /
  * hist), everything in device memory, enqueued on `stream` (NULL = the engine's) without
  * synchronising.  Request i = document doc_index[i] of b (NULL: document i); hist_len / clock_rows
@@ -1090,6 +1136,32 @@ int hm_docset_materialize_patch_at(hm_docset *ds, uint32_t n, const uint32_t *do
  * All-or-nothing as hm_docset_apply is (a failed call leaves the new documents empty). */
 int hm_docset_fork(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *hist_len, const uint32_t *entry_off,
                    const char *actor_ids, const uint32_t *actor_off, const double *seqs, uint32_t *out_first, hm_text **out);
+/* Merge into live documents (RepoBackend.merge, src/RepoBackend.ts:213-217; hm_store_merge_from_submit
+ * per stride class): destination dst_docs[i] (each at most once, none a source of the call) is handed
+ * source src_docs[i]'s (may repeat) applied changes above what it was handed before — its
+ * DocBackend.clock — up to the clock given as hm_docset_materialize takes one, actor after actor in
+ * entry order (an id the source never saw is dropped, a repeated id counts once with its last seq,
+ * Infinity clamps).  Every actor, object, register and string of the source is interned into the
+ * destination (deps and links may name any); its content table grows by the (actor, seq) entries the
+ * selector covers.  *out = what a hm_docset_apply round handing the destinations those changes returns
+ * (result rows, one combined patch per destination, DocBackend.clock), whatever the docset's flags.
+ * Routes: a request whose two documents live in one stride class, the destination staying in it,
+ * moves its rows on the device (renamed there; the change and op rows are read back for the host
+ * mirror); every other request — classes that differ, a destination that must move to a wider class
+ * or is not placed yet, a source not placed yet (nothing to hand) — reads the source's log back,
+ * selects and renames on the host and goes through the apply round's placement.  A class that takes
+ * a host-route round in a call takes all its rounds of that call that way (a store has one batch in
+ * flight and undoes only its last).  A performance caveat: one such request in a class — a destination
+ * or a source not placed yet among them — moves every request of that class in the call to the host
+ * route; a caller that cares sends those requests in a call of their own (hm_docset_merge_stats shows
+ * what happened).  Both routes give the same patches and state.  The destination's
+ * DocBackend.clock rows are read once per stride class; the device route reads back the renamed change
+ * rows and the op map, and the renamed op rows only where the docset keeps no host copy of its logs
+ * (HM_DOCSET_NET_DIFFS, HM_DOCSET_NO_PATCHES).  All-or-nothing as hm_docset_apply is.
+ * hm_docset_merge_stats: out2 = requests that took the device route, the host route. */
+int hm_docset_merge_from(hm_docset *ds, uint32_t n, const uint32_t *dst_docs, const uint32_t *src_docs, const uint32_t *entry_off,
+                         const char *actor_ids, const uint32_t *actor_off, const double *seqs, hm_text **out);
+int hm_docset_merge_stats(const hm_docset *ds, uint64_t *out2);
 /* the merged document: {uuid: {"type", "keys": [[key, entry]], "elems": [[elemId, entry]]}} */
 int hm_docset_view(hm_docset *ds, uint32_t doc, hm_text **out);
 /* counters: calls, documents, class moves, net patches from the hit registers, net patches from every

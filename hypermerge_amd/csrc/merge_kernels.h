@@ -57,6 +57,41 @@ size_t hm_large_scratch_bound(const hm_batch *b);
 size_t hm_large_stack_bytes();
 hipError_t hm_launch_large(const SmallParams &p, void *pool, size_t pool_bytes, unsigned long long *pool_used,
                            uint32_t grid, hipStream_t s);
+// Path census of merge_large_kernel (check builds, -DHM_PATH_CENSUS=1): one counter per outcome
+// of each run-time layout decision in merge_large.hip.  Every slot counts documents, except the
+// two REG slots (registers).  A yes / no pair is (slot, slot + 1).  tests/general_edges.py
+// restates the order; keep the two in step.
+enum hm_large_path {
+    HM_LP_GATE_PASSED = 0,      // the dispatcher tried the all-LDS path (merge_doc_res)
+    HM_LP_GATE_REFUSED,         // ... or went straight to the pool path (merge_doc_large)
+    // the all-LDS path's exits to the pool path (RES_FALLBACK), one per document at most
+    HM_LP_RES_OUT_ROWS,         // malformed change rows
+    HM_LP_RES_OUT_TABLE,        // sparse first-arrival table, or table + closure rows over stage_base
+    HM_LP_RES_OUT_NOT_READY,    // a change not ready on arrival, or a mismatched duplicate
+    HM_LP_RES_OUT_FOLD,         // the literal fold differs from the closure
+    HM_LP_RES_OUT_TAIL,         // l34_res: the layout's tail over the limit (or its id widths)
+    HM_LP_RES_OUT_COUNTERS,     // counter ops
+    HM_LP_RES_OUT_LONG_LIST,    // a register with more than RES_SEG_MAX assigns (and no counters)
+    HM_LP_RES_OUT_TOUR,         // the Euler tour does not fit over the dead region (neither of the above)
+    HM_LP_RES_OUT_LATE,         // an insert after an element that arrives later
+    HM_LP_RES_DONE,             // the all-LDS path merged the document
+    // the pool path: (yes, no) pairs
+    HM_LP_STAGED, HM_LP_STAGED_NO,
+    HM_LP_LTAB, HM_LP_LTAB_NO,
+    HM_LP_CLOSURE_LDS, HM_LP_CLOSURE_LDS_NO,
+    HM_LP_L3, HM_LP_L3_NO,
+    HM_LP_LOP, HM_LP_LOP_NO,
+    HM_LP_OBJ_LDS, HM_LP_OBJ_LDS_NO,
+    HM_LP_TOUR_LDS, HM_LP_TOUR_LDS_NO,          // (documents with lists only)
+    HM_LP_SCRATCH_REUSED, HM_LP_SCRATCH_CARVED,
+    HM_LP_HIST_FAST, HM_LP_HIST_PARALLEL, HM_LP_HIST_SERIAL,     // the pool path's history
+    HM_LP_REG_SHORT, HM_LP_REG_LONG,            // registers with 1..SEG_SHORT / more assigns
+    HM_LP_POOL_DONE,            // the pool path merged the document
+    HM_LP_N
+};
+// (check builds only) out[0 .. n) = the counters since the last reset; returns the slots copied
+extern "C" int hm_debug_large_paths(unsigned long long *out, int n, int reset);
+
 // small-kernel size class (LDS carve) for a batch's per-document maxima
 uint32_t hm_small_class(uint32_t max_regs, uint32_t max_objs, uint32_t max_deps);
 size_t hm_small_lds_bytes(uint32_t opl, uint32_t cls, bool lists, bool counters);

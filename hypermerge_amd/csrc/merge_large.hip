@@ -48,6 +48,10 @@ typedef unsigned long long u64;
 #define HM_STAMPS 0     // diagnostic builds only: per-phase s_memtime shares (tools/lstamps.py); never timed
 #endif
 #define HML_NSTAMP 16
+#ifndef HM_PATH_CENSUS
+#define HM_PATH_CENSUS 0    // check builds (libhmgpu_check.so): every layout decision a document takes is counted
+                            // (hm_large_path in merge_kernels.h, read by hm_debug_large_paths); never feeds a decision
+#endif
 // registers with at most this many assigns test survivors against the assign list directly;
 // longer lists build per-actor maxima with atomics (SEG_SHORT assign lists cost one LDS row
 // read each, where every assign's A atomicMax on shared L2 lines cost ~27 % of C3's kernel)
@@ -70,6 +74,18 @@ __device__ __forceinline__ u64 lstamp_now() {
 #define LSTAMP(i) do { bsync(); const u64 t_ = lstamp_now(); if (threadIdx.x == 0) { hml_st[i] += t_ - hml_st[HML_NSTAMP]; hml_st[HML_NSTAMP] = t_; } } while (0)
 #else
 #define LSTAMP(i) do { } while (0)
+#endif
+#if HM_PATH_CENSUS
+__device__ unsigned long long hml_paths[HM_LP_N];
+// block-uniform decision points: thread 0 counts the outcome
+#define CENSUS(slot) do { if (threadIdx.x == 0) atomicAdd(&hml_paths[slot], 1ull); } while (0)
+#define CENSUS_YN(c, yes) CENSUS((c) ? (yes) : (yes) + 1)
+// per-thread tallies (registers by assign-list length)
+#define CENSUS_ADD(slot, v) do { if (v) atomicAdd(&hml_paths[slot], (unsigned long long)(v)); } while (0)
+#else
+#define CENSUS(slot) do { } while (0)
+#define CENSUS_YN(c, yes) do { } while (0)
+#define CENSUS_ADD(slot, v) do { } while (0)
 #endif
 // order one lane's global writes before the wave's next reads (wave-uniform sections)
 __device__ __forceinline__ void wfence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
@@ -456,7 +472,7 @@ __device__ __forceinline__ int l34_res(const SmallParams &p, Shared &sh, LDS uin
     LDS uint32_t *p_cnt = w32(NP), *p_off = w32(NP);
     LDS uint16_t *p_fc = w16(NP);
     const uint32_t tail = off;
-    if (A > 8 || O > LA_MAX || m >= 65536 || NP >= 32767 || n >= 65536 || tail > limit) return RES_FALLBACK;
+    if (A > 8 || O > LA_MAX || m >= 65536 || NP >= 32767 || n >= 65536 || tail > limit) { CENSUS(HM_LP_RES_OUT_TAIL); return RES_FALLBACK; }
     auto dec_reg = [](uint32_t w) { return w & 0xFFFFu; };
     auto dec_act = [](uint32_t w) { return (w >> 16) & 15u; };
     auto dec_obj = [](uint32_t w) { return (w >> 20) & 127u; };
@@ -546,6 +562,7 @@ __device__ __forceinline__ int l34_res(const SmallParams &p, Shared &sh, LDS uin
         const uint32_t N = sh.nins < R ? sh.nins : R;
         const bool out = sh.ctrs || sh.grew || 2 * (N + O) + N > dead_end;
         if (out) {                                  // (uniform) every thread has read the flags
+            CENSUS(sh.ctrs ? HM_LP_RES_OUT_COUNTERS : (sh.grew ? HM_LP_RES_OUT_LONG_LIST : HM_LP_RES_OUT_TOUR));
             bsync();
             if (tid == 0) { sh.nins = 0; sh.ctrs = 0; }
             bsync();
@@ -630,6 +647,7 @@ __device__ __forceinline__ int l34_res(const SmallParams &p, Shared &sh, LDS uin
     if (any_list) sh.lists = 1;
     bsync();
     if (sh.late) {                                  // (uniform) every thread has read the flag
+        CENSUS(HM_LP_RES_OUT_LATE);
         bsync();
         if (tid == 0) { sh.nins = 0; sh.ctrs = 0; }
         bsync();
@@ -787,6 +805,7 @@ __device__ __forceinline__ int l34_res(const SmallParams &p, Shared &sh, LDS uin
     bsync();
     LSTAMP(10);
     if (sh.flags) return LUNSUP;
+    CENSUS(HM_LP_RES_DONE);
     return LOK;
 }
 
@@ -842,7 +861,7 @@ __device__ __forceinline__ int merge_doc_res(const SmallParams &p, Shared &sh, L
         else { atomicMin(&sh.base[c.actor], c.seq); atomicMax(&sh.maxs[c.actor], c.seq); atomicMax(&sh.bclock[c.actor], c.seq); }
     }
     bsync();
-    if (sh.flags) return RES_FALLBACK;
+    if (sh.flags) { CENSUS(HM_LP_RES_OUT_ROWS); return RES_FALLBACK; }
     // table offsets per actor, computed by every thread (A <= 8) and published by thread 0
     uint32_t T = 0;
     for (uint32_t a = 0; a < A; a++) { if (tid == 0) sh.tabo[a] = T; if (sh.maxs[a]) T += sh.maxs[a] - sh.base[a] + 1; }
@@ -850,7 +869,7 @@ __device__ __forceinline__ int merge_doc_res(const SmallParams &p, Shared &sh, L
     // closure rows at an odd stride: the groups of a wave read rows of different changes, and
     // at stride 8 those rows met in the same banks four apart
     const uint32_t AS = A | 1u;
-    if (T > 4 * n + 64 || n * AS + T > stage_base) return RES_FALLBACK;
+    if (T > 4 * n + 64 || n * AS + T > stage_base) { CENSUS(HM_LP_RES_OUT_TABLE); return RES_FALLBACK; }
     LDS uint32_t *lt = ar, *lc = ar + T;            // L1 table, L2 closure rows (stride A)
     for (uint32_t i = tid; i < T; i += LWG) lt[i] = 0xFFFFFFFFu;
     bsync();                                        // (also publishes sh.tabo)
@@ -879,7 +898,7 @@ __device__ __forceinline__ int merge_doc_res(const SmallParams &p, Shared &sh, L
     }
     bsync();
     const bool all_ready = sh.all_ok != 0;          // (next written after the history scan's barriers)
-    if (!all_ready) return RES_FALLBACK;
+    if (!all_ready) { CENSUS(HM_LP_RES_OUT_NOT_READY); return RES_FALLBACK; }
     if (n <= LWG) {
         H_out = 0;
         const uint32_t Hc = scan_fn_small(sh, [&](uint32_t i) -> uint32_t {
@@ -1004,7 +1023,7 @@ __device__ __forceinline__ int merge_doc_res(const SmallParams &p, Shared &sh, L
         if (!same) sh.all_ok = 0;
     }
     bsync();
-    if (!sh.all_ok) return RES_FALLBACK;       // the literal fold lowers an entry: general path
+    if (!sh.all_ok) { CENSUS(HM_LP_RES_OUT_FOLD); return RES_FALLBACK; }      // the literal fold lowers an entry: general path
     LSTAMP(3);
     for (uint32_t h = tid; h < H; h += LWG) {
         const uint32_t ci = lh2a[h];
@@ -1041,6 +1060,7 @@ __device__ __noinline__ Outcome merge_doc_large(const SmallParams &p, Shared &sh
     const uint32_t nd = doc.n_deps;
     const bool staged = 8 * (size_t)n + 2 * (size_t)nd <= LARENA / 4;
     const uint32_t stage_base = staged ? (LARENA - (8 * n + 2 * nd)) & ~1u : LARENA;
+    CENSUS_YN(staged, HM_LP_STAGED);
     LDS hm_change_row *sCH = (LDS hm_change_row *)(ar + stage_base);
     LDS hm_dep_row *sDP = (LDS hm_dep_row *)(ar + stage_base + 6 * n);
     LDS int32_t *lh = (LDS int32_t *)(ar + stage_base + 6 * n + 2 * nd);
@@ -1073,6 +1093,7 @@ __device__ __noinline__ Outcome merge_doc_large(const SmallParams &p, Shared &sh
         const size_t need = large_carve(0, n, m, R, O, A, t, &tmp);
         // reuse the workgroup's previous scratch when it is big enough: its lines are still in
         // L2 / MALL, where fresh pool memory per document cost HBM write-backs and misses
+        CENSUS_YN(need <= sh.ws_size, HM_LP_SCRATCH_REUSED);
         if (need <= sh.ws_size) sh.scratch_base = sh.ws_base;
         else {
             const u64 at = atomicAdd(pool_used, (u64)need);
@@ -1089,6 +1110,7 @@ __device__ __noinline__ Outcome merge_doc_large(const SmallParams &p, Shared &sh
     const bool regrows = A <= 8;            // L2 rows held in registers: one LDS buffer, updated in place
     const uint32_t l2words = (regrows ? n * A : 2 * n * A) + T;
     const bool ltab = staged && l2words <= stage_base;
+    CENSUS_YN(ltab, HM_LP_LTAB);
     LDS uint32_t *lt = ar;                  // L1 table (ltab) / L2 table
     auto tabv = [&](uint32_t sl) -> uint32_t { if (ltab) return lt[sl]; return X.tab[sl]; };
     for (uint32_t i = tid; i < T; i += LWG) { if (ltab) lt[i] = 0xFFFFFFFFu; else X.tab[i] = 0xFFFFFFFFu; }
@@ -1132,6 +1154,7 @@ __device__ __noinline__ Outcome merge_doc_large(const SmallParams &p, Shared &sh
     const bool all_ready = sh.all_ok != 0;
     bsync();
     if (all_ready) {
+        CENSUS(HM_LP_HIST_FAST);
         // history = arrival order minus duplicates (block scan of non-duplicate flags)
         uint32_t carry = 0;
         for (uint32_t c0 = 0; c0 < n; c0 += LWG) {
@@ -1157,7 +1180,9 @@ __device__ __noinline__ Outcome merge_doc_large(const SmallParams &p, Shared &sh
     }
     if (parallel_history(CH, p.deps, sh, X.vc, X.hx, X.tab, X.h2a, X.hist, n, A, T)) {
         // history from (t, pass, arrival) without the serial queue emulation
+        CENSUS(HM_LP_HIST_PARALLEL);
     } else if (wave == 0) {
+        CENSUS(HM_LP_HIST_SERIAL);
         // ---- exact emulation of addChange / applyQueuedOps; wave 0, wave-uniform control ----
         // hist: -3 not arrived, -1 queued, -2 duplicate (no-op), >= 0 history position
         for (uint32_t i = lane; i < T; i += 64) X.tab[i] = 0xFFFFFFFFu;       // -> applied arrival index
@@ -1248,6 +1273,7 @@ __device__ __noinline__ Outcome merge_doc_large(const SmallParams &p, Shared &sh
     //     fold runs serially in history order below.
     uint32_t *cur = p.res_all_deps + (size_t)doc.change_off * S, *nxt = X.vc;   // row stride S / A
     LDS uint32_t *lrows = nullptr;          // the closure rows when L2 ran in LDS (stride A)
+    CENSUS_YN(staged ? ltab : l2words <= LARENA, HM_LP_CLOSURE_LDS);
     if (staged ? ltab : l2words <= LARENA) {
         // the same rounds and check with the first-arrival table and both row buffers in LDS
         LDS uint32_t *lc = ar + T, *ln = ar + T + n * A;        // row stride A
@@ -1530,6 +1556,9 @@ __device__ __noinline__ Outcome merge_doc_large(const SmallParams &p, Shared &sh
     LDS uint16_t *l_opchg = (LDS uint16_t *)(ar + 5 * n + n * A);
     // object tables in LDS when they fit (text / list documents have a handful of objects)
     const bool obj_lds = O <= LA_MAX;
+    CENSUS_YN(l3, HM_LP_L3);
+    CENSUS_YN(lop, HM_LP_LOP);
+    CENSUS_YN(obj_lds, HM_LP_OBJ_LDS);
     auto oslot_get = [&](uint32_t o) -> uint32_t { return obj_lds ? sh.oslot[o] : X.objslot[o]; };
     auto otype_get = [&](uint32_t o) -> uint32_t { return obj_lds ? sh.otype[o] : X.objtype[o]; };
     for (uint32_t i = tid; i < O; i += LWG) {
@@ -1629,6 +1658,7 @@ __device__ __noinline__ Outcome merge_doc_large(const SmallParams &p, Shared &sh
     for (uint32_t i = tid; i < R; i += LWG) {
         const uint32_t c = X.segcnt[i];
         X.segoff[i] = c;
+        CENSUS_ADD(c > SEG_SHORT ? HM_LP_REG_LONG : HM_LP_REG_SHORT, c ? 1u : 0u);
         if (c > SEG_SHORT) for (uint32_t a = 0; a < A; a++) X.segmax[(size_t)i * A + a] = 0;
     }
     bsync();
@@ -1926,6 +1956,7 @@ __device__ __noinline__ Outcome merge_doc_large(const SmallParams &p, Shared &sh
         // tour entries (next, value): two pool arrays, or one LDS word each (next << 16 | value,
         // END = 0xFFFF) when the tour fits the arena and its indices fit 16 bits
         const bool tour_lds = E <= LARENA && E < 0xFFFFu;
+        CENSUS_YN(tour_lds, HM_LP_TOUR_LDS);
         LDS uint32_t *tw = ar;
         uint32_t *nx0 = X.tour0, *nx1 = X.tour1;
         uint32_t *va0 = X.tval0, *va1 = X.tval1;
@@ -2023,6 +2054,7 @@ __device__ __noinline__ Outcome merge_doc_large(const SmallParams &p, Shared &sh
     bsync();
     if (sh.flags) return LUNSUP;
     LSTAMP(10);
+    CENSUS(HM_LP_POOL_DONE);
     return LOK;
 }
 
@@ -2067,8 +2099,10 @@ __global__ __launch_bounds__(LWG) __attribute__((amdgpu_waves_per_eu(HML_WPE))) 
         int rc = RES_FALLBACK;
         const uint32_t dn = doc.n_changes, dd = doc.n_deps;
         if (dn >= 1 && doc.n_actors <= 8 && doc.n_objs >= 1 && doc.n_objs <= LA_MAX && doc.n_ops < 65536 &&
-            doc.n_regs + doc.n_objs < 32767 && 8 * (size_t)dn + 2 * (size_t)dd <= LARENA / 4)
+            doc.n_regs + doc.n_objs < 32767 && 8 * (size_t)dn + 2 * (size_t)dd <= LARENA / 4) {
+            CENSUS(HM_LP_GATE_PASSED);
             rc = merge_doc_res(p, sh, arena, doc, H);
+        } else CENSUS(HM_LP_GATE_REFUSED);
         const bool via_res = rc != RES_FALLBACK;   // (every change ready on arrival: nothing queued)
         if (!via_res) {
             bsync();
@@ -2144,6 +2178,20 @@ extern "C" int hm_debug_lstamps(unsigned long long *out, int n, int reset) {
     if (reset) {
         unsigned long long z[HML_NSTAMP] = {};
         if (hipMemcpyToSymbol(HIP_SYMBOL(hml::hml_stamp_acc), z, sizeof z) != hipSuccess) return -1;
+    }
+    return n;
+}
+#endif
+
+#if HM_PATH_CENSUS
+// (check builds) documents per outcome of each layout decision since the last reset: out[hm_large_path]
+extern "C" int hm_debug_large_paths(unsigned long long *out, int n, int reset) {
+    if (n > HM_LP_N) n = HM_LP_N;
+    if (!out || n < 0 || hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(hml::hml_paths), n * sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (reset) {
+        unsigned long long z[HM_LP_N] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(hml::hml_paths), z, sizeof z) != hipSuccess) return -1;
     }
     return n;
 }

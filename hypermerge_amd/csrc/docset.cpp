@@ -1365,18 +1365,18 @@ struct Call {
     }
     // placement: a document lives in the narrowest class that holds its actors
     void place() {
-        for (uint32_t i = 0; i < n; i++) {
-            Round &x = R[i];
-            if (x.status != HM_OK) continue;
-            DocSt &d = ds->doc(x.doc);
-            uint8_t c = class_for(x.n_actors);
-            if (d.cls != NO_CLASS && d.cls > c) c = d.cls;
-            x.cls = c;
-            x.placed = d.cls == NO_CLASS;
-            x.moved = !x.placed && c != d.cls;
-            x.handle = d.handle;
-            by_cls[c].push_back(i);
-        }
+        for (uint32_t i = 0; i < n; i++) if (R[i].status == HM_OK) place_round(i);
+    }
+    void place_round(uint32_t i) {
+        Round &x = R[i];
+        DocSt &d = ds->doc(x.doc);
+        uint8_t c = class_for(x.n_actors);
+        if (d.cls != NO_CLASS && d.cls > c) c = d.cls;
+        x.cls = c;
+        x.placed = d.cls == NO_CLASS;
+        x.moved = !x.placed && c != d.cls;
+        x.handle = d.handle;
+        by_cls[c].push_back(i);
     }
     // `fresh` handles of class c for its placed and moved documents: released ones first, then new ones
     int take_handles(uint32_t c, hm_store *st, uint32_t fresh, std::vector<uint32_t> &fh) {
@@ -1475,21 +1475,85 @@ struct Call {
         ClsOut &O = co[c];
         if ((rc = hm_batch_submit(st, &b, hand.data(), any_remap ? remap.data() : nullptr, &O.id))) return rc;
         O.sub = true;
-        O.res.resize(rows.size()); O.clock.resize(rows.size() * (size_t)S); O.back.resize(rows.size() * (size_t)S);
-        O.heads.resize(rows.size() * (size_t)S);
-        if ((rc = hm_batch_wait(st, O.id, O.res.data(), O.clock.data(), O.back.data(), O.heads.data()))) return rc;
-        O.sub = false;
-        O.done = true;
+        if ((rc = wait_class(c, (uint32_t)rows.size()))) return rc;
+        if (n_waited++ == inj_wait) return hm_engine_fail(ds->e, HM_ERR_DEVICE, "injected failure (HM_DOCSET_INJECT_FAIL)");
+        for (uint32_t k = 0; k < rows.size(); k++) point_round(R[rows[k]], c, k);
+        return HM_OK;
+    }
+    // class c's submitted batch of m rounds, waited for: its result rows, the call's routing
+    int wait_class(uint32_t c, uint32_t m) {
+        ClsOut &O = co[c];
+        hm_store *st = ds->stores[c];
+        const size_t S = STRIDES[c];
+        O.res.resize(m); O.clock.resize(m * S); O.back.resize(m * S); O.heads.resize(m * S);
+        const int rc = hm_batch_wait(st, O.id, O.res.data(), O.clock.data(), O.back.data(), O.heads.data());
+        if (rc) return rc;
+        O.sub = false; O.done = true;
         uint32_t r3[3] = {0, 0, 0};
         if (hm_store_last_routing(st, r3) == HM_OK)
             for (int k = 0; k < 3; k++) call_routing[k] += r3[k];         // (counted once the call commits)
-        if (n_waited++ == inj_wait) return hm_engine_fail(ds->e, HM_ERR_DEVICE, "injected failure (HM_DOCSET_INJECT_FAIL)");
-        for (uint32_t k = 0; k < rows.size(); k++) {
-            Round &x = R[rows[k]];
-            x.res = O.res[k];
-            x.clock = O.clock.data() + (size_t)k * S; x.back = O.back.data() + (size_t)k * S; x.heads = O.heads.data() + (size_t)k * S;
-        }
         return HM_OK;
+    }
+    // round x reads row j of class c's results
+    void point_round(Round &x, uint32_t c, uint32_t j) {
+        const ClsOut &O = co[c];
+        const size_t at = (size_t)j * STRIDES[c];
+        x.res = O.res[j];
+        x.clock = O.clock.data() + at; x.back = O.back.data() + at; x.heads = O.heads.data() + at;
+    }
+    // Class c's gathered batch in flight (a fork's, a merge's) as its rounds' rows, then the wait.  What a
+    // decode would have handed each round: the gathered change rows and the op map come back; the op rows
+    // through the map from the source's own host copy of its log where the docset keeps one (the per-op
+    // patch modes), from the device otherwise; the per-op tables through the map.  Dep rows are not needed.
+    // The hook says what differs: source(i), the document request i gathered from; rename / actor, host op
+    // rows and an op's actor id into the round's id spaces (false / HM_NONE: outside them); rest, what else
+    // the round's document takes over; PARALLEL, rows on host threads (else in row order, ending at the
+    // first bad one); the error texts.
+    template <typename H> int take_gathered(uint32_t c, const H &h) {
+        const std::vector<uint32_t> &rows = by_cls[c];
+        const bool host_ops = ds->patches && ds->op_diffs;
+        std::vector<hm_doc_row> gd;
+        std::vector<hm_change_row> gc;
+        std::vector<hm_op_row> go;
+        std::vector<uint32_t> gl;
+        int rc = hm_store_fork_rows(ds->stores[c], co[c].id, gd, gc, host_ops ? nullptr : &go, gl);
+        if (rc || (rc = wait_class(c, (uint32_t)rows.size()))) return rc;
+        auto row = [&](uint32_t j) -> const char * {             // (what is wrong with row j, or nullptr)
+            const uint32_t i = rows[j];
+            Round &x = R[i];
+            DocSt &d = ds->doc(x.doc);
+            const DocSt &p = h.source(i);
+            const hm_doc_row &r = gd[j];
+            if ((uint64_t)r.change_off + r.n_changes > gc.size() || (uint64_t)r.op_off + r.n_ops > gl.size() ||
+                (!host_ops && (uint64_t)r.op_off + r.n_ops > go.size()))
+                return H::BAD_ROWS;
+            x.ch.assign(gc.begin() + r.change_off, gc.begin() + r.change_off + r.n_changes);
+            for (hm_change_row &cr : x.ch) { cr.dep_off -= r.dep_off; cr.op_first -= r.op_off; }
+            const uint32_t *log = gl.data() + r.op_off;
+            if (!host_ops) x.op.assign(go.begin() + r.op_off, go.begin() + r.op_off + r.n_ops);
+            else {
+                x.op.resize(r.n_ops);
+                for (uint32_t q = 0; q < r.n_ops; q++) { if (log[q] >= p.oplog.size()) return H::BAD_OPS; x.op[q] = p.oplog[log[q]]; }
+                if (!h.rename(i, x.op)) return H::BAD_IDS;
+            }
+            if (d.op_actor.empty()) { d.op_actor.reserve(r.n_ops); d.op_dt.reserve(r.n_ops); }
+            for (uint32_t q = 0; q < r.n_ops; q++) {
+                const uint32_t a = log[q] < p.op_actor.size() && log[q] < p.op_dt.size() ? h.actor(i, p.op_actor[log[q]]) : HM_NONE;
+                if (a == HM_NONE) return H::BAD_OPS;
+                d.op_actor.push_back((uint16_t)a); d.op_dt.push_back(p.op_dt[log[q]]);
+            }
+            h.rest(i, x, d);
+            point_round(x, c, j);
+            return nullptr;
+        };
+        std::atomic<const char *> bad{nullptr};
+        try {
+            par_for((uint32_t)rows.size(), H::PARALLEL ? T : 1u, [&](uint32_t lo, uint32_t hi, uint32_t) {
+                for (uint32_t j = lo; j < hi && !bad; j++)
+                    if (const char *w = row(j)) bad = w;
+            });
+        } catch (...) { return hm_engine_fail(ds->e, HM_ERR_NOMEM, H::NOMEM); }
+        return bad ? hm_engine_fail(ds->e, HM_ERR_DEVICE, bad) : HM_OK;
     }
     void release() {
         for (uint32_t c = 0; c < N_CLASS; c++) {
@@ -1943,8 +2007,104 @@ int finish(Call &c, hm_text *out) {
     return HM_OK;
 }
 
+// ---------------- what the host queries over many documents share ----------------
+// the request's documents exist (and, with entry_off, its entry ranges do not decrease)
+int check_request(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off = nullptr) {
+    const uint32_t nd = ds->n_docs.load();
+    for (uint32_t i = 0; i < n; i++) {
+        if (docs[i] >= nd) return hm_engine_fail(ds->e, HM_ERR_INVALID, "bad docset document");
+        if (entry_off && entry_off[i + 1] < entry_off[i]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "entry_off must not decrease");
+    }
+    return HM_OK;
+}
+
+// the request's documents that live in class c: their places in docs[0..n) and their store handles
+void class_docs(hm_docset *ds, uint32_t c, uint32_t n, const uint32_t *docs, std::vector<uint32_t> &idx, std::vector<uint32_t> &hs) {
+    for (uint32_t i = 0; i < n; i++) {
+        const DocSt &d = ds->doc(docs[i]);
+        if (d.cls == c) { idx.push_back(i); hs.push_back(d.handle); }
+    }
+}
+
+// a clock entry's seq (a JS number) as the stores' u32
+uint32_t seq_u32(double v) { return !(v > 0) ? 0u : v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v; }
+
+// the per-document texts as one JSON array
+hm_text *json_array(const std::vector<std::string> &js) {
+    std::unique_ptr<hm_text> t(new hm_text());
+    t->s = "[";
+    for (size_t i = 0; i < js.size(); i++) { if (i) t->s += ','; t->s += js[i]; }
+    t->s += ']';
+    return t.release();
+}
+
+// what a request about a document's past selects by: a history length, or a clock row [a_stride], per request
+struct Selector {
+    std::vector<uint32_t> v;
+    bool by_len = false;
+    const uint32_t *lens() const { return by_len ? v.data() : nullptr; }
+    const uint32_t *rows() const { return by_len ? nullptr : v.data(); }
+};
+
+// The clocks of a call's requests as the C ABI hands them over (request i's entries are entry_off[i] ..
+// entry_off[i + 1]; entry e's actor id is actor_ids[actor_off[e] .. actor_off[e + 1]), its seq seqs[e]),
+// and the one place that reads them against a document.
+struct Clocks {
+    hm_docset *ds;
+    const uint32_t *entry_off;
+    const char *actor_ids;
+    const uint32_t *actor_off;
+    const double *seqs;
+    int check(uint32_t i) const { return each(i, nullptr, [](uint32_t, uint32_t) {}, [](uint32_t) {}); }
+    // request i's entries in listed order: known(rank, seq) for an actor d has seen, unknown(seq) for any
+    // other (without d: the entries' lengths are checked, nothing more)
+    template <typename K, typename U> int each(uint32_t i, const DocSt *d, K &&known, U &&unknown) const {
+        for (uint32_t e = entry_off[i]; e < entry_off[i + 1]; e++) {
+            if (actor_off[e + 1] < actor_off[e]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease");
+            if (!d) continue;
+            const uint32_t a = d->actors.find(actor_ids + actor_off[e], actor_off[e + 1] - actor_off[e], 0);
+            if (a == HM_NONE || a >= d->rank_of.size()) unknown(seq_u32(seqs[e]));
+            else known(d->rank_of[a], seq_u32(seqs[e]));
+        }
+        return HM_OK;
+    }
+    // as a dense row[S] (zeroed by the caller): ranks from S on are dropped, a rank's later entry wins;
+    // order[S] (HM_NONE by the caller, optional): the ranks in first-listed order
+    int dense(uint32_t i, const DocSt &d, uint32_t S, uint32_t *row, uint32_t *order = nullptr) const {
+        return each(i, &d, [&](uint32_t r, uint32_t q) {
+            if (r >= S) return;
+            row[r] = q;
+            uint32_t *at = order ? std::find_if(order, order + S, [r](uint32_t o) { return o == r || o == HM_NONE; }) : nullptr;
+            if (at && at != order + S) *at = r;
+        }, [](uint32_t) {});
+    }
+    // as a sparse (rank, seq) list, appended.  With `ready`: an actor never seen with a seq above 0 is a
+    // change d has not applied — the request is then not ready and appends nothing.
+    int sparse(uint32_t i, const DocSt &d, std::vector<uint16_t> &act, std::vector<uint32_t> &seq, bool *ready = nullptr) const {
+        const size_t keep = act.size();
+        bool all = true;
+        const int rc = each(i, &d, [&](uint32_t r, uint32_t q) { act.push_back((uint16_t)r); seq.push_back(q); },
+                            [&](uint32_t q) { all = all && q == 0u; });
+        if (ready && !(*ready = all)) { act.resize(keep); seq.resize(keep); }
+        return rc;
+    }
+    // the selector of a class's requests idx[] (places in docs[] / hist_len[]) at stride S: the history
+    // lengths, or each request's clock as a dense row (and, with `order`, its order row)
+    int select(const uint32_t *docs, const uint32_t *hist_len, const std::vector<uint32_t> &idx, uint32_t S, Selector &sel,
+               std::vector<uint32_t> *order = nullptr) const {
+        sel.by_len = hist_len != nullptr;
+        sel.v.assign(hist_len ? idx.size() : idx.size() * (size_t)S, 0u);
+        if (order && !hist_len) order->assign(idx.size() * (size_t)S, HM_NONE);
+        int rc = HM_OK;
+        for (size_t j = 0; j < idx.size() && !rc; j++) {
+            if (hist_len) sel.v[j] = hist_len[idx[j]];
+            else rc = dense(idx[j], ds->doc(docs[idx[j]]), S, sel.v.data() + j * S, order ? order->data() + j * S : nullptr);
+        }
+        return rc;
+    }
+};
+
 // ---------------- fork ----------------
-uint32_t seq_u32(double v);
 // The new document d as its parent p names things: the interners and rank tables (the gathered rows
 // keep the parent's ranks, object and register ids), an empty log.
 void clone_names(DocSt &d, const DocSt &p) {
@@ -1952,6 +2112,31 @@ void clone_names(DocSt &d, const DocSt &p) {
     d.actors = p.actors; d.objs = p.objs; d.regs = p.regs; d.strs = p.strs;
     d.rank_of = p.rank_of; d.by_rank = p.by_rank;
 }
+
+// Call::take_gathered for a fork: the new document names things as its parent does (ids are copied) and
+// takes over the content table of the selected (actor, seq)
+struct ForkHook {
+    hm_docset *ds;
+    const uint32_t *parents;
+    static constexpr bool PARALLEL = true;
+    static constexpr const char *BAD_ROWS = "a fork's rows outside the gathered tables or its parent's log", *BAD_OPS = BAD_ROWS,
+                                *BAD_IDS = BAD_ROWS, *NOMEM = "out of memory in hm_docset_fork";
+    const DocSt &source(uint32_t i) const { return ds->doc(parents[i]); }
+    bool rename(uint32_t, std::vector<hm_op_row> &) const { return true; }
+    uint32_t actor(uint32_t, uint16_t a) const { return a; }
+    void rest(uint32_t i, const Round &x, DocSt &d) const {
+        const DocSt &p = source(i);
+        std::unordered_set<uint64_t> keys;
+        for (const hm_change_row &cr : x.ch)
+            if (cr.actor < p.by_rank.size()) keys.insert(((uint64_t)p.by_rank[cr.actor] << 32) | cr.seq);
+        for (const DocSt::CE &e : p.cents)
+            if (keys.count(e.key)) d.cents.push_back({e.key, e.h, e.cid, HM_NONE});
+        d.n_content = p.n_content;
+        size_t cap = 64;
+        while ((d.cents.size() + 1) * 2 > cap) cap *= 2;
+        d.crehash(cap);
+    }
+};
 
 // hm_docset_fork: the new documents first + i are rounds of one Call whose rows come from the stores'
 // fork batches instead of a decode — a parent not placed yet gives a round without blocks — and whose
@@ -1963,6 +2148,7 @@ int fork_docs(hm_docset *ds, uint32_t n, const uint32_t *parents, const uint32_t
     Call c{ds, nullptr, nullptr, no_blocks.data(), nd.data(), n};
     c.t0 = std::chrono::steady_clock::now();
     c.R.resize(n);
+    const Clocks clocks{ds, entry_off, actor_ids, actor_off, seqs};
     std::vector<uint32_t> forks[N_CLASS];
     ClsOut plain;                                            // the batch of the rounds without blocks
     int rc;
@@ -2010,95 +2196,20 @@ int fork_docs(hm_docset *ds, uint32_t n, const uint32_t *parents, const uint32_t
         const auto &rows = c.by_cls[k];
         const uint32_t S = STRIDES[k], m = (uint32_t)rows.size();
         hm_store *st = ds->stores[k];
-        std::vector<uint32_t> fh, src(m), sel, ord;
+        std::vector<uint32_t> fh, src(m), ord;
+        Selector sel;
         if ((rc = c.take_handles(k, st, m, fh))) return c.fail(rc);
-        if (hist_len) sel.resize(m); else { sel.assign((size_t)m * S, 0u); ord.assign((size_t)m * S, HM_NONE); }
         for (uint32_t j = 0; j < m; j++) {
-            const uint32_t i = rows[j];
-            Round &x = c.R[i];
-            const DocSt &p = ds->doc(parents[i]);
+            Round &x = c.R[rows[j]];
             x.handle = fh[j]; x.fresh = true; x.row = j;
-            src[j] = p.handle;
-            if (hist_len) { sel[j] = hist_len[i]; continue; }
-            uint32_t *row = sel.data() + (size_t)j * S, *orow = ord.data() + (size_t)j * S, listed = 0;
-            for (uint32_t e = entry_off[i]; e < entry_off[i + 1]; e++) {
-                if (actor_off[e + 1] < actor_off[e]) return c.fail(hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease"));
-                const uint32_t a = p.actors.find(actor_ids + actor_off[e], actor_off[e + 1] - actor_off[e], 0);
-                if (a == HM_NONE || a >= p.rank_of.size() || p.rank_of[a] >= S) continue;   // (an actor the parent has never seen)
-                const uint32_t r = p.rank_of[a];
-                bool again = false;
-                for (uint32_t q = 0; q < listed && !again; q++) again = orow[q] == r;
-                if (!again) orow[listed++] = r;
-                row[r] = seq_u32(seqs[e]);
-            }
+            src[j] = ds->doc(parents[rows[j]]).handle;
         }
+        if ((rc = clocks.select(parents, hist_len, rows, S, sel, &ord))) return c.fail(rc);
         ClsOut &O = c.co[k];
-        if ((rc = hm_store_fork_submit(st, m, src.data(), hist_len ? sel.data() : nullptr, hist_len ? nullptr : sel.data(),
-                                       hist_len ? nullptr : ord.data(), fh.data(), 0u, &O.id)))
+        if ((rc = hm_store_fork_submit(st, m, src.data(), sel.lens(), sel.rows(), sel.by_len ? nullptr : ord.data(), fh.data(), 0u, &O.id)))
             return c.fail(rc);
         O.sub = true;
-        // what a decode would have handed this round: the gathered change rows and the op map come
-        // back; the op rows through the map from the parent's own copy of its log where the docset
-        // keeps one (the per-op patch modes), and from the device otherwise.  Dep rows are not needed.
-        const bool host_ops = ds->patches && ds->op_diffs;
-        std::vector<hm_doc_row> gd;
-        std::vector<hm_change_row> gc;
-        std::vector<hm_op_row> go;
-        std::vector<uint32_t> gl;
-        if ((rc = hm_store_fork_rows(st, O.id, gd, gc, host_ops ? nullptr : &go, gl))) return c.fail(rc);
-        O.res.resize(m); O.clock.resize((size_t)m * S); O.back.resize((size_t)m * S); O.heads.resize((size_t)m * S);
-        if ((rc = hm_batch_wait(st, O.id, O.res.data(), O.clock.data(), O.back.data(), O.heads.data()))) return c.fail(rc);
-        O.sub = false;
-        O.done = true;
-        uint32_t r3[3] = {0, 0, 0};
-        if (hm_store_last_routing(st, r3) == HM_OK)
-            for (int q = 0; q < 3; q++) c.call_routing[q] += r3[q];
-        std::atomic<bool> outside{false};
-        try {
-        par_for(m, c.T, [&](uint32_t j_lo, uint32_t j_hi, uint32_t) {
-        for (uint32_t j = j_lo; j < j_hi; j++) {
-            const uint32_t i = rows[j];
-            Round &x = c.R[i];
-            DocSt &d = ds->doc(nd[i]);
-            const DocSt &p = ds->doc(parents[i]);
-            const hm_doc_row &r = gd[j];
-            if ((uint64_t)r.change_off + r.n_changes > gc.size() || (uint64_t)r.op_off + r.n_ops > gl.size()) { outside = true; continue; }
-            x.ch.assign(gc.begin() + r.change_off, gc.begin() + r.change_off + r.n_changes);
-            for (hm_change_row &cr : x.ch) { cr.dep_off -= r.dep_off; cr.op_first -= r.op_off; }
-            if (!host_ops) x.op.assign(go.begin() + r.op_off, go.begin() + r.op_off + r.n_ops);
-            else {
-                x.op.resize(r.n_ops);
-                for (uint32_t q = 0; q < r.n_ops; q++) {
-                    const uint32_t lo = gl[r.op_off + q];
-                    if (lo >= p.oplog.size()) { outside = true; break; }
-                    x.op[q] = p.oplog[lo];
-                }
-            }
-            // the per-op tables through the op map, the content table of the selected (actor, seq)
-            d.op_actor.reserve(r.n_ops); d.op_dt.reserve(r.n_ops);
-            for (uint32_t q = 0; q < r.n_ops; q++) {
-                const uint32_t lo = gl[r.op_off + q];
-                if (lo >= p.op_actor.size() || lo >= p.op_dt.size()) { outside = true; break; }
-                d.op_actor.push_back(p.op_actor[lo]);
-                d.op_dt.push_back(p.op_dt[lo]);
-            }
-            std::unordered_set<uint64_t> keys;
-            for (const hm_change_row &cr : x.ch)
-                if (cr.actor < p.by_rank.size()) keys.insert(((uint64_t)p.by_rank[cr.actor] << 32) | cr.seq);
-            for (const DocSt::CE &e : p.cents)
-                if (keys.count(e.key)) d.cents.push_back({e.key, e.h, e.cid, HM_NONE});
-            d.n_content = p.n_content;
-            size_t cap = 64;
-            while ((d.cents.size() + 1) * 2 > cap) cap *= 2;
-            d.crehash(cap);
-            x.res = O.res[j];
-            x.clock = O.clock.data() + (size_t)j * S; x.back = O.back.data() + (size_t)j * S; x.heads = O.heads.data() + (size_t)j * S;
-        }
-        });
-        } catch (...) {
-            return c.fail(hm_engine_fail(ds->e, HM_ERR_NOMEM, "out of memory in hm_docset_fork"));
-        }
-        if (outside) return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a fork's rows outside the gathered tables or its parent's log"));
+        if ((rc = c.take_gathered(k, ForkHook{ds, parents}))) return c.fail(rc);
     }
     c.mark("fork");
     return finish(c, out);
@@ -2110,7 +2221,7 @@ int fork_docs(hm_docset *ds, uint32_t n, const uint32_t *parents, const uint32_t
 struct MergeReq {
     std::vector<uint32_t> amap;                              // source actor id -> destination actor id
     std::vector<uint32_t> rank, omap, rmap, smap, cmap;      // rank: [source ranks]
-    std::vector<uint32_t> clock, have, order;                // [source ranks]; order: listed ranks
+    std::vector<uint32_t> clock, have, order;                // [source ranks]; order: listed ranks, then HM_NONE
     bool device = false, empty = false;                      // route; empty: the source holds nothing
 };
 
@@ -2157,6 +2268,25 @@ bool rename_rows(const MergeReq &q, std::vector<hm_change_row> &ch, std::vector<
     return ok;
 }
 
+// Call::take_gathered for a merge: the source's ids go through the request's maps (the change rows were
+// renamed on the device)
+struct MergeHook {
+    hm_docset *ds;
+    const uint32_t *src;
+    const MergeReq *Q;
+    static constexpr bool PARALLEL = false;
+    static constexpr const char *BAD_ROWS = "a merge's rows outside the gathered tables", *BAD_OPS = "a merge's ops outside its source's log",
+                                *BAD_IDS = "a merge's ops name an id its source's tables do not hold", *NOMEM = "out of memory in hm_docset_merge_from";
+    const DocSt &source(uint32_t i) const { return ds->doc(src[i]); }
+    bool rename(uint32_t i, std::vector<hm_op_row> &op) const {
+        std::vector<hm_change_row> no_ch;
+        std::vector<hm_dep_row> no_dp;
+        return rename_rows(Q[i], no_ch, no_dp, op);
+    }
+    uint32_t actor(uint32_t i, uint16_t a) const { return a < Q[i].amap.size() ? Q[i].amap[a] : HM_NONE; }
+    void rest(uint32_t, const Round &, DocSt &) const {}
+};
+
 // hm_docset_merge_from: destination dst[i] is handed source src[i]'s applied changes above what it was
 // handed before (its DocBackend.clock) up to the request's clock, actor after actor in the clock's key
 // order.  The destinations are rounds of one Call whose rows come from the stores' merge batches (the
@@ -2167,6 +2297,7 @@ int merge_docs(hm_docset *ds, uint32_t n, const uint32_t *dst, const uint32_t *s
                const char *actor_ids, const uint32_t *actor_off, const double *seqs, hm_text *out) {
     std::vector<uint32_t> no_blocks(n + 1, 0);
     Call c{ds, nullptr, nullptr, no_blocks.data(), dst, n};
+    const Clocks clocks{ds, entry_off, actor_ids, actor_off, seqs};
     int rc = c.validate();
     if (rc) return rc;
     {
@@ -2194,8 +2325,7 @@ int merge_docs(hm_docset *ds, uint32_t n, const uint32_t *dst, const uint32_t *s
     std::vector<std::vector<uint32_t>> backs(n);
     for (uint32_t k = 0; k < N_CLASS; k++) {
         std::vector<uint32_t> idx, hh;
-        for (uint32_t i = 0; i < n; i++)
-            if (ds->doc(dst[i]).cls == k) { idx.push_back(i); hh.push_back(ds->doc(dst[i]).handle); }
+        class_docs(ds, k, n, dst, idx, hh);
         if (idx.empty()) continue;
         const uint32_t Sd = STRIDES[k];
         std::vector<uint32_t> rows(idx.size() * (size_t)Sd);
@@ -2230,14 +2360,8 @@ int merge_docs(hm_docset *ds, uint32_t n, const uint32_t *dst, const uint32_t *s
             q.smap.resize(p.strs.size());
             for (uint32_t s = 0; s < p.strs.size(); s++) q.smap[s] = d.strs.get(p.strs.ptr(s), p.strs.len(s), 0, f);
             // the clock, by actor id in key order (the hand-over order); an id the source never saw is dropped
-            for (uint32_t e = entry_off[i]; e < entry_off[i + 1]; e++) {
-                if (actor_off[e + 1] < actor_off[e]) return c.fail(hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease"));
-                const uint32_t a = p.actors.find(actor_ids + actor_off[e], actor_off[e + 1] - actor_off[e], 0);
-                if (a == HM_NONE || a >= p.rank_of.size()) continue;
-                const uint32_t r = p.rank_of[a];
-                if (std::find(q.order.begin(), q.order.end(), r) == q.order.end()) q.order.push_back(r);
-                q.clock[r] = seq_u32(seqs[e]);
-            }
+            q.order.assign(ns, HM_NONE);
+            if ((rc = clocks.dense(i, p, ns, q.clock.data(), q.order.data()))) return c.fail(rc);
             // have: the destination's DocBackend.clock, in the source's ranks
             if (d.cls != NO_CLASS) {
                 const std::vector<uint32_t> &back = backs[i];
@@ -2298,6 +2422,7 @@ int merge_docs(hm_docset *ds, uint32_t n, const uint32_t *dst, const uint32_t *s
             if (hist[k] >= 0) at[((uint64_t)lc[k].actor << 32) | lc[k].seq] = k;
         std::vector<uint32_t> oplog_at;                        // the gathered ops' source log indices
         for (uint32_t r : q.order) {
+            if (r == HM_NONE) break;
             for (uint64_t sq = (uint64_t)q.have[r] + 1; sq <= q.clock[r]; sq++) {
                 auto it = at.find(((uint64_t)r << 32) | sq);
                 if (it == at.end()) break;                     // (an actor's applied changes are its seqs 1 .. opSet.clock)
@@ -2320,19 +2445,9 @@ int merge_docs(hm_docset *ds, uint32_t n, const uint32_t *dst, const uint32_t *s
             d.op_dt.push_back(p.op_dt[lo_i]);
         }
     }
-    // place the host-route rounds (Call::place, for them alone)
-    for (uint32_t i = 0; i < n; i++) {
-        Round &x = c.R[i];
-        if (x.status != HM_OK || Q[i].device) continue;
-        DocSt &d = ds->doc(x.doc);
-        uint8_t k = class_for(x.n_actors);
-        if (d.cls != NO_CLASS && d.cls > k) k = d.cls;
-        x.cls = k;
-        x.placed = d.cls == NO_CLASS;
-        x.moved = !x.placed && k != d.cls;
-        x.handle = d.handle;
-        c.by_cls[k].push_back(i);
-    }
+    // place the host-route rounds, and merge them
+    for (uint32_t i = 0; i < n; i++)
+        if (c.R[i].status == HM_OK && !Q[i].device) c.place_round(i);
     for (uint32_t k = 0; k < N_CLASS; k++)
         if (!c.by_cls[k].empty() && (rc = c.merge_class(k))) return c.fail(rc);
     // the device route, a merge batch per class
@@ -2378,94 +2493,13 @@ int merge_docs(hm_docset *ds, uint32_t n, const uint32_t *dst, const uint32_t *s
                                              any_remap ? remap.data() : nullptr, &O.id)))
             return c.fail(rc);
         O.sub = true;
-        // what a decode would have handed each round: the renamed change rows and the op map come back;
-        // the op rows through the map from the source's own host copy of its log, renamed here, where
-        // the docset keeps one (the per-op patch modes), and renamed from the device otherwise
-        const bool host_ops = ds->patches && ds->op_diffs;
-        std::vector<hm_doc_row> gd;
-        std::vector<hm_change_row> gc;
-        std::vector<hm_op_row> go;
-        std::vector<uint32_t> gl;
-        if ((rc = hm_store_fork_rows(st, O.id, gd, gc, host_ops ? nullptr : &go, gl))) return c.fail(rc);
-        O.res.resize(m); O.clock.resize((size_t)m * S); O.back.resize((size_t)m * S); O.heads.resize((size_t)m * S);
-        if ((rc = hm_batch_wait(st, O.id, O.res.data(), O.clock.data(), O.back.data(), O.heads.data()))) return c.fail(rc);
-        O.sub = false;
-        O.done = true;
-        uint32_t r3[3] = {0, 0, 0};
-        if (hm_store_last_routing(st, r3) == HM_OK)
-            for (int t = 0; t < 3; t++) c.call_routing[t] += r3[t];
-        for (uint32_t j = 0; j < m; j++) {
-            const uint32_t i = rows[j];
-            Round &x = c.R[i];
-            const MergeReq &q = Q[i];
-            DocSt &d = ds->doc(dst[i]);
-            const DocSt &p = ds->doc(src[i]);
-            const hm_doc_row &r = gd[j];
-            if ((uint64_t)r.change_off + r.n_changes > gc.size() || (uint64_t)r.op_off + r.n_ops > gl.size() ||
-                (!host_ops && (uint64_t)r.op_off + r.n_ops > go.size()))
-                return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a merge's rows outside the gathered tables"));
-            x.ch.assign(gc.begin() + r.change_off, gc.begin() + r.change_off + r.n_changes);
-            for (hm_change_row &cr : x.ch) { cr.dep_off -= r.dep_off; cr.op_first -= r.op_off; }
-            if (!host_ops) x.op.assign(go.begin() + r.op_off, go.begin() + r.op_off + r.n_ops);
-            else {
-                x.op.resize(r.n_ops);
-                for (uint32_t t = 0; t < r.n_ops; t++) {
-                    const uint32_t lo = gl[r.op_off + t];
-                    if (lo >= p.oplog.size()) return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a merge's ops outside its source's log"));
-                    x.op[t] = p.oplog[lo];
-                }
-                std::vector<hm_change_row> no_ch;
-                std::vector<hm_dep_row> no_dp;
-                if (!rename_rows(q, no_ch, no_dp, x.op))
-                    return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a merge's ops name an id its source's tables do not hold"));
-            }
-            for (uint32_t t = 0; t < r.n_ops; t++) {
-                const uint32_t lo = gl[r.op_off + t];
-                if (lo >= p.op_actor.size() || p.op_actor[lo] >= q.amap.size())
-                    return c.fail(hm_engine_fail(ds->e, HM_ERR_DEVICE, "a merge's ops outside its source's log"));
-                d.op_actor.push_back((uint16_t)q.amap[p.op_actor[lo]]);
-                d.op_dt.push_back(p.op_dt[lo]);
-            }
-            x.res = O.res[j];
-            x.clock = O.clock.data() + (size_t)j * S; x.back = O.back.data() + (size_t)j * S; x.heads = O.heads.data() + (size_t)j * S;
-        }
+        if ((rc = c.take_gathered(k, MergeHook{ds, src, Q.data()}))) return c.fail(rc);
     }
     } catch (...) {
         return c.fail(hm_engine_fail(ds->e, HM_ERR_NOMEM, "out of memory in hm_docset_merge_from"));
     }
     c.mark("merge_from");
     return finish(c, out);
-}
-
-// ---------------- what the host queries over many documents share ----------------
-// the request's documents exist (and, with entry_off, its entry ranges do not decrease)
-int check_request(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint32_t *entry_off = nullptr) {
-    const uint32_t nd = ds->n_docs.load();
-    for (uint32_t i = 0; i < n; i++) {
-        if (docs[i] >= nd) return hm_engine_fail(ds->e, HM_ERR_INVALID, "bad docset document");
-        if (entry_off && entry_off[i + 1] < entry_off[i]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "entry_off must not decrease");
-    }
-    return HM_OK;
-}
-
-// the request's documents that live in class c: their places in docs[0..n) and their store handles
-void class_docs(hm_docset *ds, uint32_t c, uint32_t n, const uint32_t *docs, std::vector<uint32_t> &idx, std::vector<uint32_t> &hs) {
-    for (uint32_t i = 0; i < n; i++) {
-        const DocSt &d = ds->doc(docs[i]);
-        if (d.cls == c) { idx.push_back(i); hs.push_back(d.handle); }
-    }
-}
-
-// a clock entry's seq (a JS number) as the stores' u32
-uint32_t seq_u32(double v) { return !(v > 0) ? 0u : v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v; }
-
-// the per-document texts as one JSON array
-hm_text *json_array(const std::vector<std::string> &js) {
-    std::unique_ptr<hm_text> t(new hm_text());
-    t->s = "[";
-    for (size_t i = 0; i < js.size(); i++) { if (i) t->s += ','; t->s += js[i]; }
-    t->s += ']';
-    return t.release();
 }
 
 // hm_docset_materialize: one class's result tables, sized by the store once its count pass has
@@ -2730,24 +2764,17 @@ int hm_docset_missing_changes(hm_docset *ds, uint32_t n, const uint32_t *docs, c
         int rc = check_request(ds, n, docs, entry_off);
         if (rc) return rc;
         if (n && entry_off[n] - entry_off[0] && (!actor_ids || !actor_off || !seqs)) return HM_ERR_INVALID;
+        const Clocks clocks{ds, entry_off, actor_ids, actor_off, seqs};
         std::vector<std::string> js(n, "[]");                                    // (a document not placed yet)
         for (uint32_t c = 0; c < N_CLASS; c++) {
             std::vector<uint32_t> idx, hs, off(1, 0), eseq;
             std::vector<uint16_t> eact;
-            for (uint32_t i = 0; i < n; i++) {
-                const DocSt &d = ds->doc(docs[i]);
-                if (d.cls != c) continue;
-                idx.push_back(i); hs.push_back(d.handle);
-                for (uint32_t k = entry_off[i]; k < entry_off[i + 1]; k++) {
-                    if (actor_off[k + 1] < actor_off[k]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease");
-                    const uint32_t a = d.actors.find(actor_ids + actor_off[k], actor_off[k + 1] - actor_off[k], 0);
-                    if (a == HM_NONE || a >= d.rank_of.size()) continue;       // (an actor the document has never seen)
-                    eact.push_back(d.rank_of[a]);
-                    eseq.push_back(seq_u32(seqs[k]));
-                }
+            class_docs(ds, c, n, docs, idx, hs);
+            if (idx.empty()) continue;
+            for (uint32_t i : idx) {                             // (an actor the document has never seen is dropped)
+                if ((rc = clocks.sparse(i, ds->doc(docs[i]), eact, eseq))) return rc;
                 off.push_back((uint32_t)eact.size());
             }
-            if (idx.empty()) continue;
             const uint32_t k = (uint32_t)idx.size();
             std::vector<uint32_t> rng(2 * (size_t)k), log;
             uint32_t total = 0;
@@ -2787,9 +2814,9 @@ int hm_docset_fields(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint
             if (field_off[i + 1] < field_off[i]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "field_off must not decrease");
         if (n && entry_off[n] - entry_off[0] && (!actor_ids || !actor_off || !seqs)) return HM_ERR_INVALID;
         if (n && field_off[n] - field_off[0] && (!names || !name_off)) return HM_ERR_INVALID;
+        const Clocks clocks{ds, entry_off, actor_ids, actor_off, seqs};
         for (uint32_t i = 0; i < n; i++) {
-            for (uint32_t k = entry_off[i]; k < entry_off[i + 1]; k++)
-                if (actor_off[k + 1] < actor_off[k]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease");
+            if ((rc = clocks.check(i))) return rc;
             for (uint32_t f = 2 * field_off[i]; f < 2 * field_off[i + 1]; f++)
                 if (name_off[f + 1] < name_off[f]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "name_off must not decrease");
         }
@@ -2812,16 +2839,9 @@ int hm_docset_fields(hm_docset *ds, uint32_t n, const uint32_t *docs, const uint
             for (uint32_t i = 0; i < n; i++) {
                 const DocSt &d = ds->doc(docs[i]);
                 if (d.cls != c) continue;
-                const size_t e_keep = eact.size();
                 bool ready = true;
-                for (uint32_t k = entry_off[i]; k < entry_off[i + 1]; k++) {
-                    const uint32_t a = d.actors.find(actor_ids + actor_off[k], actor_off[k + 1] - actor_off[k], 0);
-                    const uint32_t q = seq_u32(seqs[k]);
-                    if (a == HM_NONE || a >= d.rank_of.size()) { ready = ready && q == 0u; continue; }   // (an actor never seen)
-                    eact.push_back(d.rank_of[a]);
-                    eseq.push_back(q);
-                }
-                if (!ready) { eact.resize(e_keep); eseq.resize(e_keep); js[i] = plain(i, false); continue; }
+                if ((rc = clocks.sparse(i, d, eact, eseq, &ready))) return rc;
+                if (!ready) { js[i] = plain(i, false); continue; }
                 idx.push_back(i); hs.push_back(d.handle);
                 eoff.push_back((uint32_t)eact.size());
                 for (uint32_t f = field_off[i]; f < field_off[i + 1]; f++) {
@@ -2902,6 +2922,7 @@ int hm_docset_materialize(hm_docset *ds, uint32_t n, const uint32_t *docs, const
         int rc = check_request(ds, n, docs, entry_off);
         if (rc) return rc;
         if (entry_off && n && entry_off[n] - entry_off[0] && (!actor_ids || !actor_off || !seqs)) return HM_ERR_INVALID;
+        const Clocks clocks{ds, entry_off, actor_ids, actor_off, seqs};
         std::vector<std::string> js(n);
         for (uint32_t i = 0; i < n; i++) {                       // (a document not placed yet: Backend.init())
             DocSt &d = ds->doc(docs[i]);
@@ -2913,27 +2934,15 @@ int hm_docset_materialize(hm_docset *ds, uint32_t n, const uint32_t *docs, const
         }
         for (uint32_t c = 0; c < N_CLASS; c++) {
             const uint32_t S = STRIDES[c];
-            std::vector<uint32_t> idx, hs, sel;
-            for (uint32_t i = 0; i < n; i++) {
-                const DocSt &d = ds->doc(docs[i]);
-                if (d.cls != c) continue;
-                idx.push_back(i); hs.push_back(d.handle);
-                if (hist_len) { sel.push_back(hist_len[i]); continue; }
-                sel.resize(sel.size() + S, 0u);
-                uint32_t *row = sel.data() + sel.size() - S;
-                for (uint32_t k = entry_off[i]; k < entry_off[i + 1]; k++) {
-                    if (actor_off[k + 1] < actor_off[k]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease");
-                    const uint32_t a = d.actors.find(actor_ids + actor_off[k], actor_off[k + 1] - actor_off[k], 0);
-                    if (a == HM_NONE || a >= d.rank_of.size() || d.rank_of[a] >= S) continue;   // (an actor the document has never seen)
-                    row[d.rank_of[a]] = seq_u32(seqs[k]);
-                }
-            }
+            std::vector<uint32_t> idx, hs;
+            Selector sel;
+            class_docs(ds, c, n, docs, idx, hs);
             if (idx.empty()) continue;
+            if ((rc = clocks.select(docs, hist_len, idx, S, sel))) return rc;
             const uint32_t k = (uint32_t)idx.size();
-            const uint32_t *hl = hist_len ? sel.data() : nullptr, *rows = hist_len ? nullptr : sel.data();
             PastTables T;                                        // (one count pass per class)
             T.k = k; T.S = S;
-            if ((rc = hm_store_materialize_sized(ds->stores[c], k, hs.data(), hl, rows, PastTables::alloc, &T, nullptr))) return rc;
+            if ((rc = hm_store_materialize_sized(ds->stores[c], k, hs.data(), sel.lens(), sel.rows(), PastTables::alloc, &T, nullptr))) return rc;
             std::vector<uint8_t> created;
             for (uint32_t j = 0; j < k; j++) {
                 DocSt &d = ds->doc(docs[idx[j]]);
@@ -3056,6 +3065,7 @@ static int materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs, co
         if (entry_off && n && entry_off[n] - entry_off[0] && (!actor_ids || !actor_off || !seqs)) return HM_ERR_INVALID;
         if (n && !(ds->patches && ds->op_diffs))
             return hm_engine_fail(ds->e, HM_ERR_UNSUPPORTED, "hm_docset_materialize_patch renders per-op diffs: not with HM_DOCSET_NO_PATCHES / HM_DOCSET_NET_DIFFS");
+        const Clocks clocks{ds, entry_off, actor_ids, actor_off, seqs};
         static const char TAIL[] = ",\"canUndo\":false,\"canRedo\":false,\"diffs\":[";
         std::vector<std::string> js(n);
         for (uint32_t i = 0; i < n; i++)                         // (a document not placed yet: Backend.init())
@@ -3064,39 +3074,28 @@ static int materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs, co
                         "\"patch\":{\"clock\":{},\"deps\":{}" + TAIL + "]}}";
         for (uint32_t c = 0; c < N_CLASS; c++) {
             const uint32_t S = STRIDES[c];
-            std::vector<uint32_t> idx, hs, hl;                   // (hl: the history lengths, or the clock rows)
-            for (uint32_t i = 0; i < n; i++) {
-                const DocSt &d = ds->doc(docs[i]);
-                if (d.cls != c) continue;
-                idx.push_back(i); hs.push_back(d.handle);
-                if (hist_len) { hl.push_back(hist_len[i]); continue; }
-                hl.resize(hl.size() + S, 0u);
-                uint32_t *row = hl.data() + hl.size() - S;
-                for (uint32_t k = entry_off[i]; k < entry_off[i + 1]; k++) {
-                    if (actor_off[k + 1] < actor_off[k]) return hm_engine_fail(ds->e, HM_ERR_INVALID, "actor_off must not decrease");
-                    const uint32_t a = d.actors.find(actor_ids + actor_off[k], actor_off[k + 1] - actor_off[k], 0);
-                    if (a == HM_NONE || a >= d.rank_of.size() || d.rank_of[a] >= S) continue;   // (an actor the document has never seen)
-                    row[d.rank_of[a]] = seq_u32(seqs[k]);
-                }
-            }
+            std::vector<uint32_t> idx, hs;
+            Selector sel;
+            class_docs(ds, c, n, docs, idx, hs);
             if (idx.empty()) continue;
-            const uint32_t k = (uint32_t)idx.size();
+            if ((rc = clocks.select(docs, hist_len, idx, S, sel))) return rc;
+            const uint32_t k = (uint32_t)idx.size(), *hl = sel.v.data();       // (hl: the history lengths, or the clock rows)
             PastTables T;                                        // the selection's clock and deps: its merge from Backend.init()
             T.k = k; T.S = S;
-            if ((rc = hm_store_materialize_sized(ds->stores[c], k, hs.data(), hist_len ? hl.data() : nullptr, hist_len ? nullptr : hl.data(),
+            if ((rc = hm_store_materialize_sized(ds->stores[c], k, hs.data(), sel.lens(), sel.rows(),
                                                  PastTables::alloc_heads, &T, nullptr))) return rc;
             // the diffs: what each op of the selection did, from the resident tables
             const std::vector<uint32_t> from(hist_len ? k : 0u, 0u);
             uint64_t tot[2] = {0, 0};
-            if ((rc = hist_len ? hm_store_op_diff_sizes_ex(ds->stores[c], k, hs.data(), from.data(), hl.data(), nullptr, nullptr, tot, opts)
-                               : hm_store_op_diff_sizes_at(ds->stores[c], k, hs.data(), hl.data(), nullptr, nullptr, tot, opts))) return rc;
+            if ((rc = hist_len ? hm_store_op_diff_sizes_ex(ds->stores[c], k, hs.data(), from.data(), hl, nullptr, nullptr, tot, opts)
+                               : hm_store_op_diff_sizes_at(ds->stores[c], k, hs.data(), hl, nullptr, nullptr, tot, opts))) return rc;
             if (tot[0] > 0xFFFFFFFFull || tot[1] > 0xFFFFFFFFull) return hm_engine_fail(ds->e, HM_ERR_NOMEM, "a call's rows stay below 2^32");
             std::vector<hm_op_diff> rows(tot[0] + 1);
             std::vector<hm_surv_result> surv(tot[1] + 1);
             std::vector<uint32_t> range(2 * (size_t)k), flags(k), index(tot[0] + 1);   // (index: element rows, HM_ODF_LISTS)
             hm_op_diff_out po = {(uint32_t)tot[0], (uint32_t)tot[1], rows.data(), surv.data(), range.data(), flags.data()};
-            if ((rc = hist_len ? hm_store_op_diffs_ex(ds->stores[c], k, hs.data(), from.data(), hl.data(), &po, index.data(), nullptr, opts)
-                               : hm_store_op_diffs_at(ds->stores[c], k, hs.data(), hl.data(), &po, index.data(), nullptr, opts))) return rc;
+            if ((rc = hist_len ? hm_store_op_diffs_ex(ds->stores[c], k, hs.data(), from.data(), hl, &po, index.data(), nullptr, opts)
+                               : hm_store_op_diffs_at(ds->stores[c], k, hs.data(), hl, &po, index.data(), nullptr, opts))) return rc;
             for (uint32_t j = 0; j < k; j++) {
                 DocSt &d = ds->doc(docs[idx[j]]);
                 if (!d.ready) d.setup();

@@ -1344,6 +1344,45 @@ int hm_store_materialize(hm_store *s, uint32_t n, const uint32_t *doc_handles, c
                                       [](void *ctx, const uint64_t *) { return (const hm_past_out *)ctx; }, (void *)out, out_totals);
 }
 
+// The gathered batch of a count pass, placed in the store's own buffer: the slots [docs][changes][deps]
+// [ops][change_log][op_log], the caller's n_extra slots behind them (one with a host source is copied up
+// first), the fill.  sz / o: every slot's bytes and place in s->past; b: tables, counts and a_stride.
+struct Gathered {
+    size_t sz[17], o[17];
+    hm_batch b;
+};
+
+static int place_gathered(hm_store *s, PastArgs &P, uint32_t n, const uint64_t *tot, int n_extra, const size_t *extra_sz,
+                          const void *const *extra_host, Gathered &G) {
+    const uint64_t tc = tot[0], td = tot[1], to = tot[2], tr = tot[3];
+    if (std::max(std::max(tc, td), std::max(to, tr)) > 0xFFFFFFFFull)
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "a call's rows stay below 2^32");
+    hipStream_t st = hm_engine_stream(s->e);
+    const size_t head[6] = {n * sizeof(hm_doc_row), tc * sizeof(hm_change_row), td * sizeof(hm_dep_row), to * sizeof(hm_op_row), tc * 4, to * 4};
+    size_t total = 0;
+    for (int i = 0; i < 6 + n_extra; i++) { G.sz[i] = i < 6 ? head[i] : extra_sz[i - 6]; G.o[i] = total; total += (G.sz[i] + 1 + 255) & ~(size_t)255; }
+    const int rc = ensure_buf(s, s->past, total);
+    if (rc) return rc;
+    uint8_t *bp = s->past.p;
+    for (int i = 6; extra_host && i < 6 + n_extra; i++)
+        if (extra_host[i - 6] && G.sz[i]) SCHK(s, hipMemcpyAsync(bp + G.o[i], extra_host[i - 6], G.sz[i], hipMemcpyHostToDevice, st));
+    P.cap[0] = (uint32_t)tc; P.cap[1] = (uint32_t)td; P.cap[2] = (uint32_t)to; P.cap[3] = (uint32_t)tr;
+    P.out_docs = (hm_doc_row *)(bp + G.o[0]); P.out_changes = (hm_change_row *)(bp + G.o[1]); P.out_deps = (hm_dep_row *)(bp + G.o[2]);
+    P.out_ops = (hm_op_row *)(bp + G.o[3]); P.out_change_log = (uint32_t *)(bp + G.o[4]); P.out_op_log = (uint32_t *)(bp + G.o[5]);
+    SCHK(s, hm_launch_past_fill(P, st));
+    G.b = hm_batch{};
+    G.b.a_stride = s->S; G.b.n_docs = n; G.b.n_changes = (uint32_t)tc; G.b.n_deps = (uint32_t)td; G.b.n_ops = (uint32_t)to;
+    G.b.docs = P.out_docs; G.b.changes = P.out_changes; G.b.deps = P.out_deps; G.b.ops = P.out_ops;
+    return HM_OK;
+}
+
+// the fork (or merge) batch now in flight: what hm_store_fork_rows reads until the wait
+static void note_fork(hm_store *s, uint64_t id, uint32_t n, const uint64_t *tot, const Gathered &G) {
+    s->fork_id = id; s->fork_n = n;
+    for (int i = 0; i < 3; i++) s->fork_rows[i] = (size_t)tot[i];
+    for (int i = 0; i < 6; i++) s->fork_off[i] = G.o[i];
+}
+
 // Fork: count, scan and fill into the store's own buffer, then the device-table submit of those
 // tables to the destinations.  The gathered rows (and the staged destination handles, copied behind
 // them) stay untouched until the wait: every call that would reuse the buffer is refused while the
@@ -1366,38 +1405,22 @@ int hm_store_fork_submit(hm_store *s, uint32_t n, const uint32_t *src_handles, c
         const uint32_t *dst_staged = nullptr;
         int rc = past_count(s, n, src_handles, hist_len, clock_rows, P, &sum, actor_order, dst_handles, &dst_staged);
         if (rc) return rc;
-        const uint64_t tc = sum.totals[0], td = sum.totals[1], to = sum.totals[2], tr = sum.totals[3];
-        if (std::max(std::max(tc, td), std::max(to, tr)) > 0xFFFFFFFFull)
-            return hm_engine_fail(s->e, HM_ERR_NOMEM, "a call's rows stay below 2^32");
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        // [docs][changes][deps][ops][change_log][op_log][destination handles]
-        const size_t sz[7] = {n * sizeof(hm_doc_row), tc * sizeof(hm_change_row), td * sizeof(hm_dep_row), to * sizeof(hm_op_row),
-                              tc * 4, to * 4, (size_t)n * 4};
-        size_t o[7], total = 0;
-        for (int i = 0; i < 7; i++) { o[i] = total; total += al(sz[i] + 1); }
-        if ((rc = ensure_buf(s, s->past, total))) return rc;
-        uint8_t *bp = s->past.p;
-        P.cap[0] = (uint32_t)tc; P.cap[1] = (uint32_t)td; P.cap[2] = (uint32_t)to; P.cap[3] = (uint32_t)tr;
-        P.out_docs = (hm_doc_row *)(bp + o[0]); P.out_changes = (hm_change_row *)(bp + o[1]); P.out_deps = (hm_dep_row *)(bp + o[2]);
-        P.out_ops = (hm_op_row *)(bp + o[3]); P.out_change_log = (uint32_t *)(bp + o[4]); P.out_op_log = (uint32_t *)(bp + o[5]);
+        // [the gathered batch][destination handles]
         // (the fill, the copy and the min-clock kernel below still read the stage buffer — handles, counts,
         // offsets, order rows — when the submit stages its own rows there: they are enqueued first on the
         // same stream, and a stage buffer that has to grow is freed only after ensure_buf has synchronised
         // that stream)
-        SCHK(s, hm_launch_past_fill(P, st));
-        uint32_t *dst_dev = (uint32_t *)(bp + o[6]);
+        const size_t extra[1] = {(size_t)n * 4};
+        Gathered G;
+        if ((rc = place_gathered(s, P, n, sum.totals, 1, extra, nullptr, G))) return rc;
+        uint32_t *dst_dev = (uint32_t *)(s->past.p + G.o[6]);
         SCHK(s, hipMemcpyAsync(dst_dev, dst_staged, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
         // (the destinations passed the check: empty documents, whose minimumClock row no result shows)
         SCHK(s, hm_launch_fork_min_clock(P.src.handles, dst_dev, n, S, s->dm, s->min_clock, flags & HM_FORK_MIN_CLOCK ? 1u : 0u, st));
-        hm_batch b = {};
-        b.a_stride = S; b.n_docs = n;
-        b.n_changes = (uint32_t)tc; b.n_deps = (uint32_t)td; b.n_ops = (uint32_t)to; b.n_regs = (uint32_t)tr;
-        b.docs = P.out_docs; b.changes = P.out_changes; b.deps = P.out_deps; b.ops = P.out_ops;
+        G.b.n_regs = (uint32_t)sum.totals[3];
         uint64_t id = 0;
-        if ((rc = hm_batch_submit_device(s, &b, dst_dev, nullptr, &id))) return rc;
-        s->fork_id = id; s->fork_n = n;
-        s->fork_rows[0] = (size_t)tc; s->fork_rows[1] = (size_t)td; s->fork_rows[2] = (size_t)to;
-        for (int i = 0; i < 6; i++) s->fork_off[i] = o[i];
+        if ((rc = hm_batch_submit_device(s, &G.b, dst_dev, nullptr, &id))) return rc;
+        note_fork(s, id, n, sum.totals, G);
         if (out_batch_id) *out_batch_id = id;
         return HM_OK;
     } catch (...) {
@@ -1439,30 +1462,19 @@ int hm_store_merge_from_submit(hm_store *s, uint32_t n, const uint32_t *src_hand
         int rc = past_count(s, n, src_handles, nullptr, clock_rows, P, &sum, actor_order, dst_handles, &dst_staged, have_rows,
                             maps->totals, &tot_staged);
         if (rc) return rc;
-        const uint64_t tc = sum.totals[0], td = sum.totals[1], to = sum.totals[2], tr = sum.totals[3];
-        if (std::max(std::max(tc, td), std::max(to, tr)) > 0xFFFFFFFFull)
-            return hm_engine_fail(s->e, HM_ERR_NOMEM, "a call's rows stay below 2^32");
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        // [docs][changes][deps][ops][change_log][op_log][destination handles][remap rows][rank rows]
+        // [the gathered batch][destination handles][remap rows][rank rows]
         // [obj_off][obj_map][reg_off][reg_map][str_off][str_map][content_off][content_map]
         const size_t offb = ((size_t)n + 1) * 4;
-        const size_t sz[17] = {n * sizeof(hm_doc_row), tc * sizeof(hm_change_row), td * sizeof(hm_dep_row), to * sizeof(hm_op_row),
-                               tc * 4, to * 4, (size_t)n * 4, dst_actor_remap ? (size_t)n * S : 0, (size_t)n * S * 4,
-                               offb, (size_t)offs[0][n] * 4, offb, (size_t)offs[1][n] * 4,
-                               offs[2] ? offb : 0, offs[2] ? (size_t)offs[2][n] * 4 : 0,
-                               offs[3] ? offb : 0, offs[3] ? (size_t)offs[3][n] * 4 : 0};
-        size_t o[17], total = 0;
-        for (int i = 0; i < 17; i++) { o[i] = total; total += al(sz[i] + 1); }
-        if ((rc = ensure_buf(s, s->past, total))) return rc;
+        const size_t extra[11] = {(size_t)n * 4, dst_actor_remap ? (size_t)n * S : 0, (size_t)n * S * 4,
+                                  offb, (size_t)offs[0][n] * 4, offb, (size_t)offs[1][n] * 4,
+                                  offs[2] ? offb : 0, offs[2] ? (size_t)offs[2][n] * 4 : 0,
+                                  offs[3] ? offb : 0, offs[3] ? (size_t)offs[3][n] * 4 : 0};
+        const void *host[11] = {nullptr, dst_actor_remap, maps->rank, offs[0], tabs[0], offs[1], tabs[1], offs[2], tabs[2],
+                                offs[3], tabs[3]};
+        Gathered G;
+        if ((rc = place_gathered(s, P, n, sum.totals, 11, extra, host, G))) return rc;
+        const size_t *o = G.o;
         uint8_t *bp = s->past.p;
-        const void *host[17] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, dst_actor_remap, maps->rank,
-                                offs[0], tabs[0], offs[1], tabs[1], offs[2], tabs[2], offs[3], tabs[3]};
-        for (int i = 7; i < 17; i++)
-            if (host[i] && sz[i]) SCHK(s, hipMemcpyAsync(bp + o[i], host[i], sz[i], hipMemcpyHostToDevice, st));
-        P.cap[0] = (uint32_t)tc; P.cap[1] = (uint32_t)td; P.cap[2] = (uint32_t)to; P.cap[3] = (uint32_t)tr;
-        P.out_docs = (hm_doc_row *)(bp + o[0]); P.out_changes = (hm_change_row *)(bp + o[1]); P.out_deps = (hm_dep_row *)(bp + o[2]);
-        P.out_ops = (hm_op_row *)(bp + o[3]); P.out_change_log = (uint32_t *)(bp + o[4]); P.out_op_log = (uint32_t *)(bp + o[5]);
-        SCHK(s, hm_launch_past_fill(P, st));
         uint32_t *dst_dev = (uint32_t *)(bp + o[6]);
         SCHK(s, hipMemcpyAsync(dst_dev, dst_staged, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
         RenameArgs R = {};
@@ -1481,15 +1493,9 @@ int hm_store_merge_from_submit(hm_store *s, uint32_t n, const uint32_t *src_hand
         memcpy(&sum, s->h_st, sizeof sum);
         if (sum.bad & HM_PAST_BAD_MAP)
             return hm_engine_fail(s->e, HM_ERR_INVALID, "a merge map: an id beyond its slice, an entry of HM_NONE, or an image beyond the stated totals");
-        hm_batch b = {};
-        b.a_stride = S; b.n_docs = n;
-        b.n_changes = (uint32_t)tc; b.n_deps = (uint32_t)td; b.n_ops = (uint32_t)to;
-        b.docs = P.out_docs; b.changes = P.out_changes; b.deps = P.out_deps; b.ops = P.out_ops;
         uint64_t id = 0;
-        if ((rc = hm_batch_submit_device(s, &b, dst_dev, dst_actor_remap ? bp + o[7] : nullptr, &id))) return rc;
-        s->fork_id = id; s->fork_n = n;
-        s->fork_rows[0] = (size_t)tc; s->fork_rows[1] = (size_t)td; s->fork_rows[2] = (size_t)to;
-        for (int i = 0; i < 6; i++) s->fork_off[i] = o[i];
+        if ((rc = hm_batch_submit_device(s, &G.b, dst_dev, dst_actor_remap ? bp + o[7] : nullptr, &id))) return rc;
+        note_fork(s, id, n, sum.totals, G);
         if (out_batch_id) *out_batch_id = id;
         return HM_OK;
     } catch (...) {
@@ -1571,28 +1577,18 @@ int hm_store_materialize_sized(hm_store *s, uint32_t n, const uint32_t *doc_hand
         if ((want_c && tc > out->cap_changes) || (want_d && td > out->cap_deps) || (want_o && to > out->cap_ops) ||
             (want_r && tr > out->cap_regs))
             return hm_engine_fail(s->e, HM_ERR_NOMEM, "a capacity below the rows of the materialized documents");
-        if (std::max(std::max(tc, td), std::max(to, tr)) > 0xFFFFFFFFull)
-            return hm_engine_fail(s->e, HM_ERR_NOMEM, "a call's rows stay below 2^32");
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        // [docs][changes][deps][ops][change_log][op_log] the gathered batch, then its merge's tables
-        const size_t sz[14] = {n * sizeof(hm_doc_row), tc * sizeof(hm_change_row), td * sizeof(hm_dep_row), to * sizeof(hm_op_row),
-                               tc * 4, to * 4, n * sizeof(hm_doc_result), (size_t)n * S * 4, (size_t)n * S * 4, (size_t)n * S * 4,
-                               tc * 4, tc * S * 4, tr * sizeof(hm_reg_result), to * sizeof(hm_surv_result)};
-        size_t o[14], total = 0;
-        for (int i = 0; i < 14; i++) { o[i] = total; total += al(sz[i] + 1); }
-        if ((rc = ensure_buf(s, s->past, total))) return rc;
+        // [the gathered batch], then its merge's tables
+        const size_t extra[8] = {n * sizeof(hm_doc_result), (size_t)n * S * 4, (size_t)n * S * 4, (size_t)n * S * 4,
+                                 (size_t)tc * 4, (size_t)tc * S * 4, (size_t)tr * sizeof(hm_reg_result), (size_t)to * sizeof(hm_surv_result)};
+        Gathered G;
+        if ((rc = place_gathered(s, P, n, sum.totals, 8, extra, nullptr, G))) return rc;
+        const size_t *sz = G.sz, *o = G.o;
         uint8_t *bp = s->past.p;
-        P.cap[0] = (uint32_t)tc; P.cap[1] = (uint32_t)td; P.cap[2] = (uint32_t)to; P.cap[3] = (uint32_t)tr;
-        P.out_docs = (hm_doc_row *)(bp + o[0]); P.out_changes = (hm_change_row *)(bp + o[1]); P.out_deps = (hm_dep_row *)(bp + o[2]);
-        P.out_ops = (hm_op_row *)(bp + o[3]); P.out_change_log = (uint32_t *)(bp + o[4]); P.out_op_log = (uint32_t *)(bp + o[5]);
-        SCHK(s, hm_launch_past_fill(P, st));
-        hm_batch b = {};
-        b.a_stride = S; b.n_docs = n;
-        b.n_changes = (uint32_t)tc; b.n_deps = (uint32_t)td; b.n_ops = (uint32_t)to; b.n_regs = (uint32_t)tr;
+        hm_batch &b = G.b;
+        b.n_regs = (uint32_t)tr;
         b.max_changes = sum.max_changes; b.max_ops = sum.max_ops; b.max_regs = sum.max_regs; b.max_objs = sum.max_objs;
         b.max_deps = sum.max_deps; b.doc_flags = sum.doc_flags;
         if (!b.max_changes && !b.max_ops && !b.max_regs && !b.max_objs) b.max_objs = 1;   // device hints present
-        b.docs = P.out_docs; b.changes = P.out_changes; b.deps = P.out_deps; b.ops = P.out_ops;
         hm_results d;
         d.docs = (hm_doc_result *)(bp + o[6]); d.clock = (uint32_t *)(bp + o[7]); d.back_clock = (uint32_t *)(bp + o[8]);
         d.heads = (uint32_t *)(bp + o[9]); d.hist = (int32_t *)(bp + o[10]); d.all_deps = (uint32_t *)(bp + o[11]);

@@ -13,9 +13,9 @@ CSRC = os.path.join(HERE, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("HM_OFFLOAD_ARCH", "gfx950")
 
-GPU_SRCS = ["merge_kernels.hip", "merge_large.hip", "store_kernels.hip", "waiting_kernels.hip", "changes_kernels.hip", "field_kernels.hip", "past_kernels.hip", "op_diff_kernels.hip", "inc_kernels.hip", "exchange.hip", "cursors.hip", "engine.cpp", "store.cpp",
+GPU_SRCS = ["merge_kernels.hip", "merge_large.hip", "store_kernels.hip", "waiting_kernels.hip", "changes_kernels.hip", "field_kernels.hip", "past_kernels.hip", "op_diff_kernels.hip", "state_kernels.hip", "inc_kernels.hip", "exchange.hip", "cursors.hip", "engine.cpp", "store.cpp",
             "decode.cpp", "docset.cpp"]
-GPU_DEPS = GPU_SRCS + ["scan.h", "merge_kernels.h", "store_kernels.h", "waiting_kernels.h", "changes_kernels.h", "field_kernels.h", "past_kernels.h", "op_diff_kernels.h", "doc_source.h", "wave.h", "engine_internal.h", "../../include/hypermerge_amd.h"]
+GPU_DEPS = GPU_SRCS + ["scan.h", "merge_kernels.h", "store_kernels.h", "waiting_kernels.h", "changes_kernels.h", "field_kernels.h", "past_kernels.h", "op_diff_kernels.h", "state_kernels.h", "doc_source.h", "wave.h", "engine_internal.h", "../../include/hypermerge_amd.h"]
 
 
 def _stale(out: str, deps) -> bool:

@@ -3123,6 +3123,192 @@ static int materialize_patch(hm_docset *ds, uint32_t n, const uint32_t *docs, co
     }
 }
 
+namespace {
+
+// The state rows of one document (hm_store_state) placed for rendering, by render_view's rules: a
+// keyed row goes to its object's keys in register order (the rows' order); on a list / text object
+// a row without an index (a detached element) is dropped and the others are placed at
+// elems[index], no sort.  keys / elems hold row numbers.
+struct StateView {
+    std::vector<std::vector<uint32_t>> keys, elems;
+    std::vector<uint32_t> n_el;
+    // NULL, or why the rows are not a merge's: an index at or past its object's elements, a slot filled twice
+    const char *place(const DocSt &d, const hm_state_row *rows, uint32_t n) {
+        const size_t no = d.obj_type.size();
+        keys.assign(no, {}); elems.assign(no, {}); n_el.assign(no, 0);
+        auto usable = [&](const hm_state_row &r) { return r.obj < no && r.reg < d.regs.size(); };
+        auto is_list = [&](uint32_t ob) { return d.obj_type[ob] == HM_MAKE_LIST || d.obj_type[ob] == HM_MAKE_TEXT; };
+        for (uint32_t i = 0; i < n; i++)
+            if (usable(rows[i]) && is_list(rows[i].obj) && rows[i].index >= 0) n_el[rows[i].obj]++;
+        for (size_t ob = 0; ob < no; ob++) if (n_el[ob]) elems[ob].assign(n_el[ob], HM_NONE);
+        for (uint32_t i = 0; i < n; i++) {
+            const hm_state_row &r = rows[i];
+            if (!usable(r)) continue;
+            if (!is_list(r.obj)) { keys[r.obj].push_back(i); continue; }
+            if (r.index < 0) continue;
+            if ((uint32_t)r.index >= n_el[r.obj]) return "a list element's index at or past its object's elements";
+            if (elems[r.obj][r.index] != HM_NONE) return "two list elements at one index";
+            elems[r.obj][r.index] = i;
+        }
+        return nullptr;
+    }
+    bool shown(const DocSt &d, uint32_t ob) const { return d.obj_type[ob] != NO_TYPE || !keys[ob].empty() || !elems[ob].empty(); }
+};
+
+// render_view's text from placed state rows (surv: the call's survivor table)
+void render_state_view(std::string &o, const DocSt &d, const StateView &V, const hm_state_row *rows, const hm_surv_result *surv) {
+    o += '{';
+    const size_t start = o.size();
+    for (uint32_t ob = 0; ob < d.obj_type.size(); ob++) {
+        if (!V.shown(d, ob)) continue;
+        if (o.size() > start) o += ',';
+        jstr(o, d.objs.ptr(ob), d.objs.len(ob));
+        const uint8_t t = d.obj_type[ob] == NO_TYPE ? HM_MAKE_MAP : d.obj_type[ob];
+        o += ":{\"type\":\""; o += TYPE_NAME[t & 3]; o += "\",\"keys\":[";
+        for (size_t i = 0; i < V.keys[ob].size(); i++) {
+            const hm_state_row &r = rows[V.keys[ob][i]];
+            if (i) o += ',';
+            o += '[';
+            jstr(o, d.regs.ptr(r.reg), d.regs.len(r.reg));
+            o += ",{";
+            jentry(o, d, surv + r.surv_off, r.n_surv);
+            o += "}]";
+        }
+        o += "],\"elems\":[";
+        for (size_t i = 0; i < V.elems[ob].size(); i++) {
+            const hm_state_row &r = rows[V.elems[ob][i]];
+            if (i) o += ',';
+            o += '[';
+            jstr(o, d.regs.ptr(r.reg), d.regs.len(r.reg));
+            o += ",{";
+            jentry(o, d, surv + r.surv_off, r.n_surv);
+            o += "}]";
+        }
+        o += "]}";
+    }
+    o += '}';
+}
+
+// Backend.getPatch's diffs from placed state rows: a create for every object of the view but ROOT, in
+// view order, then per object its sets in key order and its inserts in element order
+void render_state_diffs(std::string &o, const DocSt &d, const StateView &V, const hm_state_row *rows, const hm_surv_result *surv) {
+    JsonW w{o, d};
+    o += '[';
+    for (uint32_t ob = 1; ob < d.obj_type.size(); ob++)
+        if (V.shown(d, ob)) w.create(ob, d.obj_type[ob] == NO_TYPE ? HM_MAKE_MAP : d.obj_type[ob]);
+    for (uint32_t ob = 0; ob < d.obj_type.size(); ob++) {
+        if (!V.shown(d, ob)) continue;
+        const uint8_t t = d.obj_type[ob] == NO_TYPE ? HM_MAKE_MAP : d.obj_type[ob];
+        for (uint32_t i : V.keys[ob]) w.map_set(t, ob, rows[i].reg, surv + rows[i].surv_off, rows[i].n_surv);
+        for (uint32_t x = 0; x < V.elems[ob].size(); x++) {
+            const hm_state_row &r = rows[V.elems[ob][x]];
+            w.list_insert(t, ob, x, r.reg, surv + r.surv_off, r.n_surv);
+        }
+    }
+    o += ']';
+}
+
+// hm_docset_views (patch = false) and hm_docset_get_patch (patch = true): one hm_store_state call per
+// stride class, the documents rendered on the docset's host threads
+int docset_states(hm_docset *ds, uint32_t n, const uint32_t *docs, bool patch, hm_text **out) {
+    int rc = check_request(ds, n, docs);
+    if (rc) return rc;
+    std::vector<std::string> js(n);
+    auto head = [&](std::string &o, uint32_t doc, uint32_t hist) {
+        o = "{\"doc\":" + std::to_string(doc) + ",\"history\":" + std::to_string(hist) + ",\"patch\":{\"clock\":";
+    };
+    const char *mid = ",\"canUndo\":false,\"canRedo\":false,\"diffs\":";
+    for (uint32_t i = 0; i < n; i++) {                           // (a document not placed yet: Backend.init())
+        DocSt &d = ds->doc(docs[i]);
+        if (!d.ready) d.setup();
+        if (d.cls != NO_CLASS) continue;
+        StateView V;
+        V.place(d, nullptr, 0);
+        if (patch) {
+            head(js[i], docs[i], 0);
+            js[i] += "{},\"deps\":{}"; js[i] += mid;
+            render_state_diffs(js[i], d, V, nullptr, nullptr);
+            js[i] += "}}";
+        } else render_state_view(js[i], d, V, nullptr, nullptr);
+    }
+    for (uint32_t c = 0; c < N_CLASS; c++) {
+        const uint32_t S = STRIDES[c];
+        std::vector<uint32_t> idx, hs;
+        class_docs(ds, c, n, docs, idx, hs);
+        if (idx.empty()) continue;
+        const uint32_t k = (uint32_t)idx.size();
+        // the tables sized by what the host knows of the documents: a live register is one of the
+        // document's, a survivor one of its ops (the call's totals, should they be larger)
+        uint64_t cap[2] = {0, 0};
+        for (uint32_t j = 0; j < k; j++) { const DocSt &d = ds->doc(docs[idx[j]]); cap[0] += d.regs.size(); cap[1] += d.n_ops; }
+        std::vector<hm_state_row> rows;
+        std::vector<hm_surv_result> surv;
+        std::vector<uint32_t> range(4 * (size_t)k), flags(k), clock, heads;
+        if (patch) { clock.resize((size_t)k * S); heads.resize((size_t)k * S); }
+        for (int attempt = 0;; attempt++) {
+            if (cap[0] > 0xFFFFFFFFull || cap[1] > 0xFFFFFFFFull) return hm_engine_fail(ds->e, HM_ERR_NOMEM, "the state of the request's documents exceeds 2^32 rows");
+            rows.resize(cap[0] + 1); surv.resize(cap[1] + 1);
+            const hm_state_out so = {(uint32_t)cap[0], (uint32_t)cap[1], rows.data(), surv.data(), range.data(), flags.data()};
+            uint64_t tot[2] = {0, 0};
+            rc = hm_store_state(ds->stores[c], k, hs.data(), &so, patch ? clock.data() : nullptr, patch ? heads.data() : nullptr, tot);
+            if (rc == HM_ERR_NOMEM && attempt == 0 && (tot[0] > cap[0] || tot[1] > cap[1])) { cap[0] = tot[0]; cap[1] = tot[1]; continue; }
+            if (rc) return rc;
+            break;
+        }
+        std::atomic<const char *> bad{nullptr};
+        par_for(k, std::min<uint32_t>(ds->threads, std::max<uint32_t>(1, k / 64)), [&](uint32_t lo, uint32_t hi, uint32_t) {
+            StateView V;
+            for (uint32_t j = lo; j < hi; j++) {
+                const DocSt &d = ds->doc(docs[idx[j]]);
+                if (flags[j] & HM_ST_BAD_ROWS) { bad = "register survivors outside the document's slots"; return; }
+                const hm_state_row *r = rows.data() + range[4 * (size_t)j];
+                const char *why = V.place(d, r, range[4 * (size_t)j + 1]);
+                if (why) { bad = why; return; }
+                std::string &o = js[idx[j]];
+                if (patch) {
+                    const uint32_t na = (uint32_t)std::min<size_t>(d.actors.size(), S);
+                    head(o, docs[idx[j]], d.hist_len);
+                    jclock(o, d, clock.data() + (size_t)j * S, na);
+                    o += ",\"deps\":";
+                    jclock(o, d, heads.data() + (size_t)j * S, na);
+                    o += mid;
+                    render_state_diffs(o, d, V, r, surv.data());
+                    o += "}}";
+                } else render_state_view(o, d, V, r, surv.data());
+            }
+        });
+        if (bad.load()) return hm_engine_fail(ds->e, HM_ERR_DEVICE, bad.load());
+    }
+    *out = json_array(js);
+    return HM_OK;
+}
+
+}  // namespace
+
+int hm_docset_views(hm_docset *ds, uint32_t n, const uint32_t *docs, hm_text **out) {
+    if (!ds || !out || (n && !docs)) return HM_ERR_INVALID;
+    *out = nullptr;
+    Busy b(ds);
+    if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
+    try {
+        return docset_states(ds, n, docs, false, out);
+    } catch (...) {
+        return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_views");
+    }
+}
+
+int hm_docset_get_patch(hm_docset *ds, uint32_t n, const uint32_t *docs, hm_text **out) {
+    if (!ds || !out || (n && !docs)) return HM_ERR_INVALID;
+    *out = nullptr;
+    Busy b(ds);
+    if (!b.ok) return hm_engine_fail(ds->e, HM_ERR_INVALID, "docset busy");
+    try {
+        return docset_states(ds, n, docs, true, out);
+    } catch (...) {
+        return hm_engine_fail(ds->e, HM_ERR_NOMEM, "exception in hm_docset_get_patch");
+    }
+}
+
 int hm_docset_view(hm_docset *ds, uint32_t doc, hm_text **out) {
     if (!ds || !out || doc >= ds->n_docs.load()) return HM_ERR_INVALID;
     *out = nullptr;

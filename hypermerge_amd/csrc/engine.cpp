@@ -20,6 +20,7 @@
 #include "field_kernels.h"
 #include "past_kernels.h"
 #include "op_diff_kernels.h"
+#include "state_kernels.h"
 
 struct hm_engine {
     int device = 0;
@@ -748,6 +749,125 @@ static int op_diffs_host(hm_engine *e, const hm_batch *hb, const hm_results *hr,
         return HM_OK;
     } catch (...) {
         return fail(e, HM_ERR_DEVICE, "exception in hm_op_diffs_host");
+    }
+}
+
+// (the state calls read the document table and the results alone: no change, dep or op table is asked for)
+static int check_state_batch(hm_engine *e, const hm_batch *b, const hm_results *r, bool clock, bool heads) {
+    if (!b || b->a_stride == 0 || b->a_stride > HM_MAX_STRIDE) return fail(e, HM_ERR_INVALID, "a_stride must be in [1,256]");
+    if (b->n_docs && !b->docs) return fail(e, HM_ERR_INVALID, "docs table missing");
+    if ((b->n_docs && !r->docs) || (b->n_regs && !r->regs) || (b->n_ops && !r->surv) || (clock && !r->clock) || (heads && !r->heads))
+        return fail(e, HM_ERR_INVALID, "hm_state needs the results' docs, regs and surv tables (and clock / heads when asked for)");
+    return HM_OK;
+}
+
+size_t hm_state_work_bytes(uint32_t n) {
+    // [counts 4n][offsets 4n][zero and flags 2n] u32, then the scan's per-chunk words
+    return ((((size_t)n * 40) + 255) & ~(size_t)255) + (size_t)hm_past_scan_chunks(n) * HM_PAST_PART * 8;
+}
+
+int hm_state_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                    const hm_state_out *out, uint32_t *out_clock, uint32_t *out_heads, hm_state_summary *out_summary,
+                    void *work, void *stream) {
+    try {
+        if (!e || !r || !out || !out_summary) return HM_ERR_INVALID;
+        int st = check_state_batch(e, b, r, out_clock != nullptr, out_heads != nullptr);
+        if (st) return st;
+        if (n && (!work || !out->range || !out->flags))
+            return fail(e, HM_ERR_INVALID, "hm_state: work, the range array or the flags missing");
+        if (((uintptr_t)work | (uintptr_t)r->regs | (uintptr_t)r->surv | (uintptr_t)out->surv | (uintptr_t)out->range) & 15u)
+            return fail(e, HM_ERR_INVALID, "hm_state: work, the register and survivor tables and out->range must be 16-byte aligned");
+        if ((out->cap_rows && !out->rows) || (out->cap_surv && !out->surv))
+            return fail(e, HM_ERR_INVALID, "hm_state: an output table with a capacity is missing");
+        HIPCHK(e, hipSetDevice(e->device));
+        hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+        StateArgs A = {};
+        A.n = n;
+        A.src.docs = b->docs; A.src.res = r->docs; A.src.n_docs = b->n_docs; A.src.S = b->a_stride; A.src.handles = doc_index;
+        A.src.clock = r->clock;
+        A.regs = r->regs; A.surv = r->surv; A.lim_r = b->n_regs; A.lim_s = b->n_ops; A.heads = r->heads;
+        A.cnt = (uint32_t *)work; A.off = A.cnt + 4 * (size_t)n; A.aux = A.off + 4 * (size_t)n;
+        A.part = (unsigned long long *)((char *)work + ((((size_t)n * 40) + 255) & ~(size_t)255));
+        A.sum = out_summary;
+        A.cap_rows = out->cap_rows; A.cap_surv = out->cap_surv;
+        A.out_rows = out->rows; A.out_surv = out->surv; A.out_range = out->range; A.out_flags = out->flags;
+        A.out_clock = out_clock; A.out_heads = out_heads;
+        hipError_t hr = hm_launch_state_count(A, s);
+        if (hr == hipSuccess) hr = hm_launch_state_fill(A, s);
+        return hr == hipSuccess ? HM_OK : hip_fail(e, hr, "state kernels launch");
+    } catch (...) {
+        return fail(e, HM_ERR_DEVICE, "exception in hm_state_device");
+    }
+}
+
+int hm_state_host(hm_engine *e, const hm_batch *hb, const hm_results *hr, uint32_t n, const uint32_t *doc_index,
+                  const hm_state_out *out, uint32_t *out_clock, uint32_t *out_heads, uint64_t *out_totals) {
+    try {
+        if (!e || !hr || !out) return HM_ERR_INVALID;
+        int st = check_state_batch(e, hb, hr, out_clock != nullptr, out_heads != nullptr);
+        if (st) return st;
+        if (out_totals) out_totals[0] = out_totals[1] = 0;
+        if (!n) return HM_OK;
+        if (!out->range || !out->flags || (out->cap_rows && !out->rows) || (out->cap_surv && !out->surv))
+            return fail(e, HM_ERR_INVALID, "hm_state: the range array, the flags or an output table missing");
+        if (doc_index)
+            for (uint32_t i = 0; i < n; i++)
+                if (doc_index[i] >= hb->n_docs) return fail(e, HM_ERR_INVALID, "hm_state: a document outside the batch");
+        if (!doc_index && n > hb->n_docs) return fail(e, HM_ERR_INVALID, "hm_state: a document outside the batch");
+        HIPCHK(e, hipSetDevice(e->device));
+        const size_t S = hb->a_stride, nd = hb->n_docs;
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        // inputs 0..6, then the summary, the work memory and the six outputs
+        const size_t sz[15] = {nd * sizeof(hm_doc_row), nd * sizeof(hm_doc_result), hb->n_regs * sizeof(hm_reg_result),
+                               hb->n_ops * sizeof(hm_surv_result), out_clock ? nd * S * 4 : 0, out_heads ? nd * S * 4 : 0,
+                               doc_index ? (size_t)n * 4 : 0, sizeof(hm_state_summary), hm_state_work_bytes(n),
+                               (size_t)out->cap_rows * sizeof(hm_state_row), (size_t)out->cap_surv * sizeof(hm_surv_result),
+                               (size_t)n * 16, (size_t)n * 4, out_clock ? (size_t)n * S * 4 : 0, out_heads ? (size_t)n * S * 4 : 0};
+        const void *src[7] = {hb->docs, hr->docs, hr->regs, hr->surv, hr->clock, hr->heads, doc_index};
+        size_t off[15], total = 0;
+        for (int i = 0; i < 15; i++) { off[i] = total; total += al(sz[i] ? sz[i] : 1); }
+        char *base = nullptr;
+        if (hipMalloc((void **)&base, total) != hipSuccess) return fail(e, HM_ERR_NOMEM, "hipMalloc state staging");
+        hipStream_t s = e->stream;
+        hm_batch b = *hb;
+        b.docs = (const hm_doc_row *)(base + off[0]);
+        b.changes = nullptr; b.deps = nullptr; b.ops = nullptr; b.min_clock = nullptr;
+        hm_results d = {};
+        d.docs = (hm_doc_result *)(base + off[1]); d.regs = (hm_reg_result *)(base + off[2]); d.surv = (hm_surv_result *)(base + off[3]);
+        d.clock = (uint32_t *)(base + off[4]); d.heads = (uint32_t *)(base + off[5]);
+        hm_state_out o = *out;
+        o.rows = (hm_state_row *)(base + off[9]); o.surv = (hm_surv_result *)(base + off[10]);
+        o.range = (uint32_t *)(base + off[11]); o.flags = (uint32_t *)(base + off[12]);
+        hm_state_summary sum;
+        memset(&sum, 0, sizeof sum);
+        hipError_t rr = hipSuccess;
+        for (int i = 0; i < 7 && rr == hipSuccess; i++)
+            if (sz[i]) rr = hipMemcpyAsync(base + off[i], src[i], sz[i], hipMemcpyHostToDevice, s);
+        int rc = HM_OK;
+        if (rr == hipSuccess)
+            rc = hm_state_device(e, &b, &d, n, doc_index ? (const uint32_t *)(base + off[6]) : nullptr, &o,
+                                 out_clock ? (uint32_t *)(base + off[13]) : nullptr, out_heads ? (uint32_t *)(base + off[14]) : nullptr,
+                                 (hm_state_summary *)(base + off[7]), base + off[8], s);
+        if (rc == HM_OK && rr == hipSuccess) rr = hipMemcpyAsync(&sum, base + off[7], sizeof sum, hipMemcpyDeviceToHost, s);
+        if (rc == HM_OK && rr == hipSuccess) rr = hipStreamSynchronize(s);
+        const bool fits = sum.totals[0] <= out->cap_rows && sum.totals[1] <= out->cap_surv;
+        if (rc == HM_OK && rr == hipSuccess && !sum.bad && fits) {
+            if (sum.totals[0]) rr = hipMemcpy(out->rows, o.rows, (size_t)sum.totals[0] * sizeof(hm_state_row), hipMemcpyDeviceToHost);
+            if (rr == hipSuccess && sum.totals[1]) rr = hipMemcpy(out->surv, o.surv, (size_t)sum.totals[1] * sizeof(hm_surv_result), hipMemcpyDeviceToHost);
+            if (rr == hipSuccess) rr = hipMemcpy(out->range, o.range, sz[11], hipMemcpyDeviceToHost);
+            if (rr == hipSuccess) rr = hipMemcpy(out->flags, o.flags, sz[12], hipMemcpyDeviceToHost);
+            if (rr == hipSuccess && out_clock) rr = hipMemcpy(out_clock, base + off[13], sz[13], hipMemcpyDeviceToHost);
+            if (rr == hipSuccess && out_heads) rr = hipMemcpy(out_heads, base + off[14], sz[14], hipMemcpyDeviceToHost);
+        }
+        (void)hipFree(base);
+        if (rc != HM_OK) return rc;
+        if (rr != hipSuccess) return hip_fail(e, rr, "hm_state_host");
+        if (sum.bad & HM_ST_BAD_HANDLE) return fail(e, HM_ERR_INVALID, "hm_state: a document outside the batch");
+        if (out_totals) { out_totals[0] = sum.totals[0]; out_totals[1] = sum.totals[1]; }
+        if (!fits) return fail(e, HM_ERR_NOMEM, "a capacity below the rows of the state");
+        return HM_OK;
+    } catch (...) {
+        return fail(e, HM_ERR_DEVICE, "exception in hm_state_host");
     }
 }
 

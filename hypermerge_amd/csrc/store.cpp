@@ -44,6 +44,7 @@
 #include "field_kernels.h"
 #include "past_kernels.h"
 #include "op_diff_kernels.h"
+#include "state_kernels.h"
 
 namespace {
 
@@ -1817,6 +1818,107 @@ int hm_store_op_diffs_ex(hm_store *s, uint32_t n, const uint32_t *doc_handles, c
         return op_diffs_filled(s, n, doc_handles, from, to, nullptr, out, out_index, out_totals, opts);
     } catch (...) {
         return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_op_diffs");
+    }
+}
+
+}  // extern "C"
+
+// The count pass of n state requests: the handles go to the stage buffer, where the counts, offsets
+// and summary stay (A.cnt / A.off / A.aux / A.sum); *sum = the summary read back.
+static int state_count(hm_store *s, uint32_t n, const uint32_t *doc_handles, StateArgs &A, hm_state_summary *sum) {
+    hipStream_t st = hm_engine_stream(s->e);
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_sum = 0, o_h = 256, o_cnt = o_h + al(4 * (size_t)n), o_off = o_cnt + al(16 * (size_t)n),
+                 o_aux = o_off + al(16 * (size_t)n), o_part = o_aux + al(8 * (size_t)n),
+                 total = o_part + al((size_t)hm_past_scan_chunks(n) * HM_PAST_PART * 8);
+    int rc = ensure_stage(s, total);
+    if (rc) return rc;
+    uint8_t *sp = s->stage.p;
+    SCHK(s, hipMemcpyAsync(sp + o_h, doc_handles, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    A = StateArgs{};
+    A.n = n; A.src = store_source(s); A.src.handles = (const uint32_t *)(sp + o_h);
+    A.regs = s->regs; A.surv = s->surv; A.lim_r = s->cap_r; A.lim_s = s->cap_o; A.heads = s->heads;
+    A.cnt = (uint32_t *)(sp + o_cnt); A.off = (uint32_t *)(sp + o_off); A.aux = (uint32_t *)(sp + o_aux);
+    A.part = (unsigned long long *)(sp + o_part);
+    A.sum = (hm_state_summary *)(sp + o_sum);
+    SCHK(s, hm_launch_state_count(A, st));
+    SCHK(s, hipMemcpyAsync(s->h_st, A.sum, sizeof(hm_state_summary), hipMemcpyDeviceToHost, st));
+    SCHK(s, hipStreamSynchronize(st));
+    memcpy(sum, s->h_st, sizeof *sum);
+    if (sum->bad & HM_ST_BAD_HANDLE) return hm_engine_fail(s->e, HM_ERR_INVALID, "bad handle");
+    return HM_OK;
+}
+
+extern "C" {
+
+int hm_store_state_sizes(hm_store *s, uint32_t n, const uint32_t *doc_handles, uint32_t *out_counts, uint32_t *out_flags,
+                         uint64_t *out_totals) {
+    if (!s || (n && !doc_handles)) return HM_ERR_INVALID;
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        if (out_totals) out_totals[0] = out_totals[1] = 0;
+        if (!n) return HM_OK;
+        StateArgs A;
+        hm_state_summary sum;
+        int rc = state_count(s, n, doc_handles, A, &sum);
+        if (rc) return rc;
+        if (out_totals) { out_totals[0] = sum.totals[0]; out_totals[1] = sum.totals[1]; }
+        if (out_counts || out_flags) {
+            hipStream_t st = hm_engine_stream(s->e);
+            std::vector<uint32_t> cnt(4 * (size_t)n), aux(2 * (size_t)n);
+            SCHK(s, hipMemcpyAsync(cnt.data(), A.cnt, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
+            SCHK(s, hipMemcpyAsync(aux.data(), A.aux, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+            SCHK(s, hipStreamSynchronize(st));
+            for (size_t i = 0; i < n; i++) {
+                if (out_counts) { out_counts[2 * i] = cnt[4 * i]; out_counts[2 * i + 1] = cnt[4 * i + 1]; }
+                if (out_flags) out_flags[i] = aux[2 * i + 1];
+            }
+        }
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_state_sizes");
+    }
+}
+
+int hm_store_state(hm_store *s, uint32_t n, const uint32_t *doc_handles, const hm_state_out *out, uint32_t *out_clock,
+                   uint32_t *out_heads, uint64_t *out_totals) {
+    if (!s || !out || (n && (!doc_handles || !out->range || !out->flags)) || (out->cap_rows && !out->rows) ||
+        (out->cap_surv && !out->surv))
+        return HM_ERR_INVALID;
+    if (s->pending) return hm_engine_fail(s->e, HM_ERR_INVALID, "batch in flight");
+    try {
+        if (out_totals) out_totals[0] = out_totals[1] = 0;
+        if (!n) return HM_OK;
+        hipStream_t st = hm_engine_stream(s->e);
+        StateArgs A;
+        hm_state_summary sum;
+        int rc = state_count(s, n, doc_handles, A, &sum);
+        if (rc) return rc;
+        const uint64_t tr = sum.totals[0], ts = sum.totals[1];
+        if (out_totals) { out_totals[0] = tr; out_totals[1] = ts; }
+        if (tr > out->cap_rows || ts > out->cap_surv)
+            return hm_engine_fail(s->e, HM_ERR_NOMEM, "a capacity below the rows of the state");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        // [rows][survivors][ranges][flags][clock][heads]
+        const size_t row_b = 4 * (size_t)n * s->S;
+        const size_t sz[6] = {tr * sizeof(hm_state_row), ts * sizeof(hm_surv_result), 16 * (size_t)n, 4 * (size_t)n,
+                              out_clock ? row_b : 0, out_heads ? row_b : 0};
+        size_t o[6], total = 0;
+        for (int i = 0; i < 6; i++) { o[i] = total; total += al(sz[i] + 1); }
+        if ((rc = ensure_buf(s, s->past, total))) return rc;
+        uint8_t *bp = s->past.p;
+        A.cap_rows = (uint32_t)tr; A.cap_surv = (uint32_t)ts;
+        A.out_rows = (hm_state_row *)(bp + o[0]); A.out_surv = (hm_surv_result *)(bp + o[1]);
+        A.out_range = (uint32_t *)(bp + o[2]); A.out_flags = (uint32_t *)(bp + o[3]);
+        A.out_clock = out_clock ? (uint32_t *)(bp + o[4]) : nullptr; A.out_heads = out_heads ? (uint32_t *)(bp + o[5]) : nullptr;
+        SCHK(s, hm_launch_state_fill(A, st));
+        void *dst[6] = {out->rows, out->surv, out->range, out->flags, out_clock, out_heads};
+        for (int i = 0; i < 6; i++)
+            if (sz[i]) SCHK(s, hipMemcpyAsync(dst[i], bp + o[i], sz[i], hipMemcpyDeviceToHost, st));
+        SCHK(s, hipStreamSynchronize(st));
+        return HM_OK;
+    } catch (...) {
+        return hm_engine_fail(s->e, HM_ERR_NOMEM, "exception in hm_store_state");
     }
 }
 

@@ -131,6 +131,28 @@ class DocSet:
         s, _ = _text(self._L, t)
         return json.loads(s)
 
+    def views(self, docs: Sequence[int], raw: bool = False):
+        """hm_docset_views: what view(doc) returns for every document of `docs` (a document may
+        repeat), from one device call per stride class.  raw=True: the call's text as it came (a
+        JSON array whose element i is hm_docset_view(docs[i])'s bytes)."""
+        ids = np.ascontiguousarray(docs, np.uint32)
+        t = ctypes.c_void_p()
+        self.engine._check(self._L.hm_docset_views(self._h, len(ids), ids.ctypes.data if len(ids) else None, ctypes.byref(t)),
+                           "hm_docset_views")
+        s, _ = _text(self._L, t, raw=raw)
+        return s if raw else json.loads(s)
+
+    def get_patch(self, docs: Sequence[int]) -> List[Dict[str, Any]]:
+        """hm_docset_get_patch: Backend.getPatch per document, {"doc", "history", "patch": {"clock",
+        "deps", "canUndo": False, "canRedo": False, "diffs"}}: the diffs build the document from an
+        empty one (creates, then per object its sets and its inserts)."""
+        ids = np.ascontiguousarray(docs, np.uint32)
+        t = ctypes.c_void_p()
+        self.engine._check(self._L.hm_docset_get_patch(self._h, len(ids), ids.ctypes.data if len(ids) else None, ctypes.byref(t)),
+                           "hm_docset_get_patch")
+        s, _ = _text(self._L, t)
+        return json.loads(s)
+
     def blocked(self) -> List[int]:
         """Documents that hold queued changes (every stride class), ids ascending."""
         n = ctypes.c_uint32()

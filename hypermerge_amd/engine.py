@@ -47,7 +47,9 @@ EXPORTS = ("hm_abi_version", "hm_status_message", "hm_engine_create", "hm_engine
            "hm_store_fields", "hm_fields_device", "hm_fields_host", "hm_docset_fields",
            "hm_store_op_diff_sizes_at", "hm_store_op_diffs_at", "hm_op_diffs_at_work_bytes", "hm_op_diffs_at_device",
            "hm_op_diffs_at_host", "hm_docset_materialize_patch_at", "hm_store_fork_submit", "hm_docset_fork",
-           "hm_store_merge_from_submit", "hm_docset_merge_from", "hm_docset_merge_stats")
+           "hm_store_merge_from_submit", "hm_docset_merge_from", "hm_docset_merge_stats",
+           "hm_store_state_sizes", "hm_store_state", "hm_state_work_bytes", "hm_state_device", "hm_state_host",
+           "hm_docset_views", "hm_docset_get_patch")
 
 _lib = None
 
@@ -148,6 +150,13 @@ def lib():
             "hm_op_diffs_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, vp],
             "hm_op_diffs_host": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp],
             "hm_docset_materialize_patch_ex": [vp, u32, vp, vp, u32, vp],
+            "hm_store_state_sizes": [vp, u32, vp, vp, vp, vp],
+            "hm_store_state": [vp, u32, vp, vp, vp, vp, vp],
+            "hm_state_work_bytes": [u32],
+            "hm_state_device": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp, vp, vp],
+            "hm_state_host": [vp, ctypes.POINTER(CBatch), ctypes.POINTER(CResults), u32, vp, vp, vp, vp, vp],
+            "hm_docset_views": [vp, u32, vp, ctypes.POINTER(vp)],
+            "hm_docset_get_patch": [vp, u32, vp, ctypes.POINTER(vp)],
             "hm_store_op_diff_sizes_ex": [vp, u32, vp, vp, vp, vp, vp, vp, u32],
             "hm_store_op_diffs_ex": [vp, u32, vp, vp, vp, vp, vp, vp, u32],
             "hm_op_diffs_work_bytes_ex": [ctypes.POINTER(CBatch), u32, u32],
@@ -182,6 +191,7 @@ def lib():
         L.hm_op_diffs_work_bytes.restype = ctypes.c_size_t
         L.hm_op_diffs_work_bytes_ex.restype = ctypes.c_size_t
         L.hm_op_diffs_at_work_bytes.restype = ctypes.c_size_t
+        L.hm_state_work_bytes.restype = ctypes.c_size_t
         L.hm_docset_destroy.restype = None
         L.hm_docset_engine.restype = ctypes.c_void_p
         L.hm_text_data.restype = ctypes.c_void_p
@@ -232,6 +242,26 @@ class COpDiffSummary(ctypes.Structure):
 
 
 assert ctypes.sizeof(COpDiffSummary) == 64 and OP_DIFF_DT.itemsize == 16
+
+
+ST_BAD_ROWS = 1                           # HM_ST_BAD_ROWS request flag
+STATE_ROW_DT = np.dtype([("reg", "<u4"), ("obj", "<u4"), ("index", "<i4"), ("n_surv", "<u4"), ("surv_off", "<u4")])
+
+
+class CStateOut(ctypes.Structure):
+    """struct hm_state_out"""
+    _fields_ = [("cap_rows", ctypes.c_uint32), ("cap_surv", ctypes.c_uint32), ("rows", ctypes.c_void_p),
+                ("surv", ctypes.c_void_p), ("range", ctypes.c_void_p), ("flags", ctypes.c_void_p)]
+
+
+class CStateSummary(ctypes.Structure):
+    """struct hm_state_summary"""
+    _fields_ = [("totals", ctypes.c_uint64 * 2), ("reserved64", ctypes.c_uint64 * 2), ("max_rows", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 3), ("max_surv", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("bad", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(CStateSummary) == 64 and STATE_ROW_DT.itemsize == 20
 
 
 FLD_NOT_READY, FLD_BAD_ROWS = 1, 2          # HM_FLD_* request flags
@@ -527,6 +557,49 @@ class Engine:
                                                   p(clock_rows), ctypes.byref(out), p(out_index), p(out_summary), p(work),
                                                   p(stream), ODF_LISTS if lists else 0),
                     "hm_op_diffs_at_device")
+
+    def state_host(self, batch: Batch, results: Results, docs=None, cap=None, clocks=False):
+        """hm_state_host: the current state of documents docs[i] of a merged batch (None: every document,
+        one request each): per live register (n_surv > 0, obj known) one STATE_ROW_DT row in ascending
+        register id, the survivors in row order.  Returns (rows, survivors SURV_RESULT_DT, ranges [n, 4] =
+        first row, rows, first survivor, survivors per request, flags [n]); a request flagged ST_BAD_ROWS
+        has no rows, as has a document whose status is not OK.  cap = (rows, survivors) the tables hold
+        (None: sized by a first call's totals).  clocks=True: the requests' clock and heads rows
+        ([n, a_stride] each) as a fifth and sixth element."""
+        from .columnar import SURV_RESULT_DT
+        idx = None if docs is None else np.ascontiguousarray(docs, np.uint32)
+        n = batch.n_docs if idx is None else len(idx)
+        S = batch.a_stride
+        cb, cr = batch.c_struct(), results.c_struct()
+        tot = (ctypes.c_uint64 * 2)()
+        caps = cap if cap is not None else (0, 0)
+        for _ in range(2):
+            rows, surv = np.zeros(max(caps[0], 1), STATE_ROW_DT), np.zeros(max(caps[1], 1), SURV_RESULT_DT)
+            rng, fl = np.zeros((max(n, 1), 4), np.uint32), np.zeros(max(n, 1), np.uint32)
+            ck, hd = np.zeros((max(n, 1), S), np.uint32), np.zeros((max(n, 1), S), np.uint32)
+            out = CStateOut(caps[0], caps[1], rows.ctypes.data, surv.ctypes.data, rng.ctypes.data, fl.ctypes.data)
+            st = self._L.hm_state_host(self._h, ctypes.byref(cb), ctypes.byref(cr), n,
+                                       idx.ctypes.data if idx is not None and n else None, ctypes.byref(out),
+                                       ck.ctypes.data if clocks else None, hd.ctypes.data if clocks else None, tot)
+            if st == 34 and cap is None and (tot[0] > caps[0] or tot[1] > caps[1]):   # HM_ERR_NOMEM: sized by the totals
+                caps = (int(tot[0]), int(tot[1]))
+                continue
+            break
+        self._check(st, "hm_state_host")
+        base = (rows[:int(tot[0])], surv[:int(tot[1])], rng[:n], fl[:n])
+        return base + (ck[:n], hd[:n]) if clocks else base
+
+    def state_work_bytes(self, n: int) -> int:
+        return int(self._L.hm_state_work_bytes(n))
+
+    def state_device(self, cbatch: CBatch, cresults: CResults, n: int, doc_index: int, out: "CStateOut", out_summary: int,
+                     work: int, stream: int = 0, out_clock: int = 0, out_heads: int = 0) -> None:
+        """hm_state_device: the same with every table in device memory (pointers; `out` a CStateOut of
+        device tables, `work` of state_work_bytes(n) bytes; enqueued, not synchronised)."""
+        p = lambda x: ctypes.c_void_p(x) if x else None
+        self._check(self._L.hm_state_device(self._h, ctypes.byref(cbatch), ctypes.byref(cresults), n, p(doc_index),
+                                            ctypes.byref(out), p(out_clock), p(out_heads), p(out_summary), p(work), p(stream)),
+                    "hm_state_device")
 
     def small_occupancy(self, batch: Batch) -> Sequence[int]:
         """(resident one-wave workgroups per CU, CUs, op rows per lane, size class, lists, counters) of

@@ -625,6 +625,31 @@ class GpuEngine {
     return out
   }
 
+  // the merged documents of states[i] now, many at once (one device call per docset and stride
+  // class): per state what addon.docsetView parses to, {objUuid: {type, keys: [[key, entry]], elems:
+  // [[elemId, entry]]}}.  Reflects the rounds already applied: in 'async' mode await idle() first.
+  views(states) { return this.perShard(states, (ds, ids) => JSON.parse(addon.docsetViews(ds, ids))) }
+
+  // Backend.getPatch for many documents at once: per state {history, patch} with patch = {clock, deps,
+  // canUndo: false, canRedo: false, diffs}, the diffs building the document from an empty one
+  // (creates first, then per object its sets and its inserts).  Reflects the rounds already applied.
+  getPatches(states) {
+    return this.perShard(states, (ds, ids) => JSON.parse(addon.docsetGetPatch(ds, ids)).map((r) => ({ history: r.history, patch: r.patch })))
+  }
+
+  // f(docset, the ids of the states that live there) per shard, its answers back in the states' order
+  perShard(states, f) {
+    const out = new Array(states.length)
+    this.docsets.forEach((ds, k) => {
+      const at = []
+      states.forEach((st, i) => { if (st.shard === k) at.push(i) })
+      if (!at.length) return
+      const got = f(ds, Uint32Array.from(at.map((i) => states[i].id)))
+      at.forEach((i, j) => { out[i] = got[j] })
+    })
+    return out
+  }
+
   // the patches of documents as they were, many at once: reqs[i] = {state | id, history: n} -> per
   // request {history, patch}: the patch Backend.applyChanges(Backend.init(), history.slice(0, n))
   // returns ({clock, deps, canUndo: false, canRedo: false, diffs}), its per-op diffs read off the
@@ -1084,18 +1109,15 @@ function materialize(state) {
   return view
 }
 
-// Backend.getPatch(state): the whole document as diffs from an empty one
+// Backend.getPatch(state): the whole document as diffs from an empty one (a create per object but
+// ROOT in view order, then per object its sets in key order and its inserts in element order),
+// rendered by the docset from one device read of the document's live registers; canUndo / canRedo
+// are the state's
 function fullPatch(state) {
-  const diffs = []
-  for (const [uuid, ov] of materialize(state)) {
-    if (uuid !== '00000000-0000-0000-0000-000000000000') diffs.push({ action: 'create', obj: uuid, type: ov.type })
-  }
-  for (const [uuid, ov] of materialize(state)) {
-    for (const [key, e] of ov.keys) diffs.push(Object.assign({ action: 'set', type: ov.type, obj: uuid, key }, e))
-    ov.elems.forEach(([elemId, e], index) => diffs.push(Object.assign({ action: 'insert', type: ov.type, obj: uuid, index, elemId }, e)))
-  }
-  return { clock: dictCopy(state.clock), deps: dictCopy(state.deps), canUndo: state.canUndo,
-    canRedo: state.canRedo, diffs }
+  const { patch } = state.engine.getPatches([state])[0]
+  patch.canUndo = state.canUndo
+  patch.canRedo = state.canRedo
+  return patch
 }
 
 const emptyPatch = (state) => ({ clock: dictCopy(state.clock), deps: dictCopy(state.deps),

@@ -974,6 +974,30 @@ static napi_value DocsetWaiting(napi_env env, napi_callback_info info) {
     return js;
 }
 
+/* docsetViews / docsetGetPatch(docset, ids Uint32Array) -> JSON text: per document what docsetView
+ * returns / {"doc", "history", "patch"} with Backend.getPatch's patch, from one device call per
+ * stride class (refused while a call on the docset is in flight) */
+static napi_value docset_states(napi_env env, napi_callback_info info, int patch) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return NULL;
+    Docset *d = get_docset(env, argv[0]);
+    if (!d) return NULL;
+    void *p; size_t n;
+    if (!get_bytes(env, argv[1], &p, &n)) return NULL;
+    hm_text *t = NULL;
+    int st = patch ? hm_docset_get_patch(d->ds, (uint32_t)(n / 4), (const uint32_t *)p, &t)
+                   : hm_docset_views(d->ds, (uint32_t)(n / 4), (const uint32_t *)p, &t);
+    if (st) return throw_status(env, d->engine, st, patch ? "hm_docset_get_patch" : "hm_docset_views");
+    size_t len = 0;
+    const char *s = hm_text_data(t, &len);
+    napi_value js;
+    napi_create_string_utf8(env, s, len, &js);
+    hm_text_free(t);
+    return js;
+}
+static napi_value DocsetViews(napi_env env, napi_callback_info info) { return docset_states(env, info, 0); }
+static napi_value DocsetGetPatch(napi_env env, napi_callback_info info) { return docset_states(env, info, 1); }
+
 /* docsetMissingChanges(docset, ids Uint32Array, entryOff Uint32Array [n + 1], actorIds Buffer (the
  * entries' actor ids, UTF-8, end to end), actorOff Uint32Array [entries + 1], seqs Float64Array,
  * flags) -> JSON text [[log indices in history order], ...], one array per request (the changes a
@@ -1472,7 +1496,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"waitAsync", WaitAsync}, {"readRegs", ReadRegs},
         {"docsetCreate", DocsetCreate}, {"docsetOpen", DocsetOpen}, {"docsetApply", DocsetApply}, {"docsetApplyPacked", DocsetApplyPacked},
         {"docsetHistoryPrefix", DocsetHistoryPrefix}, {"docsetClockUpdate", DocsetClockUpdate},
-        {"docsetView", DocsetView}, {"docsetBlocked", DocsetBlocked}, {"docsetWaiting", DocsetWaiting},
+        {"docsetView", DocsetView}, {"docsetViews", DocsetViews}, {"docsetGetPatch", DocsetGetPatch}, {"docsetBlocked", DocsetBlocked}, {"docsetWaiting", DocsetWaiting},
         {"docsetMissingChanges", DocsetMissingChanges}, {"docsetFields", DocsetFields}, {"docsetMaterialize", DocsetMaterialize}, {"docsetFork", DocsetFork}, {"docsetMergeFrom", DocsetMergeFrom}, {"docsetMaterializePatch", DocsetMaterializePatch}, {"docsetMaterializePatchEx", DocsetMaterializePatchEx}, {"docsetMaterializePatchAt", DocsetMaterializePatchAt}, {"docsetInfo", DocsetInfo}, {"docsetStats", DocsetStats},
         {"cursorsCreate", CursorsCreate}, {"cursorsReserve", CursorsReserve}, {"cursorsUpdate", CursorsUpdate},
         {"cursorsGet", CursorsGet}, {"cursorsEntry", CursorsEntry}, {"cursorsDocsWithActors", CursorsDocsWithActors},

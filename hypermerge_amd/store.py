@@ -916,6 +916,36 @@ class DocStore:
         base = (rows[:int(tot[0])], surv[:int(tot[1])], rng[:n], fl[:n])
         return base + (index[:int(tot[0])],) if lists else base
 
+    def state_sizes(self, handles) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """hm_store_state_sizes: ([n, 2] state rows / survivor rows per request, flags [n], their [2] totals)."""
+        hs = np.ascontiguousarray(handles, np.uint32)
+        n = len(hs)
+        cnt, fl, tot = np.zeros((max(n, 1), 2), np.uint32), np.zeros(max(n, 1), np.uint32), np.zeros(2, np.uint64)
+        self._check(self._L.hm_store_state_sizes(self._h, n, _p(hs), _p(cnt), _p(fl), _p(tot)), "hm_store_state_sizes")
+        return cnt[:n], fl[:n], tot
+
+    def state(self, handles, cap=None, clocks=False):
+        """hm_store_state: what the documents `handles` (a handle may repeat) hold now, in one device
+        call: per live register (n_surv > 0, obj known) one STATE_ROW_DT row in ascending register id,
+        request after request, and the survivors in row order (winner first).  Returns (rows, survivors
+        SURV_RESULT_DT, ranges [n, 4] = first row, rows, first survivor, survivors per request, flags
+        [n]); a request flagged ST_BAD_ROWS has no rows.  cap = (rows, survivors) the tables hold; None:
+        the sizes are asked first.  clocks=True: the requests' opSet.clock and opSet.deps rows
+        ([n, a_stride] each) as a fifth and sixth element."""
+        from .engine import CStateOut, STATE_ROW_DT
+        hs = np.ascontiguousarray(handles, np.uint32)
+        n = len(hs)
+        if cap is None:
+            cap = tuple(int(x) for x in self.state_sizes(hs)[2]) if n else (0, 0)
+        rows, surv = np.zeros(max(cap[0], 1), STATE_ROW_DT), np.zeros(max(cap[1], 1), SURV_RESULT_DT)
+        rng, fl, tot = np.zeros((max(n, 1), 4), np.uint32), np.zeros(max(n, 1), np.uint32), np.zeros(2, np.uint64)
+        ck, hd = np.zeros((max(n, 1), self.S), np.uint32), np.zeros((max(n, 1), self.S), np.uint32)
+        out = CStateOut(cap[0], cap[1], rows.ctypes.data, surv.ctypes.data, rng.ctypes.data, fl.ctypes.data)
+        self._check(self._L.hm_store_state(self._h, n, _p(hs), ctypes.byref(out), _p(ck) if clocks else None,
+                                           _p(hd) if clocks else None, _p(tot)), "hm_store_state")
+        base = (rows[:int(tot[0])], surv[:int(tot[1])], rng[:n], fl[:n])
+        return base + (ck[:n], hd[:n]) if clocks else base
+
     def set_min_clock(self, h: int, clock: Dict[str, int]) -> None:
         """minimumClock (actor id -> seq); its actors must already be in the document's actor table."""
         e = self.enc[h]

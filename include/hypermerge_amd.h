@@ -805,6 +805,67 @@ int hm_op_diffs_at_host(hm_engine *e, const hm_batch *b, const hm_results *r, ui
                         const uint32_t *clock_rows, const hm_op_diff_out *out, uint32_t *out_index,
                         uint64_t *out_totals, uint32_t opts);
 
+/* The current state of many documents in one call: a stream compaction of each request's live
+ * registers (what hm_doc_read hands out one document at a time, without the dead registers and the
+ * survivor slack).  Request i = document doc_handles[i] (a handle may repeat).  A register is live
+ * when n_surv > 0, obj != HM_NONE and obj < n_objs; one hm_state_row per live register, in ascending
+ * register id, request after request; the survivors are copied in row order (op, vtag and value
+ * unchanged), wherever the incremental path left them inside the document's slots.  Nothing is
+ * re-merged and the device needs no object types: placing list elements by `index` is the
+ * consumer's part. */
+typedef struct {          /* 20 B, five 32-bit words */
+    uint32_t reg;         /* document-local register id */
+    uint32_t obj;         /* as hm_reg_result.obj */
+    int32_t  index;       /* as hm_reg_result.list_index (-1: not a visible list element) */
+    uint32_t n_surv;
+    uint32_t surv_off;    /* into the call's hm_surv_result table: winner first, then conflicts */
+} hm_state_row;
+#define HM_ST_BAD_ROWS 1u   /* request flag: a live register's survivors (or the document's register
+                               segment) lie outside the document's slots; the request gets no rows */
+typedef struct {          /* 64 B */
+    uint64_t totals[2];   /* state rows and survivor rows of all requests */
+    uint64_t reserved64[2];
+    uint32_t max_rows, reserved[3], max_surv;   /* the largest request */
+    uint32_t flags;       /* OR of the requests' flags */
+    uint32_t bad;         /* _device form: 1 a handle outside the source */
+    uint32_t pad;
+} hm_state_summary;
+typedef struct {
+    uint32_t cap_rows, cap_surv;   /* rows the two tables hold */
+    hm_state_row   *rows;          /* [cap_rows] request order, ascending register id within a request */
+    hm_surv_result *surv;          /* [cap_surv] row order */
+    uint32_t       *range;         /* [4n] (first row, rows, first survivor, survivors) per request */
+    uint32_t       *flags;         /* [n] HM_ST_* per request */
+} hm_state_out;
+/* The count pass alone: out_counts [2n] = state rows, survivor rows per request, out_flags [n],
+ * out_totals [2] the sums (each may be NULL).  HM_ERR_INVALID: a handle outside the store.  No batch
+ * in flight. */
+int hm_store_state_sizes(hm_store *s, uint32_t n, const uint32_t *doc_handles, uint32_t *out_counts, uint32_t *out_flags,
+                         uint64_t *out_totals);
+/* The rows as host tables (out->range and out->flags are required, the two tables when their
+ * capacity is not 0).  out_clock / out_heads (optional, [n * a_stride]): the requests' opSet.clock and
+ * opSet.deps rows, gathered by the same launches.  out_totals [2] (optional) = rows needed per table;
+ * HM_ERR_NOMEM with out_totals filled and no other output written when one exceeds its capacity (or
+ * the call's rows reach 2^32); HM_ERR_INVALID (outputs untouched) for a handle outside the store; a
+ * call between submit and wait is refused.  n == 0 launches nothing. */
+int hm_store_state(hm_store *s, uint32_t n, const uint32_t *doc_handles, const hm_state_out *out, uint32_t *out_clock,
+                   uint32_t *out_heads, uint64_t *out_totals);
+/* The same over a merged cold batch (b's docs, r's docs / regs / surv and, when asked for, clock /
+ * heads), everything in device memory, enqueued on `stream` (NULL = the engine's) without
+ * synchronising.  Request i = document doc_index[i] of b (NULL: document i); a document whose status
+ * is not HM_OK offers nothing.  *out_summary (device) is valid after synchronising; when a total
+ * exceeds its capacity nothing is written to out, out_clock or out_heads.  `work` = device memory of
+ * hm_state_work_bytes(n) bytes, 16-byte aligned as r->regs and r->surv must be (HM_ERR_INVALID
+ * otherwise); afterwards its first 4n words are the per-request counts (rows, survivors, 0, 0) and
+ * the next 4n their offsets.  n == 0: *out_summary is zeroed and nothing else is touched. */
+size_t hm_state_work_bytes(uint32_t n);
+int hm_state_device(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                    const hm_state_out *out, uint32_t *out_clock, uint32_t *out_heads, hm_state_summary *out_summary,
+                    void *work, void *stream);
+/* _host: host tables in, host rows out (staged, synchronous), errors as hm_store_state. */
+int hm_state_host(hm_engine *e, const hm_batch *b, const hm_results *r, uint32_t n, const uint32_t *doc_index,
+                  const hm_state_out *out, uint32_t *out_clock, uint32_t *out_heads, uint64_t *out_totals);
+
 /* The fields a proposed local change touches (the undo bookkeeping of Automerge 0.12
  * applyLocalChange, src/DocBackend.ts:187-205: applyAssign's recordUndo reads fieldOps of every
  * (obj, key) the request assigns and tests isConcurrent against the request), read off the resident
@@ -1164,6 +1225,19 @@ int hm_docset_merge_from(hm_docset *ds, uint32_t n, const uint32_t *dst_docs, co
 int hm_docset_merge_stats(const hm_docset *ds, uint64_t *out2);
 /* the merged document: {uuid: {"type", "keys": [[key, entry]], "elems": [[elemId, entry]]}} */
 int hm_docset_view(hm_docset *ds, uint32_t doc, hm_text **out);
+/* the merged documents docs[0..n) (a document may repeat) as a JSON array: element i is byte for byte
+ * hm_docset_view(docs[i]).  One hm_store_state call per stride class instead of a read per
+ * document; the documents render on the docset's host threads.  A document not placed yet renders
+ * as Backend.init().  HM_ERR_DEVICE: state rows that are not a merge's (a list element's index at
+ * or past its object's elements, two elements at one index, survivors outside a document's slots). */
+int hm_docset_views(hm_docset *ds, uint32_t n, const uint32_t *docs, hm_text **out);
+/* Backend.getPatch for many documents, from the same call: a JSON array of {"doc": id, "history":
+ * history.size, "patch": {"clock", "deps", "canUndo": false, "canRedo": false, "diffs"}}.  clock /
+ * deps are the documents' opSet.clock / opSet.deps rows; diffs build the document from an empty one:
+ * a create for every object of the view but ROOT, in view order, then per object its `set` diffs in
+ * key order and its `insert` diffs (index, elemId) in element order.  No per-op row is read: the
+ * call is the same whatever the docset's patch flags are. */
+int hm_docset_get_patch(hm_docset *ds, uint32_t n, const uint32_t *docs, hm_text **out);
 /* counters: calls, documents, class moves, net patches from the hit registers, net patches from every
  * register, per-op patches, per-op replays whose registers differ from the device's merged state
  * (always 0 unless the renderer and the kernels disagree) */

@@ -48,14 +48,20 @@ def build_gpu(force: bool = False) -> str:
         # ... and its merge_large object (HM_PATH_CENSUS counts the outcome of every layout decision of
         # merge_large_kernel, read by hm_debug_large_paths); libhmgpu.so is linked from `objs` alone
         chk_large_o = os.path.join(objdir, "merge_large_check.hip.o")
+        # ... and its inc_kernels object (HM_INC_CENSUS counts every exit of the incremental apply passes
+        # by its cause, read by hm_debug_inc_paths)
+        chk_inc_o = os.path.join(objdir, "inc_kernels_check.hip.o")
         jobs = [[HIPCC] + flags + ["-c", "-o", o, os.path.join(CSRC, src)] for src, o in zip(GPU_SRCS, objs)]
         jobs.append([HIPCC] + flags + ["-DHM_ASYNC_CHECK=1", "-c", "-o", chk_o, os.path.join(CSRC, "merge_kernels.hip")])
         jobs.append([HIPCC] + flags + ["-DHM_PATH_CENSUS=1", "-c", "-o", chk_large_o, os.path.join(CSRC, "merge_large.hip")])
+        jobs.append([HIPCC] + flags + ["-DHM_INC_CENSUS=1", "-c", "-o", chk_inc_o, os.path.join(CSRC, "inc_kernels.hip")])
         with ThreadPoolExecutor(min(8, len(jobs))) as ex:
             list(ex.map(_run, jobs))
         _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out] + objs + ["-ldl"])
-        _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", os.path.join(LIBDIR, "libhmgpu_check.so"), chk_o, chk_large_o] +
-             [o for o in objs if not o.endswith((os.sep + "merge_kernels.hip.o", os.sep + "merge_large.hip.o"))] + ["-ldl"])
+        _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", os.path.join(LIBDIR, "libhmgpu_check.so"), chk_o, chk_large_o,
+              chk_inc_o] +
+             [o for o in objs if not o.endswith((os.sep + "merge_kernels.hip.o", os.sep + "merge_large.hip.o",
+                                                 os.sep + "inc_kernels.hip.o"))] + ["-ldl"])
     return out
 
 

@@ -33,6 +33,24 @@ enum { INC_DONE = 0, INC_DEFER = 1, INC_BAIL = 2 };
 constexpr uint32_t NC = HM_INC_MAX_NEW_C;     // new changes per document and submit (allDeps rows in registers)
 constexpr uint32_t TB = 8;                    // fold sources whose allDeps rows are loaded together
 
+// The exit census (check build only: hm_inc_pass / hm_inc_slot in store_kernels.h, read by
+// hm_debug_inc_paths): one lane of the group or wave (the document's lane in the lane pass) counts
+// each return below by its cause.  Nothing reads the table on the device; with HM_INC_CENSUS = 0
+// every macro expands to nothing.
+#ifndef HM_INC_CENSUS
+#define HM_INC_CENSUS 0
+#endif
+#if HM_INC_CENSUS
+__device__ unsigned long long hm_inc_cen[HM_IP_N][HM_IS_N];
+#define CEN(lead, pass, slot) do { if (lead) atomicAdd(&hm_inc_cen[pass][slot], 1ull); } while (0)
+#define CEN_PARAM , uint32_t cpass = 0u
+#define CEN_ARG(x) , (x)
+#else
+#define CEN(lead, pass, slot)
+#define CEN_PARAM
+#define CEN_ARG(x)
+#endif
+
 // lanes [base, base + G) of the wave hold one document; every group-level branch is uniform
 // within the group (shuffles and ballots are then well defined for it)
 template <int G>
@@ -130,7 +148,7 @@ __device__ __forceinline__ uint32_t list_at(const Grp<G> &g, uint32_t nl, uint32
 template <int G>
 __device__ int list_plan(const Grp<G> &g, const AppendDesc &D, const IncArgs &A, const IncState &I, uint32_t nno,
                          uint32_t o_act, uint32_t o_reg, uint32_t o_par, uint32_t o_elem, bool lst, uint32_t li,
-                         uint32_t opactor, uint2 dir, uint32_t *lscr, ListPlan &lp) {
+                         uint32_t opactor, uint2 dir, uint32_t *lscr, ListPlan &lp CEN_PARAM) {
     const uint32_t gl = g.gl, n_el = I.pad[0], nl = I.pad[1];
     // the lists' bases (lane k): the counts before list k
     const uint32_t ck = gl < nl ? dir.y : 0u;
@@ -159,7 +177,7 @@ __device__ int list_plan(const Grp<G> &g, const AppendDesc &D, const IncArgs &A,
     if (root && o_par != HM_HEAD) pold = o_par < D.n_old_r ? A.epos[D.src_r + o_par] : HM_NONE;
     if (eop && ecr == HM_NONE) eold = o_reg < D.n_old_r ? A.epos[D.src_r + o_reg] : HM_NONE;
     bad |= (root && o_par != HM_HEAD && (pold < lb || pold >= lb + lc)) || (eop && ecr == HM_NONE && (eold < lb || eold >= lb + lc));
-    if (g.bits(bad)) return INC_BAIL;
+    if (g.bits(bad)) { CEN(gl == 0, cpass, HM_IS_BAIL_LP_PARENT); return INC_BAIL; }
     // the anchor: its insertion point (after the old parent, or the list's start for '_head') and a
     // key that orders anchors by insertion point, then an element's before the '_head's at the same
     // point (the end of one list is the start of the next), then '_head's by list (empty lists
@@ -171,7 +189,7 @@ __device__ int list_plan(const Grp<G> &g, const AppendDesc &D, const IncArgs &A,
     if (root && ins_at < lb + lc) nxt = A.lorder[D.src_r + ins_at];
     if (eop && ecr == HM_NONE) at_e = A.lorder[D.src_r + eold];
     bad = (root && o_par != HM_HEAD && at_p != o_par) || (eop && ecr == HM_NONE && at_e != o_reg);
-    if (g.bits(bad)) return INC_BAIL;
+    if (g.bits(bad)) { CEN(gl == 0, cpass, HM_IS_BAIL_LP_STALE); return INC_BAIL; }
     // under an old parent (or '_head') a new element that does not sort before the parent's first
     // child (a concurrent insert at the same place with a smaller lamport key) goes before the
     // parent's first child with a smaller key, or at the end of the parent's subtree: the group
@@ -202,7 +220,7 @@ __device__ int list_plan(const Grp<G> &g, const AppendDesc &D, const IncArgs &A,
             const uint64_t sm = g.bits(stop);
             if (sm) found = j0 + (uint32_t)__builtin_ctzll(sm);
         }
-        if (g.bits(dup)) return INC_BAIL;                     // (the same elemId twice: the re-merge reports it)
+        if (g.bits(dup)) { CEN(gl == 0, cpass, HM_IS_BAIL_LP_DUP); return INC_BAIL; }   // (the same elemId twice: the re-merge reports it)
         if (gl == k) ins_at = found;
     }
     const uint32_t akey = root ? (ins_at << 4) | (o_par == HM_HEAD ? 8u | lix : 0u) : 0u;
@@ -215,7 +233,7 @@ __device__ int list_plan(const Grp<G> &g, const AppendDesc &D, const IncArgs &A,
             const uint32_t ak = g.sh(akey, k), pk = g.sh(o_par, k);
             clash |= root && ak == akey && pk != o_par;
         }
-        if (g.bits(clash)) return INC_BAIL;
+        if (g.bits(clash)) { CEN(gl == 0, cpass, HM_IS_BAIL_LP_CLASH); return INC_BAIL; }
     }
 
     // subtree sizes in the round's forest: every element counts itself at each of its ancestors
@@ -414,7 +432,7 @@ __device__ __forceinline__ void inc_append(const Grp<G> &g, const AppendDesc &D,
 
 template <int G, bool LS = false>
 __device__ int inc_doc(const AppendDesc &D, const IncArgs &A, uint4 *ssv, uint2 *smt, uint32_t *lscr, bool appended = false,
-                        uint32_t bi = HM_NONE) {
+                        uint32_t bi = HM_NONE CEN_PARAM) {
     const Grp<G> g;
     const uint32_t gl = g.gl;
     const uint32_t S = A.S, h = D.handle, NA = D.n_actors, nnc = D.n_new_c, nno = D.n_new_o, nnd = D.n_new_d;
@@ -425,8 +443,11 @@ __device__ int inc_doc(const AppendDesc &D, const IncArgs &A, uint4 *ssv, uint2 
     // anything can hand the document over, since the re-merge reads them from the log
     const bool moved = D.src_c != D.dst_c || D.src_d != D.dst_d || D.src_o != D.dst_o;
     if (!moved && !appended) inc_append<G>(g, D, A);
-    if (nnc == 0 || NA > S || S > G || D.n_old_r > D.n_r) return INC_BAIL;
-    if (nnc > NC || nno > G || nnd > G) return FAILG;       // (the tiled wave pass takes longer rounds)
+    if (nnc == 0 || NA > S || S > G || D.n_old_r > D.n_r) { CEN(gl == 0, cpass, HM_IS_BAIL_DESC); return INC_BAIL; }
+    if (nnc > NC || nno > G || nnd > G) {                   // (the tiled wave pass takes longer rounds)
+        CEN(gl == 0, cpass, nnc > NC ? HM_IS_LONG_CHANGES : (nno > G ? HM_IS_LONG_OPS : HM_IS_LONG_DEPS));
+        return FAILG;
+    }
 
     // ---- level 2: everything that depends only on the descriptor ----
     const IncState I = A.ist[h];
@@ -467,7 +488,7 @@ __device__ int inc_doc(const AppendDesc &D, const IncArgs &A, uint4 *ssv, uint2 
         const int idx = (int)D.n_old_c - 1 - (int)(k * G + gl);
         tk[k] = idx >= 0 ? A.ckey[D.src_c + idx] : 0u;
     }
-    if ((I.flags & (HM_IST_VALID | HM_IST_NOCKEY)) != HM_IST_VALID) return INC_BAIL;
+    if ((I.flags & (HM_IST_VALID | HM_IST_NOCKEY)) != HM_IST_VALID) { CEN(gl == 0, cpass, HM_IS_BAIL_STATE); return INC_BAIL; }
 
     // ---- the new rows: grouped by change, in order, after the old rows; supported ops ----
     uint32_t sd = gl < nnc ? cnd : 0u, so = gl < nnc ? cno : 0u;
@@ -516,16 +537,25 @@ __device__ int inc_doc(const AppendDesc &D, const IncArgs &A, uint4 *ssv, uint2 
                                     // an object other than ROOT must be a map / table the log (or an
                                     // earlier op of this round) created
                                     (!mk && !lst && o_obj != 0 && (o_obj >= 64 || !((known >> o_obj) & 1ull))));
-    if (g.bits(bad_c || bad_o) || total_o != nno || total_d != nnd) return INC_BAIL;
+    if (g.bits(bad_c || bad_o) || total_o != nno || total_d != nnd) {
+#if HM_INC_CENSUS
+        // the first cause in this order: rows, object creation in a list document, another make, an op
+        const bool c_ml = mk && (D.inc & HM_DINC_LISTS), c_mk = mk && (o_obj == 0 || o_obj >= 64 || ((known >> o_obj) & 1ull));
+        const uint32_t c_slot = (g.bits(bad_c) || total_o != nno || total_d != nnd) ? HM_IS_BAIL_ROWS
+                                : (g.bits(bad_o && c_ml) ? HM_IS_BAIL_MAKE_LISTS : (g.bits(bad_o && c_mk) ? HM_IS_BAIL_MAKE : HM_IS_BAIL_OP));
+        CEN(gl == 0, cpass, c_slot);
+#endif
+        return INC_BAIL;
+    }
     const bool any_list = g.bits(lst) != 0;
-    if (!LST && any_list) return INC_DEFER;                   // list / text ops: one document per wave
+    if (!LST && any_list) { CEN(gl == 0, cpass, HM_IS_DEFER_LIST); return INC_DEFER; }   // list / text ops: one document per wave
     // integer counters: |base| + sum|inc| of every counter stays <= 2^53 (the re-merge's exact rule)
     unsigned long long cadd = (gl < nno && o_vt == HM_V_INT &&
                                (o_act == HM_INC || (o_act == HM_SET && o_dt == HM_DT_COUNTER))) ? abs64(oval) : 0ull;
 #pragma unroll
     for (uint32_t d = 1; d < (uint32_t)G; d <<= 1) cadd += (unsigned long long)__shfl_xor((long long)cadd, d, G);
     const unsigned long long cabs = I.cabs + cadd;
-    if (cabs > TWO53) return INC_BAIL;
+    if (cabs > TWO53) { CEN(gl == 0, cpass, HM_IS_BAIL_COUNTER); return INC_BAIL; }
 
     // ---- level 3a: the hit registers' rows (lane = op) ----
     hm_reg_result rr = {0u, 0u, -1, HM_NONE};
@@ -538,24 +568,24 @@ __device__ int inc_doc(const AppendDesc &D, const IncArgs &A, uint4 *ssv, uint2 
     uint32_t ckr = ck, nt = 0;
     for (uint32_t j = 0; j < nnc; j++) {
         const uint32_t a = g.sh(ca, j), q = g.sh(cq, j), nd = g.sh(cnd, j), d0 = g.sh(xd, j);
-        if (g.sh(ckr, a) + 1u != q) return INC_BAIL;           // a duplicate, or not ready: the queue decides
+        if (g.sh(ckr, a) + 1u != q) { CEN(gl == 0, cpass, HM_IS_BAIL_NOT_READY); return INC_BAIL; }   // a duplicate, or not ready: the queue decides
         const uint32_t t0 = nt;
         bool own = false;
         for (uint32_t t = 0; t <= nd; t++) {
             uint32_t da, dq;
             if (t < nd) {
                 da = g.sh(dpa, d0 + t); dq = g.sh(dpq, d0 + t);
-                if (da >= NA) return INC_BAIL;
+                if (da >= NA) { CEN(gl == 0, cpass, HM_IS_BAIL_ROWS); return INC_BAIL; }
                 if (da == a) { dq = q - 1; own = true; }       // deps ∪ {actor: seq - 1}: the key keeps its place
             } else {
                 if (own) break;
                 da = a; dq = q - 1;
             }
-            if (g.sh(ckr, da) < dq) return INC_BAIL;
+            if (g.sh(ckr, da) < dq) { CEN(gl == 0, cpass, HM_IS_BAIL_NOT_READY); return INC_BAIL; }
             if (dq == 0) continue;
             const uint64_t m = g.bits(gl < j && ca == da && cq == dq);
             const uint32_t src1 = m ? (uint32_t)__builtin_ctzll(m) + 1u : 0u;
-            if (nt >= 2u * G) return FAILG;
+            if (nt >= 2u * G) { CEN(gl == 0, cpass, HM_IS_FOLD_STEPS); return FAILG; }
             const uint32_t w = da | (src1 << 8) | (j << 16);
             if (gl == (nt & (G - 1))) {
                 if (nt < (uint32_t)G) { tA0 = w; tQ0 = dq; } else { tA1 = w; tQ1 = dq; }
@@ -579,12 +609,14 @@ __device__ int inc_doc(const AppendDesc &D, const IncArgs &A, uint4 *ssv, uint2 
             const uint64_t m = g.bits(tk[k] == want);
             if (m && found < 0) found = (int)D.n_old_c - 1 - (int)(k * G + (uint32_t)__builtin_ctzll(m));
         }
+        CEN(gl == 0 && found >= 0, cpass, HM_IS_SRC_TAIL);
+        CEN(gl == 0 && found < 0, cpass, HM_IS_SRC_LOOP);        // (a source the loop misses too: BAIL_NO_SOURCE beside it)
         for (int top = (int)D.n_old_c - 1 - (int)(KT * G); found < 0 && top >= 0; top -= G) {
             const int idx = top - (int)gl;
             const uint64_t m = g.bits(idx >= 0 && A.ckey[D.src_c + idx] == want);
             if (m) found = top - (int)__builtin_ctzll(m);
         }
-        if (found < 0) return INC_BAIL;
+        if (found < 0) { CEN(gl == 0, cpass, HM_IS_BAIL_NO_SOURCE); return INC_BAIL; }
         if (gl == tl) { if (t < (uint32_t)G) tI0 = (uint32_t)found; else tI1 = (uint32_t)found; }
     }
 
@@ -600,7 +632,7 @@ __device__ int inc_doc(const AppendDesc &D, const IncArgs &A, uint4 *ssv, uint2 
         if (g.sh(xo + cno, j) <= gl) oj++;                    // the op's change: ops are grouped by change
     const uint32_t n_old = first ? rr.n_surv : 0u;
     const uint32_t n_up = first ? n_old + push : 0u;           // the list's length after the submit, at most
-    if (g.bits(first && n_up > (uint32_t)G)) return FAILG;
+    if (g.bits(first && n_up > (uint32_t)G)) { CEN(gl == 0, cpass, HM_IS_N_UP); return FAILG; }
     uint32_t s_incl = n_old, g_incl = n_up;
 #pragma unroll
     for (uint32_t d = 1; d < (uint32_t)G; d <<= 1) {
@@ -608,8 +640,8 @@ __device__ int inc_doc(const AppendDesc &D, const IncArgs &A, uint4 *ssv, uint2 
         if (gl >= d) { s_incl += y; g_incl += z; }
     }
     const uint32_t stage_off = s_incl - n_old, tot_old = g.sh(s_incl, G - 1), grow = g.sh(g_incl, G - 1);
-    if (tot_old > 2u * G) return FAILG;
-    if ((unsigned long long)I.s_used + grow > D.o_cap) return INC_BAIL;   // no room: the re-merge repacks
+    if (tot_old > 2u * G) { CEN(gl == 0, cpass, HM_IS_TOT_OLD); return FAILG; }
+    if ((unsigned long long)I.s_used + grow > D.o_cap) { CEN(gl == 0, cpass, HM_IS_BAIL_NO_ROOM); return INC_BAIL; }   // no room: the re-merge repacks
 
     // ---- level 3b: the fold sources' allDeps rows, TB at a time; allDeps / heads / clock of
     //      each new change (applyChange) ----
@@ -653,8 +685,11 @@ __device__ int inc_doc(const AppendDesc &D, const IncArgs &A, uint4 *ssv, uint2 
         if (any_list) {
             // an inserted element's register was never touched: a fresh id, or one the document's
             // declared register count reserved (untouched registers have no object)
-            if (g.bits(lst && o_act == HM_INS && o_reg < D.n_old_r && (rr.obj != HM_NONE || rr.n_surv != 0))) return INC_BAIL;
-            const int rc = list_plan(g, D, A, I, nno, o_act, o_reg, o_par, o_elem, lst, li, g.sh(ca, oj), dir, lscr, lp);
+            if (g.bits(lst && o_act == HM_INS && o_reg < D.n_old_r && (rr.obj != HM_NONE || rr.n_surv != 0))) {
+                CEN(gl == 0, cpass, HM_IS_BAIL_INS_REG);
+                return INC_BAIL;
+            }
+            const int rc = list_plan(g, D, A, I, nno, o_act, o_reg, o_par, o_elem, lst, li, g.sh(ca, oj), dir, lscr, lp CEN_ARG(cpass));
             if (rc != INC_DONE) return rc;
         }
     }
@@ -857,7 +892,7 @@ __device__ int inc_doc(const AppendDesc &D, const IncArgs &A, uint4 *ssv, uint2 
 // A tile after the first that cannot go incremental sends the document to the re-merge, which
 // rewrites every row the earlier tiles wrote.
 template <int G, bool LS = false>
-__device__ int inc_doc_tiled(const AppendDesc &D, const IncArgs &A, uint4 *ssv, uint2 *smt, uint32_t *lscr, uint32_t bi) {
+__device__ int inc_doc_tiled(const AppendDesc &D, const IncArgs &A, uint4 *ssv, uint2 *smt, uint32_t *lscr, uint32_t bi CEN_PARAM) {
     const Grp<G> g;
     const uint32_t gl = g.gl;
     // (one call site of inc_doc: a second inlined copy costs the common round its occupancy)
@@ -881,7 +916,7 @@ __device__ int inc_doc_tiled(const AppendDesc &D, const IncArgs &A, uint4 *ssv, 
                 if (gl >= d && gl < NC) { so += yo; sd += yd; }
             }
             k = (uint32_t)__popcll(g.bits(gl < NC && c0 + gl < D.n_new_c && so <= (uint32_t)G && sd <= (uint32_t)G));
-            if (k == 0) return INC_BAIL;                      // a change larger than a group: the re-merge
+            if (k == 0) { CEN(gl == 0, cpass, HM_IS_BAIL_TILE_BIG); return INC_BAIL; }   // a change larger than a group: the re-merge
             to = g.sh(so, k - 1); td = g.sh(sd, k - 1);
             T.new_c = D.new_c + c0; T.n_new_c = k; T.new_d = D.new_d + d0; T.n_new_d = td; T.new_o = D.new_o + o0; T.n_new_o = to;
             T.n_old_c = D.n_old_c + c0; T.n_old_d = D.n_old_d + d0; T.n_old_o = D.n_old_o + o0;
@@ -890,8 +925,9 @@ __device__ int inc_doc_tiled(const AppendDesc &D, const IncArgs &A, uint4 *ssv, 
                 T.n_old_r = D.n_r;                            // (the first tile wrote every new register's row)
             }
         }
-        const int rc = inc_doc<G, LS>(T, A, ssv, smt, lscr, tiled, bi);
-        if (rc != INC_DONE) return first ? rc : INC_BAIL;
+        CEN(gl == 0, cpass, HM_IS_TILES);
+        const int rc = inc_doc<G, LS>(T, A, ssv, smt, lscr, tiled, bi CEN_ARG(cpass));
+        if (rc != INC_DONE) { CEN(gl == 0 && !first, cpass, HM_IS_TILE_LATER_FAILED); return first ? rc : INC_BAIL; }
         c0 += k; d0 += td; o0 += to;
         if (c0 >= D.n_new_c) return INC_DONE;
         __threadfence_block();                                // this tile's rows, then the next tile's reads
@@ -931,8 +967,13 @@ __global__ __launch_bounds__(256, 1) void inc_group_kernel(IncArgs A_in) {
         if (G == 64 && tl != TL) continue;                             // (the other launch's document)
         if (HM_INC_LIST_GROUPS && G < 64 && ((D.inc & HM_DINC_LISTS) != 0) != LS) continue;   // (the other instantiation's)
         int rc;
-        if constexpr (TL) rc = inc_doc_tiled<G, LS>(D, A, s_sv[grp], s_mt[grp], s_ls[LST ? grp : 0], di);
-        else rc = inc_doc<G, LS>(D, A, s_sv[grp], s_mt[grp], s_ls[LST ? grp : 0], false, di);
+#if HM_INC_CENSUS
+        constexpr uint32_t cpass = G == 8 ? HM_IP_GROUP8 : (G == 16 ? HM_IP_GROUP16 : (TL ? HM_IP_WAVE_TILED : HM_IP_WAVE));
+#endif
+        CEN(gl == 0, cpass, HM_IS_ENTER);
+        if constexpr (TL) rc = inc_doc_tiled<G, LS>(D, A, s_sv[grp], s_mt[grp], s_ls[LST ? grp : 0], di CEN_ARG(cpass));
+        else rc = inc_doc<G, LS>(D, A, s_sv[grp], s_mt[grp], s_ls[LST ? grp : 0], false, di CEN_ARG(cpass));
+        CEN(gl == 0 && rc == INC_DONE, cpass, HM_IS_DONE);
         if (rc == INC_DONE && gl == 0 && A.gdone) A.gdone[di] = 1;
         if (rc != INC_DONE && gl == 0) {
             if (rc == INC_DEFER && A.defer) A.defer[1 + atomicAdd(&A.defer[0], 1u)] = di;
@@ -954,13 +995,16 @@ __global__ __launch_bounds__(256, 1) void inc_group_kernel(IncArgs A_in) {
 //   validation (before any store but the log append): every change causally ready in arrival
 //   order against the resident clock, every op a map op on ROOT / a map of the log (or a
 //   makeMap / makeTable of a new object), counters inside the exact-integer bound.  A document
-//   that fails a check with a chance in the group / wave pass (list ops, a moved segment) is
-//   deferred to it untouched; anything else goes to the re-merge (bail).  After the first store
+//   that fails a check goes to the re-merge, whether it bails or defers (inc_lane_kernel lists
+//   both in `bail`: the group passes hold a round in registers).  The defers (list ops) are dead
+//   through the store: plan_kernel routes no document with lists here; a moved segment is copied
+//   by the lane itself.  After the first store
 //   the only exits are a register of more than LSV survivors, a full slot area or a fold source
 //   missing from the log — the document is then re-merged, which rewrites every row the lane
 //   wrote (the new rows are in the log before anything else happens).
 constexpr uint32_t LSV = 8;    // survivors of a register the lane path holds (more: re-merge)
 constexpr uint32_t LKF = 2;    // fold sources resolved and loaded together
+#define LPASS(S) ((S) == 8 ? HM_IP_LANE8 : HM_IP_LANE16)      // (the census row of inc_lane_kernel<S>)
 
 // v[i] of a register array by selects (each element made opaque first: a select between two
 // loads of one array is otherwise folded into a load through a selected pointer, which sends the
@@ -1009,7 +1053,7 @@ __device__ __forceinline__ int lane_assign(const AppendDesc &D, const IncArgs &A
                                            uint32_t vhi, uint32_t op_local, const hm_reg_result &rr, uint32_t &used,
                                            int32_t &dsurv) {
     const uint32_t n = rr.n_surv;
-    if (n > LSV) return INC_BAIL;
+    if (n > LSV) { CEN(true, LPASS(S), HM_IS_BAIL_LSV); return INC_BAIL; }
     uint4 x[LSV + 1];
     uint2 m[LSV + 1];
 #pragma unroll
@@ -1049,7 +1093,7 @@ __device__ __forceinline__ int lane_assign(const AppendDesc &D, const IncArgs &A
     if (act == HM_SET || act == HM_LINK) { keep |= 1u << LSV; cnt++; }
     const uint32_t off = cnt <= n ? rr.surv_off : used;
     if (cnt > n) {
-        if ((unsigned long long)used + cnt > D.o_cap) return INC_BAIL;    // no room: the re-merge repacks
+        if ((unsigned long long)used + cnt > D.o_cap) { CEN(true, LPASS(S), HM_IS_BAIL_NO_ROOM); return INC_BAIL; }   // no room: the re-merge repacks
         used += cnt;
     }
 #pragma unroll
@@ -1120,9 +1164,9 @@ __device__ int inc_lane(const AppendDesc &D, const IncArgs &A, uint32_t bi) {
 #pragma unroll 4
         for (uint32_t i = 0; i < 2 * nno; i++) do4[i] = so4[i];
     }
-    if (nnc == 0 || NA > (uint32_t)S || D.n_old_r > D.n_r) return INC_BAIL;
+    if (nnc == 0 || NA > (uint32_t)S || D.n_old_r > D.n_r) { CEN(true, LPASS(S), HM_IS_BAIL_DESC); return INC_BAIL; }
     const IncState I = A.ist[h];
-    if ((I.flags & (HM_IST_VALID | HM_IST_NOCKEY | HM_IST_LIST)) != HM_IST_VALID) return INC_BAIL;
+    if ((I.flags & (HM_IST_VALID | HM_IST_NOCKEY | HM_IST_LIST)) != HM_IST_VALID) { CEN(true, LPASS(S), HM_IS_BAIL_STATE); return INC_BAIL; }
     // segments the append moved (append_kernel copied the log rows, the new ones included): the
     // per-change, survivor and register rows follow
     if (D.src_c != D.dst_c) {
@@ -1168,13 +1212,15 @@ __device__ int inc_lane(const AppendDesc &D, const IncArgs &A, uint32_t bi) {
         for (uint32_t j = 0; j < nnc; j++) {
             const hm_change_row c = A.st_changes[D.new_c + j];
             if (c.actor >= NA || c.seq == 0 || c.seq >= (1u << 24) || c.dep_off - D.new_d != xd || c.op_first - D.new_o != xo ||
-                xd + c.n_deps > nnd || xo + c.n_ops > nno)
+                xd + c.n_deps > nnd || xo + c.n_ops > nno) {
+                CEN(true, LPASS(S), HM_IS_BAIL_ROWS);
                 return INC_BAIL;
-            if (lsel<S>(cur, c.actor) + 1u != c.seq) return INC_BAIL;      // a duplicate, or not ready: the queue decides
+            }
+            if (lsel<S>(cur, c.actor) + 1u != c.seq) { CEN(true, LPASS(S), HM_IS_BAIL_NOT_READY); return INC_BAIL; }   // a duplicate, or not ready: the queue decides
             for (uint32_t t = 0; t < c.n_deps; t++) {
                 const hm_dep_row d = A.st_deps[D.new_d + xd + t];
-                if (d.actor >= NA) return INC_BAIL;
-                if (d.actor != c.actor && lsel<S>(cur, d.actor) < d.seq) return INC_BAIL;
+                if (d.actor >= NA) { CEN(true, LPASS(S), HM_IS_BAIL_ROWS); return INC_BAIL; }
+                if (d.actor != c.actor && lsel<S>(cur, d.actor) < d.seq) { CEN(true, LPASS(S), HM_IS_BAIL_NOT_READY); return INC_BAIL; }
             }
             for (uint32_t k = 0; k < c.n_ops; k++) {
                 const uint4 *src = reinterpret_cast<const uint4 *>(A.st_ops + D.new_o + xo + k);
@@ -1185,29 +1231,30 @@ __device__ int inc_lane(const AppendDesc &D, const IncArgs &A, uint32_t bi) {
                     // a new map: its id must be fresh (a list's id is not in mapmask: documents with
                     // lists take the group pass, which hands object creation to the re-merge)
                     if (lists) { defer = 1; continue; }
-                    if (obj == 0 || obj >= 64 || obj >= D.n_objs || ((mm >> obj) & 1ull)) return INC_BAIL;
+                    if (obj == 0 || obj >= 64 || obj >= D.n_objs || ((mm >> obj) & 1ull)) { CEN(true, LPASS(S), HM_IS_BAIL_MAKE); return INC_BAIL; }
                     mm |= 1ull << obj;
                     continue;
                 }
                 if (act == HM_INS || act == HM_MAKE_LIST || act == HM_MAKE_TEXT) { defer = 1; continue; }
-                if (act != HM_SET && act != HM_DEL && act != HM_LINK && act != HM_INC) return INC_BAIL;
-                if (obj >= D.n_objs || reg >= D.n_r) return INC_BAIL;
+                if (act != HM_SET && act != HM_DEL && act != HM_LINK && act != HM_INC) { CEN(true, LPASS(S), HM_IS_BAIL_OP); return INC_BAIL; }
+                if (obj >= D.n_objs || reg >= D.n_r) { CEN(true, LPASS(S), HM_IS_BAIL_OP); return INC_BAIL; }
                 if (obj != 0 && (obj >= 64 || !((mm >> obj) & 1ull))) {
                     if (lists) { defer = 1; continue; }              // a list element: the wave pass
+                    CEN(true, LPASS(S), HM_IS_BAIL_OP);
                     return INC_BAIL;
                 }
-                if (act == HM_INC && vt != HM_V_INT && vt != HM_V_FLOAT) return INC_BAIL;
-                if (vt == HM_V_INT && abs64(v) > TWO53) return INC_BAIL;
+                if (act == HM_INC && vt != HM_V_INT && vt != HM_V_FLOAT) { CEN(true, LPASS(S), HM_IS_BAIL_OP); return INC_BAIL; }
+                if (vt == HM_V_INT && abs64(v) > TWO53) { CEN(true, LPASS(S), HM_IS_BAIL_OP); return INC_BAIL; }
                 if (vt == HM_V_INT && (act == HM_INC || (act == HM_SET && dt == HM_DT_COUNTER))) cadd += abs64(v);
             }
             xd += c.n_deps; xo += c.n_ops;
             lput<S>(cur, c.actor, c.seq);
         }
-        if (xd != nnd || xo != nno) return INC_BAIL;
-        if (defer) return INC_DEFER;
+        if (xd != nnd || xo != nno) { CEN(true, LPASS(S), HM_IS_BAIL_ROWS); return INC_BAIL; }
+        if (defer) { CEN(true, LPASS(S), HM_IS_DEFER_LIST); return INC_DEFER; }
     }
     const unsigned long long cabs = I.cabs + cadd;
-    if (cabs > TWO53) return INC_BAIL;
+    if (cabs > TWO53) { CEN(true, LPASS(S), HM_IS_BAIL_COUNTER); return INC_BAIL; }
 
     // ---- apply: registers new to the document start empty (the ops below read their rows) ----
     for (uint32_t r = D.n_old_r; r < D.n_r; r++) {
@@ -1249,6 +1296,7 @@ __device__ int inc_lane(const AppendDesc &D, const IncArgs &A, uint32_t bi) {
                 const uint32_t want = hm_ckey(sa[u], sq[u], true);
 #pragma unroll
                 for (int t = 0; t < 8; t++) if (tail[t] == want && (int)end - 8 + t >= 0) si[u] = end - 8u + (uint32_t)t;
+                CEN(true, LPASS(S), si[u] != HM_NONE ? HM_IS_SRC_TAIL : HM_IS_SRC_LOOP);
                 if (si[u] == HM_NONE) miss |= 1u << u;
             }
             for (int top = (int)end - 9; miss && top >= 0; top -= 8) {
@@ -1264,7 +1312,7 @@ __device__ int inc_lane(const AppendDesc &D, const IncArgs &A, uint32_t bi) {
                     if (si[u] != HM_NONE) miss &= ~(1u << u);
                 }
             }
-            if (miss) return INC_BAIL;
+            if (miss) { CEN(true, LPASS(S), HM_IS_BAIL_NO_SOURCE); return INC_BAIL; }
             uint32_t row[LKF][S];
 #pragma unroll
             for (uint32_t u = 0; u < LKF; u++) {
@@ -1334,7 +1382,9 @@ __global__ __launch_bounds__(256) void inc_lane_kernel(IncArgs A) {
         const AppendDesc D = A.descs[i];
         if ((D.inc & HM_DINC_ROUTE) == 3u) {
             hnd = D.handle;
+            CEN(true, LPASS(S), HM_IS_ENTER);
             rc = inc_lane<S>(D, A, i);
+            CEN(rc == INC_DONE, LPASS(S), HM_IS_DONE);
             if (rc == INC_DONE && A.gdone) A.gdone[i] = 1;
         }
     }
@@ -1406,6 +1456,7 @@ __global__ __launch_bounds__(256) void inc_meta_kernel(MetaArgs a) {
         const DevDoc m = a.dm[h];
         const hm_doc_result r = a.res_docs[h];
         const bool was = HM_IST_COUNTS(a.ist[h].flags);      // (PlanStats.n_valid follows the change)
+        CEN(lane == 0, HM_IP_META, HM_IS_ENTER);
         // (mode 1: a small document with lists re-merges every round — one small-kernel wave either
         // way — so it keeps no incremental state at all)
         if (r.status != HM_OK || r.n_queued != 0 || r.n_surv > m.o_cap ||
@@ -1415,6 +1466,7 @@ __global__ __launch_bounds__(256) void inc_meta_kernel(MetaArgs a) {
                 a.ist[h] = z;
             }
             dv -= was ? 1 : 0;
+            CEN(lane == 0, HM_IP_META, HM_IS_META_DIRTY);
             continue;
         }
         const hm_change_row *ch = a.changes + m.c_off;
@@ -1621,6 +1673,9 @@ __global__ __launch_bounds__(256) void inc_meta_kernel(MetaArgs a) {
                 if (lane < nlst) a.ldir[(size_t)h * LMAX + lane] = make_uint2(lobj, cnt);
             }
         }
+        CEN(lane == 0 && over, HM_IP_META, HM_IS_META_LISTS_OVER);
+        CEN(lane == 0 && nlst && !over && a.lorder && a.ldir && !(flags & HM_IST_LIST), HM_IP_META, HM_IS_META_LIST_REFUSED);
+        CEN(lane == 0, HM_IP_META, wide ? HM_IS_META_NOCKEY : ((flags & HM_IST_LIST) ? HM_IS_META_VALID_LISTS : HM_IS_META_VALID));
         if (lane == 0) {
             IncState st = {};
             st.s_used = r.n_surv; st.flags = flags; st.cabs = cabs; st.mapmask = mask;
@@ -1696,6 +1751,25 @@ hipError_t hm_launch_inc_apply(const IncArgs &A, hipStream_t s) {
         hipLaunchKernelGGL((hmi::inc_group_kernel<64, true>), dim3(grid(A.n, 4) < 1024u ? grid(A.n, 4) : 1024u), dim3(256), 0, s, B);
     }
     return hipGetLastError();
+}
+
+// the exit census, [hm_inc_pass][hm_inc_slot] row-major: copies min(n, HM_IP_N * HM_IS_N) slots and
+// returns that count (0 in the product build, which has no table); reset clears the table
+extern "C" int hm_debug_inc_paths(unsigned long long *out, int n, int reset) {
+#if HM_INC_CENSUS
+    constexpr int NS = (int)HM_IP_N * (int)HM_IS_N;
+    if (!out || n <= 0 || hipDeviceSynchronize() != hipSuccess) return -1;
+    const int k = n < NS ? n : NS;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(hmi::hm_inc_cen), (size_t)k * 8) != hipSuccess) return -1;
+    if (reset) {
+        static const unsigned long long z[NS] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(hmi::hm_inc_cen), z, sizeof z) != hipSuccess) return -1;
+    }
+    return k;
+#else
+    (void)out; (void)n; (void)reset;
+    return 0;
+#endif
 }
 
 extern "C" int hm_debug_meta_stamps(unsigned long long *out8, int reset) {

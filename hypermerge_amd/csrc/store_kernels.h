@@ -177,6 +177,62 @@ struct IncArgs {
 #define HM_INC_TILED_MAX_C 256    // tiles of the group / wave passes (list documents, strides over 16)
 #define HM_INC_TILED_MAX_O 4096
 
+// The exit census of the incremental passes (check build: inc_kernels.hip with HM_INC_CENSUS=1, read
+// by hm_debug_inc_paths as a table [hm_inc_pass][hm_inc_slot]).  One lane of the group, wave or (lane
+// pass) the document's lane counts each point once per document, except the events at the end.
+// tests/inc_edges.py restates which slots one submit of one document moves.
+enum hm_inc_pass {
+    HM_IP_LANE8, HM_IP_LANE16,        // inc_lane_kernel<8> / <16>
+    HM_IP_GROUP8, HM_IP_GROUP16,      // inc_group_kernel<8, false> / <16, false>
+    HM_IP_WAVE, HM_IP_WAVE_TILED,     // inc_group_kernel<64, false> / <64, true>
+    HM_IP_META,                       // inc_meta_kernel
+    HM_IP_N
+};
+enum hm_inc_slot {
+    HM_IS_ENTER,                      // the pass picked the document up (its route and launch filters passed)
+    HM_IS_DONE,                       // rc == INC_DONE
+    // ---- INC_DEFER at G < 64, INC_BAIL at G = 64 (FAILG) ----
+    HM_IS_LONG_CHANGES,               // nnc > NC
+    HM_IS_LONG_OPS,                   // nno > G
+    HM_IS_LONG_DEPS,                  // nnd > G
+    HM_IS_FOLD_STEPS,                 // nt >= 2 * G
+    HM_IS_N_UP,                       // first && n_up > G
+    HM_IS_TOT_OLD,                    // tot_old > 2 * G
+    // ---- INC_DEFER ----
+    HM_IS_DEFER_LIST,                 // !LST && any_list (group); defer (lane: an ins / makeList / makeText, a list element)
+    // ---- INC_BAIL ----
+    HM_IS_BAIL_DESC,                  // nnc == 0 || NA > S || S > G || n_old_r > n_r
+    HM_IS_BAIL_STATE,                 // (I.flags & (VALID | NOCKEY [| LIST, lane])) != VALID
+    HM_IS_BAIL_ROWS,                  // bad_c, total_o != nno, total_d != nnd, a dep's actor >= NA (seq >= 2^24 is here)
+    HM_IS_BAIL_OP,                    // bad_o: an action, value, object, register or elem the pass does not take
+    HM_IS_BAIL_MAKE,                  // bad_o: makeMap / makeTable of object 0, >= 64 or one that exists
+    HM_IS_BAIL_MAKE_LISTS,            // bad_o: mk && (D.inc & HM_DINC_LISTS)
+    HM_IS_BAIL_COUNTER,               // cabs > TWO53
+    HM_IS_BAIL_NOT_READY,             // clock[a] + 1 != q (not ready, or a duplicate); clock[da] < dq
+    HM_IS_BAIL_NO_SOURCE,             // found < 0 (group); miss (lane): fold source not in the log
+    HM_IS_BAIL_NO_ROOM,               // s_used + grow > o_cap (group); used + cnt > o_cap (lane)
+    HM_IS_BAIL_LSV,                   // lane: n > LSV
+    HM_IS_BAIL_INS_REG,               // an ins whose register has an object or survivors
+    HM_IS_BAIL_LP_PARENT,             // list_plan: parent / element outside the op's list (first `bad`)
+    HM_IS_BAIL_LP_STALE,              // list_plan: lorder[pos] does not name the register (second `bad`)
+    HM_IS_BAIL_LP_DUP,                // list_plan: dup (the same elemId twice under one parent)
+    HM_IS_BAIL_LP_CLASH,              // list_plan: clash (anchors of different parents at one point)
+    HM_IS_BAIL_TILE_BIG,              // tile loop: k == 0 (a change larger than a group)
+    // ---- events (not exits: they do not enter ENTER == DONE + sum of exits) ----
+    HM_IS_TILE_LATER_FAILED,          // tile loop: rc != INC_DONE && !first (the failing tile's own exit is counted too)
+    HM_IS_TILES,                      // tile loop: calls of inc_doc, summed
+    HM_IS_SRC_TAIL,                   // fold sources found in tk[] (group) / tail[] (lane)
+    HM_IS_SRC_LOOP,                   // ... found by the loop over older rows
+    // ---- inc_meta_kernel: ENTER, then META_DIRTY or one of VALID / VALID_LISTS / NOCKEY ----
+    HM_IS_META_DIRTY,                 // status != OK || n_queued || n_surv > o_cap || small list document: flags = 0
+    HM_IS_META_VALID,                 // flags == VALID
+    HM_IS_META_VALID_LISTS,           // flags == VALID | LIST
+    HM_IS_META_NOCKEY,                // wide: a seq >= 2^24
+    HM_IS_META_LISTS_OVER,            // event: over (nlst == LMAX and one more list)
+    HM_IS_META_LIST_REFUSED,          // event: lists within LMAX, but `bad` / `!ok`: no HM_IST_LIST
+    HM_IS_N
+};
+
 struct PlanArgs {
     const hm_doc_row *docs;
     const hm_change_row *changes;

@@ -374,6 +374,11 @@ int hm_store_arena_info(hm_store *s, uint64_t out_cap[4], uint64_t out_used[4]);
  * out2[1] = those whose two reads differed (the asynchronous wait was too short); reset zeroes
  * both.  Returns 1 in a check build, 0 in the product build (out2 untouched), < 0 on a HIP error. */
 int hm_debug_async_check(unsigned long long *out2, int reset);
+/* The exit census of the incremental apply passes (check builds): out[pass * slots + slot] =
+ * documents (or events) counted since the last reset, for the passes and slots of hm_inc_pass /
+ * hm_inc_slot (csrc/store_kernels.h); at most n slots are copied; reset zeroes the table.  Returns the
+ * slots copied in a check build, 0 in the product build (out untouched), < 0 on a HIP error. */
+int hm_debug_inc_paths(unsigned long long *out, int n, int reset);
 /* The persistent grid of merge_small_kernel for a host batch (its max_* hints, or its document
  * table when they are all 0): out6[0] = resident one-wave workgroups per CU of the instantiation
  * the launch uses (the smaller of the register and the LDS bound), out6[1] = the device's CUs

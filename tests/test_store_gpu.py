@@ -234,7 +234,7 @@ def test_bad_remap_leaves_store_unchanged(engine):
     ("FC", 60, {}, 2, True, 8),                            # integral and f64 counters, shuffled (queued) arrivals
     ("C4", 200, {}, 6, 0.9, 16),                           # 16 lanes per document (inc_group_kernel<16>)
     ("C2", 120, {}, 8, 0.9, 64),                           # one document per wave (inc_group_kernel<64>)
-    ("C4", 200, {}, 8, 0.9, 8),                            # up to 8 changes per call: some documents handed to the wave kernel
+    ("C4", 200, {}, 8, 0.9, 8),                            # up to 8 changes per call: the rounds of over 8 ops deferred to the wave kernel (nno > G)
     ("C3", 40, {"changes_per_actor": 240}, 2, 0.9, 8),     # text: inserts / deletes on the resident element order
     ("C3", 20, {"changes_per_actor": 30, "arrival": 2, "shuffle_pct": 20}, 3, True, 8),   # text, shuffled arrivals
     # rounds longer than the group passes hold (> 8 changes or > 64 ops): the one-lane pass
